@@ -15,8 +15,13 @@ sampler: T=0.6, top-k=40; --greedy for argmax) run for every token.
 Data: synthetic random prompts, random-init weights of the named architecture
 (no network in this environment).
 
-Usage:  python bench.py [--gpus N --steps K --warmup W]
-        python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+A plain run sets up, warms up, times the steps and prints the result line.
+`--dump-outputs DIR` also writes the tokens of the last timed step to
+DIR/tokens.npy.  `--full` adds what the headline figure does not need: at
+N > 1 the token-for-token check of the pipeline against one stage.
+
+Usage:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+        python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N [--full]
 """
 from __future__ import annotations
 
@@ -72,7 +77,16 @@ def parse():
     p.add_argument("--greedy", action="store_true")
     p.add_argument("--no-graphs", action="store_true")
     p.add_argument("--seed", type=int, default=0)
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned to its caller "
+                        "(the generated token ids, one row per sequence) as DIR/tokens.npy in float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: at N > 1 the token check of "
+                        "the last timed session against a 1-stage engine (BENCH_CHECK=0 skips it)")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
 
 
 def auto_groups(args, P: int) -> int:
@@ -249,8 +263,10 @@ def main() -> int:
             out["pg_world_size"] = ranks[0]["pg_world"]
             out["data_plane_comms"] = sum(r["comms"] for r in ranks)
             out["rank_devices"] = [r["device"] for r in ranks]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_out[0], args.gen)
         rc = 0
-        if N > 1 and os.environ.get("BENCH_CHECK", "1") != "0":
+        if args.full and N > 1 and os.environ.get("BENCH_CHECK", "1") != "0":
             # outside the timed region: the pipeline's tokens of the last timed
             # session against a 1-stage engine on this rank's own GPU
             chk = check_against_one_gpu(cfg, eng, prompts, sp, last_out[0])
@@ -273,6 +289,26 @@ def main() -> int:
         else:
             eng.worker_loop()
     return rc if rank == 0 else 0
+
+
+def dump_outputs(path: str, tokens, gen: int) -> None:
+    """The last timed step's return value as path/tokens.npy: float32
+    [sequences, gen] of generated token ids (exact in float32: ids < 2^24), in
+    prompt order; a sequence that stopped early is padded with -1.  Above
+    64 MB a fixed (seeded) sample of the sequences is written, still in prompt
+    order.  Prompts, weights and sampler draws are seeded, so the same
+    arguments give the same inputs in every run."""
+    import numpy as np
+
+    rows = list(range(len(tokens)))
+    cap = max(1, (64_000_000 - 4096) // (4 * max(gen, 1)))  # file size incl. the .npy header
+    if len(rows) > cap:
+        rows = sorted(np.random.default_rng(0).choice(len(rows), cap, replace=False).tolist())
+    arr = np.full((len(rows), gen), -1.0, dtype=np.float32)
+    for i, r in enumerate(rows):
+        arr[i, :len(tokens[r])] = tokens[r][:gen]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "tokens.npy"), arr)
 
 
 def check_against_one_gpu(cfg, eng, prompts, sp, got) -> dict:

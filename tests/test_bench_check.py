@@ -1,4 +1,4 @@
-"""bench.py at N > 1 checks its own tokens: after the timed region rank 0
+"""bench.py --full at N > 1 checks its own tokens: after the timed region rank 0
 re-generates the first groups of the last session on a 1-stage engine on its
 own device and reports `pipeline_matches_1gpu`; a mismatch exits non-zero.
 The driver's multi-GPU scaling run is the only hardware execution the RCCL
@@ -30,7 +30,7 @@ def _bench(world, extra, env_extra=None, timeout=400):
     env.update(env_extra or {})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world), "--steps", "1", "--warmup", "0"] + extra
+           "--gpus", str(world), "--steps", "1", "--warmup", "0", "--full"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     return r, (json.loads(lines[-1]) if lines else None)

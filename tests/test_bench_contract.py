@@ -52,6 +52,32 @@ def test_bench_json_contract(n, dp):
         # every rank is on 2 edge groups (fwd in / fwd out or the return edge), P = 1 on none
         P = n // dp
         assert d["data_plane_comms"] == (2 * n if P > 1 else 0)
+    # a plain run does only what the headline needs: the token check is behind --full
+    assert "pipeline_matches_1gpu" not in d
+
+
+def test_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's tokens as float32
+    [sequences, gen]; the same arguments give the same tokens in a second
+    process (seeded prompts, weights and sampler draws)."""
+    import numpy as np
+
+    got = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--device", "cpu",
+                            "--model", "gpt2-test", "--batch", "3", "--prompt", "4", "--gen", "5",
+                            "--steps", "2", "--warmup", "0", "--dump-outputs", str(out)],
+                           env=dict(os.environ, OMP_NUM_THREADS="1"), capture_output=True, text=True,
+                           timeout=300, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1, r.stdout
+        assert sorted(os.listdir(out)) == ["tokens.npy"]
+        got.append(np.load(out / "tokens.npy"))
+    a, b = got
+    assert a.dtype == np.float32 and a.shape == (3, 5)
+    assert (a == np.floor(a)).all() and a.min() >= 0 and a.max() < 1000  # whole ids of the 1000-word vocabulary, nothing padded
+    assert (a == b).all()
 
 
 def test_auto_microbatch_groups():
