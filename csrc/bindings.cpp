@@ -64,7 +64,7 @@ hipError_t lsd_attn_oproj(const bf16* q, long ldq, const bf16* kc, const bf16* v
 int lsd_gemv_ok(int M, int K, int epi, int norm);
 void lsd_gemv_set_nt(int v);
 hipError_t lsd_gemv(const lsd::GemvParams* p, int epi, int norm, hipStream_t st);
-hipError_t lsd_apply_rows(const int64_t* args, int b, hipStream_t st);
+hipError_t lsd_apply_rows(const int64_t* args, int nargs, int b, hipStream_t st);
 hipError_t lsd_silu_mul(const lsd_bf16_t* y, long ldy, lsd_bf16_t* out, long ldo, int M, int F, hipStream_t st);
 hipError_t lsd_qkv_post(const float* y, long ldy, const lsd_bf16_t* bias, const int* tslot, const int* tpos,
                         const float* rope, lsd_bf16_t* q, lsd_bf16_t* kc, lsd_bf16_t* vc, int M, int q_size,
@@ -72,7 +72,8 @@ hipError_t lsd_qkv_post(const float* y, long ldy, const lsd_bf16_t* bias, const 
 hipError_t lsd_sample(const float* logits, long ld, int B, int V, const float* temp,
                       const int* topk, const int* greedy, const long long* seeds,
                       long long* step, int* out, int advance, const int* active, int* pos,
-                      const float* segmax, long ldseg, hipStream_t st);
+                      const float* segmax, long ldseg, const float* top_p, const float* min_p,
+                      hipStream_t st);
 }
 
 namespace {
@@ -604,7 +605,9 @@ void sample_launch(const torch::Tensor& logits, int64_t V, const torch::Tensor& 
                    torch::Tensor& step, torch::Tensor& out, bool advance,
                    const c10::optional<torch::Tensor>& active = c10::nullopt,
                    const c10::optional<torch::Tensor>& pos = c10::nullopt,
-                   const c10::optional<torch::Tensor>& segmax = c10::nullopt) {
+                   const c10::optional<torch::Tensor>& segmax = c10::nullopt,
+                   const c10::optional<torch::Tensor>& top_p = c10::nullopt,
+                   const c10::optional<torch::Tensor>& min_p = c10::nullopt) {
   need(logits, torch::kFloat32, "logits");
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V <= logits.size(1) && V >= 1, "logits [B, >=V]");
   TORCH_CHECK(logits.stride(0) % 4 == 0 && logits.size(1) % 4 == 0, "logits row length must be a multiple of 4");
@@ -642,11 +645,21 @@ void sample_launch(const torch::Tensor& logits, int64_t V, const torch::Tensor& 
     sm = segmax->data_ptr<float>();
     ldseg = segmax->size(1);
   }
+  // per-row nucleus / min-p cuts (sample.hip); absent = disabled
+  auto rowf = [&](const c10::optional<torch::Tensor>& t, const char* what) -> const float* {
+    if (!t.has_value()) return nullptr;
+    need(*t, torch::kFloat32, what);
+    TORCH_CHECK(t->numel() == B && t->is_contiguous(), what, " must be contiguous fp32 [B]");
+    return t->data_ptr<float>();
+  };
+  const float* tpp = rowf(top_p, "top_p");
+  const float* mpp = rowf(min_p, "min_p");
   check_hip(lsd_sample(logits.data_ptr<float>(), logits.stride(0), B, V, temp.data_ptr<float>(),
                        topk.data_ptr<int>(), greedy.data_ptr<int>(),
                        reinterpret_cast<const long long*>(seeds.data_ptr<int64_t>()),
                        reinterpret_cast<long long*>(step.data_ptr<int64_t>()),
-                       out.data_ptr<int>(), advance ? 1 : 0, act, pp, sm, ldseg, cur_stream()), "sample");
+                       out.data_ptr<int>(), advance ? 1 : 0, act, pp, sm, ldseg, tpp, mpp, cur_stream()),
+            "sample");
 }
 
 // out[m, 16 j + i] = silu(y[m, 32 j + i]) * y[m, 32 j + 16 + i]: the SiLU * up
@@ -694,8 +707,9 @@ torch::Tensor qkv_post(torch::Tensor y, c10::optional<torch::Tensor> bias, torch
 // elementwise.hip lsd_apply_rows (CPU tensor), on the current stream.
 void apply_rows(torch::Tensor args, int64_t b) {
   TORCH_CHECK(args.device().is_cpu() && args.scalar_type() == torch::kInt64 && args.is_contiguous() &&
-                  args.numel() == 12, "apply_rows: args must be a contiguous CPU int64[12] record");
-  check_hip(lsd_apply_rows(args.data_ptr<int64_t>(), (int)b, cur_stream()), "apply_rows");
+                  (args.numel() == 12 || args.numel() == 14),
+              "apply_rows: args must be a contiguous CPU int64[12] (or [14], with top_p / min_p) record");
+  check_hip(lsd_apply_rows(args.data_ptr<int64_t>(), (int)args.numel(), (int)b, cur_stream()), "apply_rows");
 }
 
 torch::Tensor silu_mul(torch::Tensor y) {
@@ -711,9 +725,11 @@ torch::Tensor silu_mul(torch::Tensor y) {
 
 torch::Tensor sample(torch::Tensor logits, int64_t V, torch::Tensor temp, torch::Tensor topk,
                      torch::Tensor greedy, torch::Tensor seeds, torch::Tensor step,
-                     c10::optional<torch::Tensor> segmax) {
+                     c10::optional<torch::Tensor> segmax, c10::optional<torch::Tensor> top_p,
+                     c10::optional<torch::Tensor> min_p) {
   auto out = torch::empty({logits.size(0)}, logits.options().dtype(torch::kInt32));
-  sample_launch(logits, V, temp, topk, greedy, seeds, step, out, false, c10::nullopt, c10::nullopt, segmax);
+  sample_launch(logits, V, temp, topk, greedy, seeds, step, out, false, c10::nullopt, c10::nullopt, segmax, top_p,
+                min_p);
   return out;
 }
 
@@ -724,8 +740,9 @@ torch::Tensor sample(torch::Tensor logits, int64_t V, torch::Tensor temp, torch:
 void sample_into(torch::Tensor logits, int64_t V, torch::Tensor temp, torch::Tensor topk,
                  torch::Tensor greedy, torch::Tensor seeds, torch::Tensor step, torch::Tensor out,
                  c10::optional<torch::Tensor> active, c10::optional<torch::Tensor> pos,
-                 c10::optional<torch::Tensor> segmax) {
-  sample_launch(logits, V, temp, topk, greedy, seeds, step, out, true, active, pos, segmax);
+                 c10::optional<torch::Tensor> segmax, c10::optional<torch::Tensor> top_p,
+                 c10::optional<torch::Tensor> min_p) {
+  sample_launch(logits, V, temp, topk, greedy, seeds, step, out, true, active, pos, segmax, top_p, min_p);
 }
 
 }  // namespace
@@ -752,10 +769,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_prefill", &attn_prefill);
   m.def("attn_oproj", &attn_oproj);
   m.def("sample", &sample, py::arg("logits"), py::arg("V"), py::arg("temp"), py::arg("topk"),
-        py::arg("greedy"), py::arg("seeds"), py::arg("step"), py::arg("segmax") = py::none());
+        py::arg("greedy"), py::arg("seeds"), py::arg("step"), py::arg("segmax") = py::none(),
+        py::arg("top_p") = py::none(), py::arg("min_p") = py::none());
   m.def("sample_into", &sample_into, py::arg("logits"), py::arg("V"), py::arg("temp"), py::arg("topk"),
         py::arg("greedy"), py::arg("seeds"), py::arg("step"), py::arg("out"), py::arg("active"),
-        py::arg("pos") = py::none(), py::arg("segmax") = py::none());
+        py::arg("pos") = py::none(), py::arg("segmax") = py::none(), py::arg("top_p") = py::none(),
+        py::arg("min_p") = py::none());
   m.def("gemv", [](torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, int64_t epi,
                    int64_t norm, c10::optional<torch::Tensor> gamma, c10::optional<torch::Tensor> beta,
                    double eps, c10::optional<torch::Tensor> resid, c10::optional<torch::Tensor> kc,

@@ -28,6 +28,14 @@
 //           from the segment maxima (25 KB per GPT-2 row instead of 200 KB)
 //           and only the segments whose maximum reaches it are read -- the
 //           same candidate superset rule, so the same draws.
+//   top-p / min-p (per row, optional): a prefix cut of the sorted top-k list
+//           before the draw.  With e_i = exp(v_i/T - v_0/T), c_i their running
+//           sum: min-p keeps the n_m entries with e_i >= min_p (p_i / p_max),
+//           top-p the shortest prefix n_p with c >= top_p * total (of
+//           the top-k-renormalised distribution); the draw runs over the first
+//           n = max(1, min(n_p, n_m)) entries, target = u * c_{n-1}.  Rows with
+//           top_p >= 1 and min_p <= 0 (or null arrays) take the uncut
+//           arithmetic unchanged.  Pure nucleus sampling: top_k = 1024.
 #include "common.h"
 
 namespace lsd {
@@ -161,7 +169,9 @@ __global__ __launch_bounds__(NT) void sample_kernel(const float* __restrict__ lo
                                                     int* __restrict__ out, int advance,
                                                     const int* __restrict__ active,
                                                     int* __restrict__ pos,
-                                                    const float* __restrict__ segmax, long ldseg) {
+                                                    const float* __restrict__ segmax, long ldseg,
+                                                    const float* __restrict__ top_p,
+                                                    const float* __restrict__ min_p) {
   __shared__ unsigned hist[4096];
   __shared__ __attribute__((aligned(16))) float cval[SMAX];
   __shared__ __attribute__((aligned(16))) int cidx[SMAX];
@@ -201,6 +211,12 @@ __global__ __launch_bounds__(NT) void sample_kernel(const float* __restrict__ lo
     return;
   }
 
+  // the nucleus / min-p cuts of a sampled row: loaded here, ahead of the row
+  // read like the parameters above (before the greedy branch they would put
+  // four more scalar loads in front of its first wait)
+  const float tp = top_p ? top_p[row] : 1.f;
+  const float mp = min_p ? min_p[row] : 0.f;
+  const bool cut = tp < 1.f || mp > 0.f;  // uniform; false: the uncut draw below, bit for bit
   const int k = min(max(k_req, 1), min(SMAX, V));
   // ---- fast path (k <= 64): threshold from segment maxima, then filter.
   // The 64 segments are the 16-thread groups of the row visit; the k-th
@@ -471,7 +487,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const float* __restrict__ lo
     const float u = counter_uniform(seed_r, step_r);
     const float p0 = e0 < k ? __expf(v[0] / T - x0) : 0.f;
     const float p1 = e0 + 1 < k ? __expf(v[1] / T - x0) : 0.f;
-    const float target = u * wave_sum(p0 + p1);
+    const float tot = wave_sum(p0 + p1);
     float pre = p0 + p1;  // inclusive prefix of the lane pairs
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -479,9 +495,23 @@ __global__ __launch_bounds__(NT) void sample_kernel(const float* __restrict__ lo
       if (tid >= d) pre += o;
     }
     const float c1 = pre, c0 = pre - p1;
-    const unsigned long long h0 = __ballot(e0 < k && c0 >= target);
-    const unsigned long long h1 = __ballot(e0 + 1 < k && c1 >= target);
-    int pick = k - 1;
+    int n = k;                // entries the draw runs over
+    float target = u * tot;   // u * their mass
+    if (cut) {
+      // min-p: the entries with e_i >= min_p (a prefix of the sorted list);
+      // top-p: through the first entry whose running sum reaches top_p * total
+      const int n_m = __popcll(__ballot(e0 < k && p0 >= mp)) + __popcll(__ballot(e0 + 1 < k && p1 >= mp));
+      const float thr = tp * tot;
+      const unsigned long long g0 = __ballot(e0 < k && c0 >= thr);
+      const unsigned long long g1 = __ballot(e0 + 1 < k && c1 >= thr);
+      const int m0 = g0 ? 2 * __builtin_ctzll(g0) : k, m1 = g1 ? 2 * __builtin_ctzll(g1) + 1 : k;
+      const int n_p = tp < 1.f ? min(min(m0, m1) + 1, k) : k;
+      n = max(1, min(n_p, n_m));
+      target = u * __shfl((n - 1) & 1 ? c1 : c0, (n - 1) >> 1, 64);
+    }
+    const unsigned long long h0 = __ballot(e0 < n && c0 >= target);
+    const unsigned long long h1 = __ballot(e0 + 1 < n && c1 >= target);
+    int pick = n - 1;
     const int l0 = h0 ? __builtin_ctzll(h0) : 64, l1 = h1 ? __builtin_ctzll(h1) : 64;
     if (l0 < 64 || l1 < 64) pick = l0 <= l1 ? 2 * l0 : 2 * l1 + 1;
     const int win = __shfl(pick & 1 ? ix[1] : ix[0], pick >> 1, 64);
@@ -522,10 +552,47 @@ __global__ __launch_bounds__(NT) void sample_kernel(const float* __restrict__ lo
       const float e = i < k ? __expf(cval[i] / T - x0) : 0.f;
       tot += wave_sum(e);
     }
-    const float target = u * tot;
+    int n = k;               // entries the draw runs over
+    float target = u * tot;  // u * their mass
+    if (cut) {
+      // the same chunked running sum as the draw below: n_m = entries with
+      // e_i >= min_p (a prefix), n_p = through the first c_i >= top_p * total
+      const float thr = tp * tot;
+      int n_m = 0, n_p = k;
+      bool found = tp >= 1.f;
+      float run = 0.f;
+      for (int base = 0; base < k; base += 64) {
+        const int i = base + tid;
+        const float e = i < k ? __expf(cval[i] / T - x0) : 0.f;
+        float pre = e;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const float o = __shfl_up(pre, d, 64);
+          if (tid >= d) pre += o;
+        }
+        n_m += __popcll(__ballot(i < k && e >= mp));
+        const unsigned long long hit = __ballot(i < k && run + pre >= thr);
+        if (!found && hit) { found = true; n_p = base + __builtin_ctzll(hit) + 1; }
+        run += __shfl(pre, 63, 64);
+      }
+      n = max(1, min(n_p, n_m));
+      run = 0.f;  // target = u * c_{n-1}
+      for (int base = 0;; base += 64) {
+        const int i = base + tid;
+        const float e = i < k ? __expf(cval[i] / T - x0) : 0.f;
+        float pre = e;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const float o = __shfl_up(pre, d, 64);
+          if (tid >= d) pre += o;
+        }
+        if (n - 1 < base + 64) { target = u * (run + __shfl(pre, (n - 1) & 63, 64)); break; }
+        run += __shfl(pre, 63, 64);
+      }
+    }
     float run = 0.f;
-    int pick = k - 1;
-    for (int base = 0; base < k; base += 64) {
+    int pick = n - 1;
+    for (int base = 0; base < n; base += 64) {
       const int i = base + tid;
       float e = i < k ? __expf(cval[i] / T - x0) : 0.f;
       // inclusive prefix within the wave
@@ -536,7 +603,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const float* __restrict__ lo
         if (tid >= d) pre += o;
       }
       const float c = run + pre;
-      const unsigned long long hit = __ballot(i < k && c >= target);
+      const unsigned long long hit = __ballot(i < n && c >= target);
       if (hit) { pick = base + __builtin_ctzll(hit); break; }
       run += __shfl(pre, 63, 64);
     }
@@ -554,14 +621,16 @@ using namespace lsd;
 
 // advance != 0: also step[row] += active[row] (1 when active is null) after
 // the draw -- the decode step's sampler-counter advance (pad rows stay put),
-// folded in instead of a conversion copy + add kernel
+// folded in instead of a conversion copy + add kernel.  top_p / min_p: per-row
+// nucleus / min-p cuts, either may be null (disabled)
 extern "C" hipError_t lsd_sample(const float* logits, long ld, int B, int V, const float* temp,
                                  const int* topk, const int* greedy, const long long* seeds,
                                  long long* step, int* out, int advance, const int* active,
-                                 int* pos, const float* segmax, long ldseg, hipStream_t st) {
+                                 int* pos, const float* segmax, long ldseg, const float* top_p,
+                                 const float* min_p, hipStream_t st) {
   if (B == 0) return hipSuccess;
   if (ld % 4 != 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(NT), 0, st, logits, ld, V, temp, topk, greedy,
-                     seeds, step, out, advance, active, pos, segmax, ldseg);
+                     seeds, step, out, advance, active, pos, segmax, ldseg, top_p, min_p);
   return hipGetLastError();
 }

@@ -36,7 +36,7 @@ void lsd_rccl_recv_raw(int64_t h, void* ptr, size_t bytes, int peer, hipStream_t
 void lsd_loop_recv_raw(int64_t chan, void* ptr, size_t bytes, hipStream_t st);          // loop_fabric.cpp
 void lsd_loop_io_wait(int64_t io);
 void lsd_loop_io_done(int64_t io);
-extern "C" hipError_t lsd_apply_rows(const int64_t* args, int b, hipStream_t st);  // elementwise.hip
+extern "C" hipError_t lsd_apply_rows(const int64_t* args, int nargs, int b, hipStream_t st);  // elementwise.hip
 
 namespace {
 
@@ -64,6 +64,7 @@ enum : int {
   X_ROWS_SRC,    //   pinned host source of the packed row state
   X_ROWS_BYTES,  //   bytes
   X_ROWS_B,      //   bucket rows
+  X_ROWS_NARGS,  //   words of the record: 12, or 14 with the top_p / min_p row vectors (0 = 12)
   X_FIELDS
 };
 
@@ -90,7 +91,8 @@ void lsd_register_exec(py::module& m) {
         hip_check(hipMemcpyAsync(reinterpret_cast<void*>(args[2]), reinterpret_cast<const void*>(it[X_ROWS_SRC]),
                                  (size_t)it[X_ROWS_BYTES], hipMemcpyHostToDevice, st),
                   "hipMemcpyAsync");
-        hip_check(lsd_apply_rows(args, (int)it[X_ROWS_B], st), "apply_rows");
+        hip_check(lsd_apply_rows(args, it[X_ROWS_NARGS] ? (int)it[X_ROWS_NARGS] : 12, (int)it[X_ROWS_B], st),
+                  "apply_rows");
       }
       if (!it[X_GRAPH]) throw std::invalid_argument("exec_items: item without a graph");
       if (it[X_IO]) lsd_loop_io_wait(it[X_IO]);  // instant: the caller pre-waited the step's ops

@@ -58,6 +58,10 @@ def main(argv=None) -> int:
     g.add_argument("--greedy", action="store_true")
     g.add_argument("--temperature", type=float, default=0.6)
     g.add_argument("--top-k", type=int, default=40)
+    g.add_argument("--top-p", type=float, default=1.0,
+                   help="nucleus cut inside the top-k candidates (pure nucleus: --top-k 1024)")
+    g.add_argument("--min-p", type=float, default=0.0,
+                   help="keep tokens at least this fraction as likely as the most likely one")
     g.add_argument("--seed", type=int)
     args = p.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(levelname)s %(message)s")
@@ -72,7 +76,8 @@ def main(argv=None) -> int:
             llm.engine.worker_loop()
             return 0
         out = llm.generate_text(args.prompt, args.max_new_tokens, greedy=args.greedy,
-                                temperature=args.temperature, top_k=args.top_k, seed=args.seed)
+                                temperature=args.temperature, top_k=args.top_k, seed=args.seed,
+                                top_p=args.top_p, min_p=args.min_p)
         print(out)
         llm.engine.shutdown()
         return 0

@@ -174,7 +174,14 @@ def model_config_from_hf_json(path: str) -> ModelConfig:
 
 @dataclass
 class SamplingParams:
-    """Per-request sampling.  Defaults reproduce `server.py:187-205`."""
+    """Per-request sampling.  Defaults reproduce `server.py:187-205`.
+
+    top_p / min_p cut the sorted top-k candidates before the draw: min_p keeps
+    the tokens at least min_p times as likely as the most likely one, top_p the
+    shortest prefix holding top_p of the top-k-renormalised mass (at least one
+    token stays).  They work inside the top-k candidates and top_k is capped at
+    1024, so pure nucleus sampling is top_k=1024 with top_p.  The defaults
+    (1.0 / 0.0) disable both; greedy requests ignore them."""
 
     temperature: float = 0.6
     top_k: int = 40
@@ -182,6 +189,8 @@ class SamplingParams:
     seed: Optional[int] = None
     max_new_tokens: int = 20
     stop_at_eos: bool = False  # reference never stops early (quirk Q10)
+    top_p: float = 1.0
+    min_p: float = 0.0
 
     def validate(self) -> None:
         if self.max_new_tokens < 0:
@@ -191,6 +200,10 @@ class SamplingParams:
                 raise ValueError("temperature must be > 0 (use greedy=True for argmax)")
             if not (1 <= self.top_k <= 1024):
                 raise ValueError("top_k must be in [1, 1024]")
+            if not (0 < self.top_p <= 1):
+                raise ValueError("top_p must be in (0, 1]")
+            if not (0 <= self.min_p <= 1):
+                raise ValueError("min_p must be in [0, 1]")
 
 
 # ---------------------------------------------------------------------------

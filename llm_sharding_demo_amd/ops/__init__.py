@@ -108,7 +108,7 @@ class ReferenceBackend(Backend):
 
     def sample(self, logits, samp, vocab: int):
         return ref.sample(logits, samp.temperature, samp.top_k, samp.greedy,
-                          samp.uniforms(), vocab)
+                          samp.uniforms(), vocab, samp.top_p, samp.min_p)
 
     def sample_into(self, logits, samp, vocab: int, out, meta=None) -> None:
         """Decode step: sampled ids into `out`, then the sampler counters (and,

@@ -363,7 +363,8 @@ class HipBackend(Backend):
 
     def sample(self, logits, samp, vocab: int):
         return self.C.sample(logits, vocab, samp.temperature, samp.top_k, samp.greedy,
-                             samp.seeds, samp.step, getattr(logits, "_lsd_segmax", None))
+                             samp.seeds, samp.step, getattr(logits, "_lsd_segmax", None),
+                             samp.top_p, samp.min_p)
 
     def sample_into(self, logits, samp, vocab: int, out, meta=None) -> None:
         # one kernel: draw into `out`, advance the per-row sampler counters
@@ -371,7 +372,7 @@ class HipBackend(Backend):
         self.C.sample_into(logits, vocab, samp.temperature, samp.top_k, samp.greedy,
                            samp.seeds, samp.step, out, getattr(samp, "active", None),
                            meta.token_pos if meta is not None else None,
-                           getattr(logits, "_lsd_segmax", None))
+                           getattr(logits, "_lsd_segmax", None), samp.top_p, samp.min_p)
 
     def gather_rows(self, x, idx):
         return x.index_select(0, idx.long())

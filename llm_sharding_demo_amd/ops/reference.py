@@ -118,12 +118,21 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
 
 
 def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
-           greedy: torch.Tensor, uniforms: torch.Tensor, vocab: int) -> torch.Tensor:
+           greedy: torch.Tensor, uniforms: torch.Tensor, vocab: int,
+           top_p: Optional[torch.Tensor] = None, min_p: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-row sampler.  Reference semantics (server.py:187-206):
     logits/T -> topk(k) -> softmax over the k values -> draw -> map to vocab id.
     `uniforms` [B] in [0,1) drive the draw (inverse CDF over the top-k sorted
     descending), so the result is a deterministic function of its inputs.
     greedy rows return argmax (lowest index on ties).
+
+    top_p / min_p [B] (optional) cut the sorted candidates to a prefix before
+    the draw.  With e_i = exp(v_i - v_0) and c their running sum: min_p keeps
+    the n_m entries with e_i >= min_p (p_i / p_max), top_p the shortest prefix
+    n_p with c >= top_p * total (of the top-k-renormalised distribution; all k
+    when top_p >= 1); the draw is the inverse CDF over the first
+    n = max(1, min(n_p, n_m)) entries.  A row with top_p >= 1 and min_p <= 0
+    (or None) takes the uncut path unchanged.
     """
     B = logits.shape[0]
     lg = logits[:, :vocab].float()
@@ -138,6 +147,22 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
         # stable ordering for ties: by value desc then index asc
         order = sorted(range(k), key=lambda j: (-float(vals[j]), int(idx[j])))
         vals, idx = vals[order], idx[order]
+        tp = float(top_p[r]) if top_p is not None else 1.0
+        mp = float(min_p[r]) if min_p is not None else 0.0
+        if tp < 1.0 or mp > 0.0:
+            e = torch.exp(vals - vals[0])
+            c = torch.cumsum(e, 0)
+            n_m = int((e >= mp).sum())
+            n_p = k
+            if tp < 1.0:
+                hit = torch.nonzero(c >= tp * float(e.sum()))
+                n_p = int(hit[0]) + 1 if hit.numel() else k
+            n = max(1, min(n_p, n_m))
+            c = c[:n]
+            u = float(uniforms[r]) * float(c[-1])
+            j = int(torch.searchsorted(c, torch.tensor([u], dtype=c.dtype)).clamp(max=n - 1))
+            out[r] = int(idx[j])
+            continue
         p = torch.softmax(vals, dim=-1)
         c = torch.cumsum(p, 0)
         u = float(uniforms[r]) * float(c[-1])

@@ -167,8 +167,9 @@ class SamplingView:
     """Sampler parameters of a decode bucket: views of the group's persistent
     per-row tensors (graph-capturable); pad rows never advance."""
 
-    def __init__(self, temperature, top_k, greedy, seeds, step, active):
+    def __init__(self, temperature, top_k, greedy, seeds, step, active, top_p=None, min_p=None):
         self.temperature, self.top_k, self.greedy = temperature, top_k, greedy
+        self.top_p, self.min_p = top_p, min_p
         self.seeds, self.step, self.active = seeds, step, active
         self.num_rows = temperature.shape[0]
 
@@ -193,9 +194,15 @@ class GroupState(racecheck.Shared):
         self.pos = torch.zeros(cap, **i32)
         self.active = torch.zeros(cap, **i32)
         self.cu = torch.arange(cap + 1, **i32)
+        # any row of the current composition with a top-p / min-p cut (last
+        # stage): the sampler gets the two vectors only then, and the decode
+        # graphs are keyed on it -- all-default traffic runs the sampler without them
+        self.cut = False
         if w.last:
             self.temp = torch.ones(cap, dtype=torch.float32, device=dev)
             self.topk = torch.ones(cap, **i32)
+            self.topp = torch.ones(cap, dtype=torch.float32, device=dev)   # nucleus cut (1 = off)
+            self.minp = torch.zeros(cap, dtype=torch.float32, device=dev)  # min-p cut (0 = off)
             self.greedy = torch.ones(cap, **i32)
             self.seeds = torch.zeros(cap, dtype=torch.int64, device=dev)
             self.sstep = torch.zeros(cap, dtype=torch.int64, device=dev)
@@ -273,8 +280,9 @@ class GroupState(racecheck.Shared):
         return m
 
     def samp(self, b: int) -> SamplingView:
+        tp, mp = (self.topp[:b], self.minp[:b]) if self.cut else (None, None)
         return SamplingView(self.temp[:b], self.topk[:b], self.greedy[:b], self.seeds[:b],
-                            self.sstep[:b], self.active[:b])
+                            self.sstep[:b], self.active[:b], tp, mp)
 
 
 class StepStats:
@@ -605,7 +613,8 @@ class StageWorker(racecheck.Shared):
             if self.P > 1 and not io:
                 return False
             gs = self.groups[gp.g]
-            key = (gp.b, gp.ctxb, io)
+            cut = gs.cut if gp.rows is None else self._rows_cut(gp.rows)  # after this item's change
+            key = (gp.b, gp.ctxb, io, cut)
             ent = gs.graphs.get(key)
             if ent is None:
                 return False
@@ -665,7 +674,8 @@ class StageWorker(racecheck.Shared):
                     # composition change: packed row state copied and applied
                     # after the readout, ahead of the graph (csrc/stage_exec.cpp)
                     slot, args = self._rows_pack(gs, gp.rows, gp.b)
-                    d[14], d[15], d[16], d[17] = args.data_ptr(), slot[0].data_ptr(), 4 * (10 * gs.cap + 1), gp.b
+                    d[14], d[15], d[16], d[17] = args.data_ptr(), slot[0].data_ptr(), 4 * self._rows_words(gs.cap), gp.b
+                    d[18] = args.numel()
                     packed.append((slot, lane))
                     self.native_changes += 1
                 rows.append(d)
@@ -903,7 +913,8 @@ class StageWorker(racecheck.Shared):
                 lf._lsd_segmax = seg[b:]
             fc = [ch[i] for i in finals]
             samp = SamplingState([c.temperature for c in fc], [c.top_k for c in fc],
-                                 [c.greedy for c in fc], [c.seed for c in fc], dev)
+                                 [c.greedy for c in fc], [c.seed for c in fc], dev,
+                                 [c.top_p for c in fc], [c.min_p for c in fc])
             gs.tokret[b: b + J].copy_(be.sample(lf, samp, V))
         self.mixed_items += 1
 
@@ -914,6 +925,7 @@ class StageWorker(racecheck.Shared):
         prefill sample)."""
         dev, rows = self.device, gp.rows
         n, b = gp.n, max(gp.b, gp.n)
+        gs.cut = self._rows_cut(rows)
         pad = b - n
         sl = [r.slot for r in rows] + [self.scratch_slot] * pad
         pos = [r.pos for r in rows] + [0] * pad
@@ -923,7 +935,7 @@ class StageWorker(racecheck.Shared):
         if dev.type == "cuda":
             if hasattr(self.stage.backend, "C"):
                 slot, args = self._rows_pack(gs, rows, b)
-                words = 10 * gs.cap + 1
+                words = self._rows_words(gs.cap)
                 gs.rows_dev.copy_(slot[0][:words], non_blocking=True)
                 self.stage.backend.C.apply_rows(args, b)
                 slot[1].record()
@@ -939,6 +951,10 @@ class StageWorker(racecheck.Shared):
                               non_blocking=True)
             gs.topk[:b].copy_(_h2d([r.top_k for r in rows] + [1] * pad, torch.int32, dev),
                               non_blocking=True)
+            gs.topp[:b].copy_(_h2d([r.top_p for r in rows] + [1.0] * pad, torch.float32, dev),
+                              non_blocking=True)
+            gs.minp[:b].copy_(_h2d([r.min_p for r in rows] + [0.0] * pad, torch.float32, dev),
+                              non_blocking=True)
             gs.greedy[:b].copy_(_h2d([1 if r.greedy else 0 for r in rows] + [1] * pad, torch.int32,
                                      dev), non_blocking=True)
             gs.seeds[:b].copy_(_h2d([r.seed for r in rows] + [0] * pad, torch.int64, dev),
@@ -950,18 +966,29 @@ class StageWorker(racecheck.Shared):
             gathered = gs.tin.index_select(0, src.to(dev, non_blocking=True))
             gs.tin[:b].copy_(gathered)
 
+    def _rows_cut(self, rows) -> bool:
+        """Whether the sampler of this composition needs the top-p / min-p vectors."""
+        return self.last and any(r.top_p < 1.0 or r.min_p > 0.0 for r in rows)
+
     _ROWS_PIN = 4  # packed row-state buffers per group: reused 4 composition changes later
+
+    def _rows_words(self, cap: int) -> int:
+        """int32 words of a group's packed row state: the last stage's also
+        carries the top-p / min-p columns."""
+        return (12 if self.last else 10) * cap + 1
 
     def _rows_pack(self, gs: GroupState, rows, b: int):
         """Composition change on a GPU, host side: the new rows' state packed
         into one pinned int32 buffer in the layout of elementwise.hip
         apply_rows_kernel (fixed offsets by the group capacity, so the device
         copy and the kernel depend on the bucket only), and the kernel's
-        argument record.  -> (pinned ring slot, CPU int64[12] record); the
+        argument record.  -> (pinned ring slot, CPU int64 record: 14 words on
+        the last stage, which owns the top-p / min-p vectors, else 12); the
         caller enqueues the copy + kernel (eagerly, or in exec_items) and then
         records the slot's event."""
         cap = gs.cap
-        words = 10 * cap + 1
+        gs.cut = self._rows_cut(rows)
+        words = self._rows_words(cap)
         if len(gs.rows_pin) < self._ROWS_PIN:
             gs.rows_pin.append([torch.empty(words, dtype=torch.int32, pin_memory=True), torch.cuda.Event(), False])
         slot = gs.rows_pin[gs.rows_pin_next % len(gs.rows_pin)]
@@ -979,6 +1006,8 @@ class StageWorker(racecheck.Shared):
                 a[f0 + 2 * cap: f0 + 2 * cap + n] = np.asarray([r.temperature for r in rows], np.float32).view(np.int32)
                 a[f0 + 3 * cap: f0 + 3 * cap + n] = [r.top_k for r in rows]
                 a[f0 + 4 * cap: f0 + 4 * cap + n] = [1 if r.greedy else 0 for r in rows]
+                a[f0 + 6 * cap: f0 + 6 * cap + n] = np.asarray([r.top_p for r in rows], np.float32).view(np.int32)
+                a[f0 + 7 * cap: f0 + 7 * cap + n] = np.asarray([r.min_p for r in rows], np.float32).view(np.int32)
                 a64 = a[: 4 * cap].view(np.int64)
                 a64[:n] = [r.seed for r in rows]
                 a64[cap: cap + n] = [r.step for r in rows]
@@ -986,13 +1015,14 @@ class StageWorker(racecheck.Shared):
                 a[f0 + 5 * cap: f0 + 5 * cap + n] = [r.src for r in rows]
         if gs.rows_dev is None:
             gs.rows_dev = torch.empty(words, dtype=torch.int32, device=self.device)
-            gs.rows_args = torch.zeros(12, dtype=torch.int64)
+            gs.rows_args = torch.zeros(14 if self.last else 12, dtype=torch.int64)
         r = gs.rows_args.numpy()
         ptr = lambda t: t.data_ptr()  # noqa: E731
         r[0], r[1], r[2] = cap, self.scratch_slot, ptr(gs.rows_dev)
         r[3], r[4], r[5] = ptr(gs.slots), ptr(gs.pos), ptr(gs.active)
         if self.last:
             r[6], r[7], r[8], r[9], r[10] = ptr(gs.temp), ptr(gs.topk), ptr(gs.greedy), ptr(gs.seeds), ptr(gs.sstep)
+            r[12], r[13] = ptr(gs.topp), ptr(gs.minp)
         r[11] = ptr(gs.tin) if self.first else 0
         return slot, gs.rows_args
 
@@ -1002,14 +1032,16 @@ class StageWorker(racecheck.Shared):
         int32 pairs at an even offset) uploaded through the group's pinned
         staging ring, then device copies into the row state -- instead of one
         pinned host tensor per field (profiles/r5_profile_issue.log).  The
-        int64 fields start at int32 offset 6 b, so their views are aligned."""
+        int64 fields start at int32 offset 8 b, so their views are aligned."""
         i32 = np.int32
         parts = [np.asarray(sl, i32), np.asarray(pos, i32), np.asarray(act, i32)]
         if self.last:
             parts += [np.asarray([r.temperature for r in rows] + [1.0] * pad, np.float32).view(i32),
                       np.asarray([r.top_k for r in rows] + [1] * pad, i32),
-                      np.asarray([1 if r.greedy else 0 for r in rows] + [1] * pad, i32)]
-            # the int64 fields start at int32 offset 6 b: 8-byte aligned
+                      np.asarray([1 if r.greedy else 0 for r in rows] + [1] * pad, i32),
+                      np.asarray([r.top_p for r in rows] + [1.0] * pad, np.float32).view(i32),
+                      np.asarray([r.min_p for r in rows] + [0.0] * pad, np.float32).view(i32)]
+            # the int64 fields start at int32 offset 8 b: 8-byte aligned
             parts += [np.asarray([r.seed for r in rows] + [0] * pad, np.int64).view(i32),
                       np.asarray([r.step for r in rows] + [0] * pad, np.int64).view(i32)]
         if self.first:
@@ -1027,7 +1059,9 @@ class StageWorker(racecheck.Shared):
             gs.temp[:b].copy_(buf[o: o + b].view(torch.float32))
             gs.topk[:b].copy_(buf[o + b: o + 2 * b])
             gs.greedy[:b].copy_(buf[o + 2 * b: o + 3 * b])
-            o += 3 * b
+            gs.topp[:b].copy_(buf[o + 3 * b: o + 4 * b].view(torch.float32))
+            gs.minp[:b].copy_(buf[o + 4 * b: o + 5 * b].view(torch.float32))
+            o += 5 * b
             gs.seeds[:b].copy_(buf[o: o + 2 * b].view(torch.int64))
             gs.sstep[:b].copy_(buf[o + 2 * b: o + 4 * b].view(torch.int64))
             o += 4 * b
@@ -1062,7 +1096,8 @@ class StageWorker(racecheck.Shared):
             logits = st.head(x, meta, rows=rows)
         fc = [ch[i] for i in finals]
         samp = SamplingState([c.temperature for c in fc], [c.top_k for c in fc],
-                             [c.greedy for c in fc], [c.seed for c in fc], dev)
+                             [c.greedy for c in fc], [c.seed for c in fc], dev,
+                             [c.top_p for c in fc], [c.min_p for c in fc])
         return be.sample(logits, samp, st.cfg.vocab_size)
 
     # Prefill chunks as hipGraphs (the non-steady items):
@@ -1179,7 +1214,7 @@ class StageWorker(racecheck.Shared):
         slot[2] = True
 
     def _decode(self, gp: GroupPlan, gs: GroupState, inp: torch.Tensor, io: bool = False) -> torch.Tensor:
-        key = (gp.b, gp.ctxb, io)
+        key = (gp.b, gp.ctxb, io, gs.cut)
         lane = self.lane_of(gp.g)
 
         def body():

@@ -114,7 +114,7 @@ class SamplingState:
     seeded request is reproducible regardless of batching or stage count.
     """
 
-    def __init__(self, temperature, top_k, greedy, seeds, device):
+    def __init__(self, temperature, top_k, greedy, seeds, device, top_p=None, min_p=None):
         self.device = torch.device(device)
         B = len(temperature)
         self.temperature = torch.tensor(temperature, dtype=torch.float32, device=device)
@@ -122,6 +122,13 @@ class SamplingState:
         self.greedy = torch.tensor([1 if g else 0 for g in greedy], dtype=torch.int32, device=device)
         self.seeds = torch.tensor(seeds, dtype=torch.int64, device=device)
         self.step = torch.zeros(B, dtype=torch.int64, device=device)
+        # nucleus / min-p cuts per row; None while every row is at the default
+        # (1.0 / 0.0: the sampler then runs uncut, with no extra upload)
+        self.top_p = self.min_p = None
+        if top_p is not None and any(p < 1.0 for p in top_p):
+            self.top_p = torch.tensor(top_p, dtype=torch.float32, device=device)
+        if min_p is not None and any(p > 0.0 for p in min_p):
+            self.min_p = torch.tensor(min_p, dtype=torch.float32, device=device)
         self.num_rows = B
 
     def uniforms(self) -> torch.Tensor:

@@ -43,6 +43,8 @@ class Chunk:
     top_k: int = 40
     greedy: bool = False
     seed: int = 0
+    top_p: float = 1.0
+    min_p: float = 0.0
 
     @property
     def qlen(self) -> int:
@@ -64,6 +66,8 @@ class Row:
     src: int            # stage 0: index of the row's input token in the previous
                         # item's token-return vector (kept rows: their old row;
                         # newly activated rows: prev_b + final-chunk index)
+    top_p: float = 1.0
+    min_p: float = 0.0
 
 
 @dataclass
@@ -141,6 +145,24 @@ def _steady_groups(plan: StepPlan):
 # follower as objects (631 KB: too big for a plan-ring slot, so it went over
 # gloo to each follower); as columns without the token ids -- which only a
 # replica's stage 0 reads -- ~6 / ~7 ms and 182 KB, inline in the ring.
+def _float_cols(xs):
+    """float64 column(s) of Chunks / Rows: [n] temperatures while every entry
+    has the default top_p / min_p (the common case stays as small as before),
+    else [n, 3] = (temperature, top_p, min_p)."""
+    import numpy as np
+
+    if all(x.top_p == 1.0 and x.min_p == 0.0 for x in xs):
+        return np.array([x.temperature for x in xs], dtype=np.float64)
+    return np.array([(x.temperature, x.top_p, x.min_p) for x in xs], dtype=np.float64).reshape(-1, 3)
+
+
+def _float_rows(temp):
+    """(temperature, top_p, min_p) per entry of a _float_cols column."""
+    if temp.ndim == 1:
+        return [(t, 1.0, 0.0) for t in temp.tolist()]
+    return temp.tolist()
+
+
 def _pack_group(gp: GroupPlan, ids: bool):
     import numpy as np
 
@@ -155,14 +177,14 @@ def _pack_group(gp: GroupPlan, ids: bool):
                               count=sum(len(x.ids) for x in c))
         ch = (np.array([(x.seq, x.slot, x.start, len(x.ids), x.final, x.top_k, x.greedy) for x in c],
                        dtype=np.int64).reshape(-1, 7),
-              np.array([x.temperature for x in c], dtype=np.float64),
+              _float_cols(c),
               np.array([x.seed for x in c], dtype=np.int64), tok)
     rows = None
     if gp.rows is not None:
         r = gp.rows
         rows = (np.array([(x.seq, x.slot, x.pos, x.top_k, x.greedy, x.seed, x.step, x.src) for x in r],
                          dtype=np.int64).reshape(-1, 8),
-                np.array([x.temperature for x in r], dtype=np.float64))
+                _float_cols(r))
     return (gp.g, gp.ret, gp.n, gp.b, gp.ctxb, gp.kind, gp.fwd_rows, ch, rows)
 
 
@@ -174,16 +196,17 @@ def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows) -> GroupPlan:
         ints, temp, seeds, tok = ch
         tok = tok.tolist() if tok is not None else None
         out, o = [], 0
-        for (seq, slot, start, ln, final, top_k, greedy), t, sd in zip(ints.tolist(), temp.tolist(),
-                                                                      seeds.tolist()):
+        for (seq, slot, start, ln, final, top_k, greedy), (t, tp, mp), sd in zip(ints.tolist(), _float_rows(temp),
+                                                                                 seeds.tolist()):
             out.append(Chunk(seq, slot, start, tok[o: o + ln] if tok is not None else range(ln), bool(final),
-                             t, top_k, bool(greedy), sd))
+                             t, top_k, bool(greedy), sd, tp, mp))
             o += ln
         gp.chunks = out
     if rows is not None:
         ints, temp = rows
-        gp.rows = [Row(seq, slot, pos, t, top_k, bool(greedy), seed, step, src)
-                   for (seq, slot, pos, top_k, greedy, seed, step, src), t in zip(ints.tolist(), temp.tolist())]
+        gp.rows = [Row(seq, slot, pos, t, top_k, bool(greedy), seed, step, src, tp, mp)
+                   for (seq, slot, pos, top_k, greedy, seed, step, src), (t, tp, mp) in zip(ints.tolist(),
+                                                                                            _float_rows(temp))]
     return gp
 
 

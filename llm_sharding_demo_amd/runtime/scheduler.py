@@ -518,6 +518,7 @@ class _Meta:
     req: Request
     seed: int
     samp: tuple = ()    # (temperature, top_k, greedy, seed): the chunk / row sampling fields
+    cut: tuple = (1.0, 0.0)  # (top_p, min_p): the trailing chunk / row fields
     done: bool = False  # finished by this scheduler (plain flag: the readout loop's hot path)
 
 
@@ -608,7 +609,7 @@ class Scheduler(racecheck.Shared):
         for i, req in zip(ids, reqs):
             p = req.params
             seed = p.seed if p.seed is not None else rng.getrandbits(62)
-            meta[i] = _Meta(req, seed, (p.temperature, p.top_k, p.greedy, seed))
+            meta[i] = _Meta(req, seed, (p.temperature, p.top_k, p.greedy, seed), (p.top_p, p.min_p))
             lens.append(len(req.prompt_ids))
             wants.append(p.max_new_tokens)
             stops.append(bool(p.stop_at_eos))
@@ -647,10 +648,10 @@ class Scheduler(racecheck.Shared):
         g, ret, n, b, ctxb, changed, chunks, rows = go
         gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb)
         meta = self.meta
-        gp.chunks = [Chunk(sid, slot, start, m.req.prompt_ids[start:start + ln], final, *m.samp)
+        gp.chunks = [Chunk(sid, slot, start, m.req.prompt_ids[start:start + ln], final, *m.samp, *m.cut)
                      for sid, slot, start, ln, final in chunks for m in (meta[sid],)]
         if changed:
-            gp.rows = [Row(sid, slot, pos, *meta[sid].samp, sstep, src)
+            gp.rows = [Row(sid, slot, pos, *meta[sid].samp, sstep, src, *meta[sid].cut)
                        for sid, slot, pos, sstep, src in rows]
         return gp
 

@@ -3,7 +3,9 @@
 `generate_text` keeps the notebook helper's signature and return contract
 (`/root/reference/notebook.ipynb:111-120`): the parsed JSON dict on HTTP 200,
 otherwise the string "Error: {code} - {text}"; network failures return
-"Request failed: {exc}".
+"Request failed: {exc}".  The optional sampling fields of /generate
+(temperature, top_k, top_p, min_p, greedy, seed, stop_at_eos) are sent when
+given.
 """
 from __future__ import annotations
 
@@ -14,10 +16,12 @@ COORDINATOR_URL = os.environ.get("COORDINATOR_URL", "http://127.0.0.1:5000/gener
 
 
 def generate_text(prompt: str, max_new_tokens: int = 20, url: str = None,
-                  timeout: float = 300.0, **sampling) -> Union[dict, str]:
+                  timeout: float = 300.0, top_p: float = None, min_p: float = None,
+                  **sampling) -> Union[dict, str]:
     import requests
 
     payload = {"prompt": prompt, "max_new_tokens": max_new_tokens}
+    sampling.update(top_p=top_p, min_p=min_p)
     payload.update({k: v for k, v in sampling.items() if v is not None})
     try:
         r = requests.post(url or COORDINATOR_URL, json=payload, timeout=timeout)

@@ -14,8 +14,8 @@ Roles (env SHARD_ROLE, `server.py:21`):
   a            stage 0 = embeddings + blocks[0:SPLIT_AT]          -> /forward
   b            blocks[SPLIT_AT:] + ln_f + lm_head                 -> /forward_b
   all          one process answers every endpoint (debug)
-Additions: optional sampling fields on /generate (temperature, top_k, greedy,
-seed, stop_at_eos; defaults = reference sampler), 422 on empty/over-long
+Additions: optional sampling fields on /generate (temperature, top_k, top_p,
+min_p, greedy, seed, stop_at_eos; defaults = reference sampler), 422 on empty/over-long
 prompts (instead of the reference's 500, quirk Q9), GET /health, GET /metrics
 (Prometheus text).  Concurrent /generate calls are batched at decode-step
 granularity by the engine's continuous-batching scheduler
@@ -57,6 +57,8 @@ class GenerateReq(BaseModel):
     greedy: bool = False
     seed: Optional[int] = None
     stop_at_eos: bool = False
+    top_p: float = 1.0   # nucleus cut inside the top-k candidates (1 = off)
+    min_p: float = 0.0   # keep tokens >= min_p x the most likely one (0 = off)
 
 
 class ShardRunner:
@@ -160,7 +162,7 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         ids = tok.encode(req.prompt)
         sp = SamplingParams(temperature=req.temperature, top_k=req.top_k, greedy=req.greedy,
                             seed=req.seed, max_new_tokens=req.max_new_tokens,
-                            stop_at_eos=req.stop_at_eos)
+                            stop_at_eos=req.stop_at_eos, top_p=req.top_p, min_p=req.min_p)
         if req.max_new_tokens == 0:
             return {"generated": tok.decode(ids, skip_special_tokens=True)}
         if not ids:
@@ -259,7 +261,8 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams) -> List
         logits = torch.tensor(r2.json()["logits"], dtype=torch.float32)[0, -1:]
         u = counter_uniform(torch.tensor([seed]), torch.tensor([step]))
         nxt = int(ref.sample(logits, torch.tensor([sp.temperature]), torch.tensor([sp.top_k]),
-                             torch.tensor([1 if sp.greedy else 0]), u, vocab)[0])
+                             torch.tensor([1 if sp.greedy else 0]), u, vocab,
+                             torch.tensor([sp.top_p]), torch.tensor([sp.min_p]))[0])
         seq.append(nxt)
         out.append(nxt)
     return out
