@@ -74,6 +74,11 @@ hipError_t lsd_sample(const float* logits, long ld, int B, int V, const float* t
                       long long* step, int* out, int advance, const int* active, int* pos,
                       const float* segmax, long ldseg, const float* top_p, const float* min_p,
                       hipStream_t st);
+hipError_t lsd_penalize(float* logits, long ld, int B, int V, const int* hist, int L, int nslots, const int* slots,
+                        const long long* counts, const float* presence, const float* frequency, float* segmax,
+                        long ldseg, hipStream_t st);
+hipError_t lsd_record_tokens(int* hist, int L, int nslots, const int* slots, const long long* step, int back,
+                             const int* tokens, const int* active, int B, hipStream_t st);
 }
 
 namespace {
@@ -707,9 +712,71 @@ torch::Tensor qkv_post(torch::Tensor y, c10::optional<torch::Tensor> bias, torch
 // elementwise.hip lsd_apply_rows (CPU tensor), on the current stream.
 void apply_rows(torch::Tensor args, int64_t b) {
   TORCH_CHECK(args.device().is_cpu() && args.scalar_type() == torch::kInt64 && args.is_contiguous() &&
-                  (args.numel() == 12 || args.numel() == 14),
-              "apply_rows: args must be a contiguous CPU int64[12] (or [14], with top_p / min_p) record");
+                  (args.numel() == 12 || args.numel() == 14 || args.numel() == 16),
+              "apply_rows: args must be a contiguous CPU int64[12] (or [14], with top_p / min_p, or [16], "
+              "with the penalties too) record");
   check_hip(lsd_apply_rows(args.data_ptr<int64_t>(), (int)args.numel(), (int)b, cur_stream()), "apply_rows");
+}
+
+// Presence / frequency penalties (penalty.hip): rewrites the fp32 logits (and
+// linear_f32's segment maxima, when given) of the rows with a non-zero penalty
+// in place, from their generated-token history hist[slots[row], 0 .. counts[row]).
+void penalize(torch::Tensor logits, int64_t V, torch::Tensor hist, torch::Tensor slots, torch::Tensor counts,
+              torch::Tensor presence, torch::Tensor frequency, c10::optional<torch::Tensor> segmax) {
+  need(logits, torch::kFloat32, "logits");
+  need(hist, torch::kInt32, "hist");
+  need(slots, torch::kInt32, "slots");
+  need(counts, torch::kInt64, "counts");
+  need(presence, torch::kFloat32, "presence");
+  need(frequency, torch::kFloat32, "frequency");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= 1 && V <= logits.size(1), "logits [B, >=V]");
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(hist.dim() == 2 && hist.is_contiguous(), "hist must be contiguous int32 [slots, max_seq]");
+  TORCH_CHECK(hist.size(1) >= 1 && hist.size(1) <= 8192,
+              "penalize: histories of more than 8192 tokens do not fit the kernel's 128 KB LDS table");
+  for (const torch::Tensor* t : {&slots, &counts, &presence, &frequency})
+    TORCH_CHECK(t->numel() == B && t->is_contiguous(), "penalize: row vectors must be contiguous [B]");
+  float* sm = nullptr;
+  long ldseg = 0;
+  if (segmax.has_value()) {
+    need(*segmax, torch::kFloat32, "segmax");
+    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && logits.size(1) % 8 == 0 &&
+                    logits.stride(0) % 8 == 0 && segmax->size(1) == logits.size(1) / 8,
+                "segmax must be fp32 [B, logits row length / 8]");
+    sm = segmax->data_ptr<float>();
+    ldseg = segmax->stride(0);
+  }
+  check_hip(lsd_penalize(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V, hist.data_ptr<int>(),
+                         (int)hist.size(1), (int)hist.size(0), slots.data_ptr<int>(),
+                         reinterpret_cast<const long long*>(counts.data_ptr<int64_t>()), presence.data_ptr<float>(),
+                         frequency.data_ptr<float>(), sm, ldseg, cur_stream()), "penalize");
+}
+
+// hist[slots[i], step[i] - back] = tokens[i] for active rows (all rows without
+// `active`); step absent = entry 0 (the prefill draw).  back = 1 after
+// sample_into, which has already advanced the counters.
+void record_tokens(torch::Tensor hist, torch::Tensor slots, c10::optional<torch::Tensor> step, torch::Tensor tokens,
+                   c10::optional<torch::Tensor> active, int64_t back) {
+  need(hist, torch::kInt32, "hist");
+  need(slots, torch::kInt32, "slots");
+  need(tokens, torch::kInt32, "tokens");
+  TORCH_CHECK(hist.dim() == 2 && hist.is_contiguous(), "hist must be contiguous int32 [slots, max_seq]");
+  const int64_t B = tokens.numel();
+  TORCH_CHECK(slots.numel() == B && slots.is_contiguous() && tokens.is_contiguous(), "record_tokens: [B] vectors");
+  const long long* sp = nullptr;
+  if (step.has_value()) {
+    need(*step, torch::kInt64, "step");
+    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
+    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
+  }
+  const int* act = nullptr;
+  if (active.has_value()) {
+    need(*active, torch::kInt32, "active");
+    TORCH_CHECK(active->numel() == B && active->is_contiguous(), "active must be contiguous int32 [B]");
+    act = active->data_ptr<int>();
+  }
+  check_hip(lsd_record_tokens(hist.data_ptr<int>(), (int)hist.size(1), (int)hist.size(0), slots.data_ptr<int>(), sp,
+                              (int)back, tokens.data_ptr<int>(), act, (int)B, cur_stream()), "record_tokens");
 }
 
 torch::Tensor silu_mul(torch::Tensor y) {
@@ -791,6 +858,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("silu_mul", &silu_mul);
   m.def("apply_rows", &apply_rows, py::arg("args"), py::arg("b"));
+  m.def("penalize", &penalize, py::arg("logits"), py::arg("V"), py::arg("hist"), py::arg("slots"),
+        py::arg("counts"), py::arg("presence"), py::arg("frequency"), py::arg("segmax") = py::none());
+  m.def("record_tokens", &record_tokens, py::arg("hist"), py::arg("slots"), py::arg("step"), py::arg("tokens"),
+        py::arg("active") = py::none(), py::arg("back") = 0);
   m.def("qkv_post", &qkv_post);
   // GEMV weight stream with non-temporal loads (A/B knob, LSD_GEMV_NT)
   m.def("gemv_set_nt", [](int64_t v) { lsd_gemv_set_nt((int)v); });

@@ -26,6 +26,8 @@ def in_process():
     print(llm.generate_text("Hi, ", max_new_tokens=8, greedy=True))         # argmax
     print(llm.generate_text("Hi, ", max_new_tokens=8, seed=1234))           # reproducible
     print(llm.generate_text("Hi, ", max_new_tokens=8, top_k=1024, top_p=0.9, min_p=0.05))  # nucleus + min-p
+    print(llm.generate_text("Hi, ", max_new_tokens=8, greedy=True, presence_penalty=0.5,
+                            frequency_penalty=0.5))  # discourage repeats of generated tokens
 
 
 def over_http(url="http://127.0.0.1:5000/generate"):

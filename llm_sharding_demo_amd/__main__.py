@@ -62,6 +62,10 @@ def main(argv=None) -> int:
                    help="nucleus cut inside the top-k candidates (pure nucleus: --top-k 1024)")
     g.add_argument("--min-p", type=float, default=0.0,
                    help="keep tokens at least this fraction as likely as the most likely one")
+    g.add_argument("--presence-penalty", type=float, default=0.0,
+                   help="subtracted once from the logit of every token generated so far ([-2, 2])")
+    g.add_argument("--frequency-penalty", type=float, default=0.0,
+                   help="subtracted per earlier occurrence of a generated token ([-2, 2])")
     g.add_argument("--seed", type=int)
     args = p.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(levelname)s %(message)s")
@@ -77,7 +81,8 @@ def main(argv=None) -> int:
             return 0
         out = llm.generate_text(args.prompt, args.max_new_tokens, greedy=args.greedy,
                                 temperature=args.temperature, top_k=args.top_k, seed=args.seed,
-                                top_p=args.top_p, min_p=args.min_p)
+                                top_p=args.top_p, min_p=args.min_p, presence_penalty=args.presence_penalty,
+                                frequency_penalty=args.frequency_penalty)
         print(out)
         llm.engine.shutdown()
         return 0

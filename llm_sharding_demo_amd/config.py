@@ -13,6 +13,7 @@ Sampling defaults match the reference's hard-coded sampler
 from __future__ import annotations
 
 import dataclasses
+import math
 import os
 from dataclasses import dataclass, field
 from typing import Optional, Sequence
@@ -181,7 +182,15 @@ class SamplingParams:
     shortest prefix holding top_p of the top-k-renormalised mass (at least one
     token stays).  They work inside the top-k candidates and top_k is capped at
     1024, so pure nucleus sampling is top_k=1024 with top_p.  The defaults
-    (1.0 / 0.0) disable both; greedy requests ignore them."""
+    (1.0 / 0.0) disable both; greedy requests ignore them.
+
+    presence_penalty / frequency_penalty act on the tokens the request has
+    generated so far (the prompt does not count; OpenAI / vLLM rule): before
+    each draw every token t generated c(t) > 0 times gets
+    logit[t] -= presence_penalty + frequency_penalty * c(t), on the raw logits,
+    ahead of temperature, top-k, top-p, min-p and the greedy argmax -- greedy
+    requests are penalised too.  Both default to 0.0 (off) and must be finite
+    and in [-2, 2]; negative values raise the logits of repeated tokens."""
 
     temperature: float = 0.6
     top_k: int = 40
@@ -191,10 +200,16 @@ class SamplingParams:
     stop_at_eos: bool = False  # reference never stops early (quirk Q10)
     top_p: float = 1.0
     min_p: float = 0.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
 
     def validate(self) -> None:
         if self.max_new_tokens < 0:
             raise ValueError("max_new_tokens must be >= 0")
+        for name in ("presence_penalty", "frequency_penalty"):  # greedy requests too
+            v = getattr(self, name)
+            if not (isinstance(v, (int, float)) and math.isfinite(v) and -2.0 <= v <= 2.0):
+                raise ValueError(f"{name} must be finite and in [-2, 2]")
         if not self.greedy:
             if self.temperature <= 0:
                 raise ValueError("temperature must be > 0 (use greedy=True for argmax)")

@@ -118,6 +118,14 @@ class ReferenceBackend(Backend):
         if meta is not None:
             meta.advance()
 
+    def penalize(self, logits, hist, slots, counts, presence, frequency, vocab: int) -> None:
+        """Presence / frequency penalties of the rows' generated-token
+        histories, in place on the fp32 logits, ahead of the sampler."""
+        ref.penalize(logits, hist, slots, counts, presence, frequency, vocab)
+
+    def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
+        ref.record_tokens(hist, slots, step, tokens, active, back)
+
     def gather_rows(self, x, idx):
         return x.index_select(0, idx.long())
 

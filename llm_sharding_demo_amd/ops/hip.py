@@ -374,5 +374,14 @@ class HipBackend(Backend):
                            meta.token_pos if meta is not None else None,
                            getattr(logits, "_lsd_segmax", None), samp.top_p, samp.min_p)
 
+    def penalize(self, logits, hist, slots, counts, presence, frequency, vocab: int) -> None:
+        # penalty.hip: the rows' logits, and the lm_head's segment maxima the
+        # sampler will trust, rewritten in place ahead of the draw
+        self.C.penalize(logits, vocab, hist, slots, counts, presence, frequency,
+                        getattr(logits, "_lsd_segmax", None))
+
+    def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
+        self.C.record_tokens(hist, slots, step, tokens, active, back)
+
     def gather_rows(self, x, idx):
         return x.index_select(0, idx.long())

@@ -117,6 +117,58 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     return out
 
 
+def penalize(logits: torch.Tensor, hist: torch.Tensor, slots: torch.Tensor, counts: torch.Tensor,
+             presence: torch.Tensor, frequency: torch.Tensor, vocab: int,
+             segmax: Optional[torch.Tensor] = None):
+    """Presence / frequency penalties over the tokens a row has generated
+    (OpenAI / vLLM rule; the prompt does not count), ahead of `sample`.
+
+    hist [slots, L] int: hist[s, j] = the j-th generated token of the sequence
+    on KV slot s; row r reads hist[slots[r], 0 .. counts[r]).  With c(t) the
+    occurrences of token t in there, every t with c(t) > 0 gets
+        logit[t] <- logit[t] - (presence[r] + frequency[r] * float(c(t)))
+    in fp32, three roundings (product, sum, difference).  Rows whose two
+    penalties are both 0, or whose history is empty, are untouched; history
+    entries outside [0, vocab) are ignored.
+
+    fp32 `logits` [B, >= vocab] are rewritten in place and returned.  With
+    `segmax` [B, width / 8] (linear_f32's 8-logit segment maxima, padding
+    columns included) the maxima of the touched segments are recomputed in
+    place too, and (logits, segmax) is returned.
+    """
+    assert logits.dtype == torch.float32, "penalize rewrites fp32 logits in place"
+    B, L = logits.shape[0], hist.shape[1]
+    for r in range(B):
+        p, f = presence[r].float(), frequency[r].float()
+        n = min(int(counts[r]), L)
+        if (float(p) == 0.0 and float(f) == 0.0) or n <= 0:
+            continue
+        h = hist[int(slots[r]), :n].long()
+        toks, cnt = torch.unique(h[(h >= 0) & (h < vocab)], return_counts=True)
+        if toks.numel() == 0:
+            continue
+        pen = p + f * cnt.to(torch.float32)  # two roundings: the product, then the sum
+        logits[r, toks] = logits[r, toks] - pen
+        if segmax is not None:
+            segs = torch.unique(toks // 8)
+            idx = segs[:, None] * 8 + torch.arange(8)
+            segmax[r, segs] = logits[r][idx].max(dim=1).values
+    return logits if segmax is None else (logits, segmax)
+
+
+def record_tokens(hist: torch.Tensor, slots: torch.Tensor, step: Optional[torch.Tensor], tokens: torch.Tensor,
+                  active: Optional[torch.Tensor] = None, back: int = 0) -> None:
+    """hist[slots[i], step[i] - back] = tokens[i] for active rows (all rows
+    when `active` is None); step None = entry 0, the prefill draw.  back = 1
+    when the sampler counters were already advanced past the draw."""
+    for i in range(tokens.shape[0]):
+        if active is not None and int(active[i]) == 0:
+            continue
+        j = int(step[i]) - back if step is not None else 0
+        if 0 <= j < hist.shape[1]:
+            hist[int(slots[i]), j] = int(tokens[i])
+
+
 def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
            greedy: torch.Tensor, uniforms: torch.Tensor, vocab: int,
            top_p: Optional[torch.Tensor] = None, min_p: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -198,7 +198,13 @@ class GroupState(racecheck.Shared):
         # stage): the sampler gets the two vectors only then, and the decode
         # graphs are keyed on it -- all-default traffic runs the sampler without them
         self.cut = False
+        # any row of the current composition with a presence / frequency
+        # penalty (last stage): only then do penalize and record_tokens run
+        # around the sampler, and the decode graphs are keyed on it too
+        self.pen = False
         if w.last:
+            self.presence = torch.zeros(cap, dtype=torch.float32, device=dev)   # penalties (0 = off)
+            self.frequency = torch.zeros(cap, dtype=torch.float32, device=dev)
             self.temp = torch.ones(cap, dtype=torch.float32, device=dev)
             self.topk = torch.ones(cap, **i32)
             self.topp = torch.ones(cap, dtype=torch.float32, device=dev)   # nucleus cut (1 = off)
@@ -400,6 +406,12 @@ class StageWorker(racecheck.Shared):
         self.native_changes = 0  # composition-change items issued by exec_items
         self.mixed_items = 0     # decode + prefill items run as one forward (_mixed)
         self.io_items = 0  # decode items whose (graph) body carried its own transfers
+        # last stage: generated-token history per KV slot, int32 [slots,
+        # max_seq], indexed by the draw's sampler counter (_hist: allocated
+        # when the first penalised request arrives), and the items whose
+        # sampler ran with the penalty pass around it
+        self.pen_hist: Optional[torch.Tensor] = None
+        self.penalty_launches = 0
 
     # ------------------------------------------------------------------
     def configure(self, groups: int, cap: int) -> None:
@@ -614,7 +626,8 @@ class StageWorker(racecheck.Shared):
                 return False
             gs = self.groups[gp.g]
             cut = gs.cut if gp.rows is None else self._rows_cut(gp.rows)  # after this item's change
-            key = (gp.b, gp.ctxb, io, cut)
+            pen = gs.pen if gp.rows is None else self._rows_pen(gp.rows)
+            key = (gp.b, gp.ctxb, io, cut, pen)
             ent = gs.graphs.get(key)
             if ent is None:
                 return False
@@ -674,10 +687,13 @@ class StageWorker(racecheck.Shared):
                     # composition change: packed row state copied and applied
                     # after the readout, ahead of the graph (csrc/stage_exec.cpp)
                     slot, args = self._rows_pack(gs, gp.rows, gp.b)
-                    d[14], d[15], d[16], d[17] = args.data_ptr(), slot[0].data_ptr(), 4 * self._rows_words(gs.cap), gp.b
+                    d[14], d[15], d[16], d[17] = (args.data_ptr(), slot[0].data_ptr(),
+                                                  4 * self._rows_words(gs.cap, gs.pen), gp.b)
                     d[18] = args.numel()
                     packed.append((slot, lane))
                     self.native_changes += 1
+                if gs.pen:
+                    self.penalty_launches += 1
                 rows.append(d)
             try:
                 with (self.t.issuing() if self.t is not None else contextlib.nullcontext()):
@@ -906,7 +922,9 @@ class StageWorker(racecheck.Shared):
         if seg is not None:
             ld._lsd_segmax = seg[:b]
         # decode rows: draw, advance their sampler counters and positions (as the graph does)
-        be.sample_into(ld, gs.samp(b), V, gs.tokret[:b], dec)
+        self._sample_rows(gs, ld, b, dec)
+        if gs.pen:
+            self.penalty_launches += 1
         if J:
             lf = logits[b:]
             if seg is not None:
@@ -915,7 +933,9 @@ class StageWorker(racecheck.Shared):
             samp = SamplingState([c.temperature for c in fc], [c.top_k for c in fc],
                                  [c.greedy for c in fc], [c.seed for c in fc], dev,
                                  [c.top_p for c in fc], [c.min_p for c in fc])
-            gs.tokret[b: b + J].copy_(be.sample(lf, samp, V))
+            ids = be.sample(lf, samp, V)
+            self._record_finals(fc, ids)
+            gs.tokret[b: b + J].copy_(ids)
         self.mixed_items += 1
 
     def _apply_rows(self, gp: GroupPlan, gs: GroupState) -> None:
@@ -926,6 +946,7 @@ class StageWorker(racecheck.Shared):
         dev, rows = self.device, gp.rows
         n, b = gp.n, max(gp.b, gp.n)
         gs.cut = self._rows_cut(rows)
+        gs.pen = self._rows_pen(rows)
         pad = b - n
         sl = [r.slot for r in rows] + [self.scratch_slot] * pad
         pos = [r.pos for r in rows] + [0] * pad
@@ -935,8 +956,8 @@ class StageWorker(racecheck.Shared):
         if dev.type == "cuda":
             if hasattr(self.stage.backend, "C"):
                 slot, args = self._rows_pack(gs, rows, b)
-                words = self._rows_words(gs.cap)
-                gs.rows_dev.copy_(slot[0][:words], non_blocking=True)
+                words = self._rows_words(gs.cap, gs.pen)
+                gs.rows_dev[:words].copy_(slot[0][:words], non_blocking=True)
                 self.stage.backend.C.apply_rows(args, b)
                 slot[1].record()
                 slot[2] = True
@@ -955,6 +976,11 @@ class StageWorker(racecheck.Shared):
                               non_blocking=True)
             gs.minp[:b].copy_(_h2d([r.min_p for r in rows] + [0.0] * pad, torch.float32, dev),
                               non_blocking=True)
+            if gs.pen:
+                gs.presence[:b].copy_(_h2d([r.presence for r in rows] + [0.0] * pad, torch.float32, dev),
+                                      non_blocking=True)
+                gs.frequency[:b].copy_(_h2d([r.frequency for r in rows] + [0.0] * pad, torch.float32, dev),
+                                       non_blocking=True)
             gs.greedy[:b].copy_(_h2d([1 if r.greedy else 0 for r in rows] + [1] * pad, torch.int32,
                                      dev), non_blocking=True)
             gs.seeds[:b].copy_(_h2d([r.seed for r in rows] + [0] * pad, torch.int64, dev),
@@ -970,12 +996,63 @@ class StageWorker(racecheck.Shared):
         """Whether the sampler of this composition needs the top-p / min-p vectors."""
         return self.last and any(r.top_p < 1.0 or r.min_p > 0.0 for r in rows)
 
+    def _rows_pen(self, rows) -> bool:
+        """Whether this composition has a row with a presence / frequency
+        penalty; the history is allocated here, on the host side of the change
+        (never inside a capture)."""
+        pen = self.last and any(r.presence != 0.0 or r.frequency != 0.0 for r in rows)
+        if pen:
+            self._hist()
+        return pen
+
+    def _hist(self) -> torch.Tensor:
+        """Generated-token history of the last stage, [KV slots (scratch and
+        compat included), max_seq] int32.  Entries at or past a row's sampler
+        counter are never read, so it needs no initial value and a reused slot
+        no clearing."""
+        if self.pen_hist is None:
+            L = self.stage.max_seq
+            if L > 8192 and self.device.type == "cuda":
+                raise ValueError(f"presence / frequency penalties: max_seq_len {L} exceeds the 8192-token "
+                                 "history the penalty kernel's LDS table holds")
+            slots = max(self.scratch_slot, self.compat_slot) + 1
+            # no fill: one enqueued on this lane could land after another lane's first record
+            self.pen_hist = torch.empty(slots, L, dtype=torch.int32, device=self.device)
+        return self.pen_hist
+
+    def _sample_rows(self, gs: GroupState, logits: torch.Tensor, b: int, meta) -> None:
+        """Decode rows of a group: draw into the token-return vector, advance
+        the sampler counters and positions.  A composition with a penalised
+        row runs lm_head, penalize, sample_into, record_tokens; any other the
+        sampler alone, as before."""
+        be, V = self.stage.backend, self.stage.cfg.vocab_size
+        if not gs.pen:
+            be.sample_into(logits, gs.samp(b), V, gs.tokret[:b], meta)
+            return
+        hist = self.pen_hist
+        be.penalize(logits, hist, gs.slots[:b], gs.sstep[:b], gs.presence[:b], gs.frequency[:b], V)
+        be.sample_into(logits, gs.samp(b), V, gs.tokret[:b], meta)
+        # the sampler has advanced the counters: the draw used counter - 1
+        be.record_tokens(hist, gs.slots[:b], gs.sstep[:b], gs.tokret[:b], gs.active[:b], 1)
+
+    def _record_finals(self, fc, ids: torch.Tensor) -> None:
+        """First generated token (draw 0) of the final chunks `fc` into the
+        history, when one of them carries a penalty (its history is empty, so
+        the prefill draw itself needs no penalty pass)."""
+        if not any(c.presence != 0.0 or c.frequency != 0.0 for c in fc):
+            return
+        slots = _h2d([c.slot for c in fc], torch.int32, self.device)
+        slots = slots.to(self.device, non_blocking=True)
+        self.stage.backend.record_tokens(self._hist(), slots, None, ids, None, 0)
+        self.penalty_launches += 1
+
     _ROWS_PIN = 4  # packed row-state buffers per group: reused 4 composition changes later
 
-    def _rows_words(self, cap: int) -> int:
+    def _rows_words(self, cap: int, pen: bool = False) -> int:
         """int32 words of a group's packed row state: the last stage's also
-        carries the top-p / min-p columns."""
-        return (12 if self.last else 10) * cap + 1
+        carries the top-p / min-p columns and, for a composition with a
+        penalised row, the presence / frequency columns."""
+        return ((14 if pen else 12) if self.last else 10) * cap + 1
 
     def _rows_pack(self, gs: GroupState, rows, b: int):
         """Composition change on a GPU, host side: the new rows' state packed
@@ -983,12 +1060,14 @@ class StageWorker(racecheck.Shared):
         apply_rows_kernel (fixed offsets by the group capacity, so the device
         copy and the kernel depend on the bucket only), and the kernel's
         argument record.  -> (pinned ring slot, CPU int64 record: 14 words on
-        the last stage, which owns the top-p / min-p vectors, else 12); the
+        the last stage, which owns the top-p / min-p vectors, 16 while the
+        composition has a penalised row, else 12); the
         caller enqueues the copy + kernel (eagerly, or in exec_items) and then
         records the slot's event."""
         cap = gs.cap
         gs.cut = self._rows_cut(rows)
-        words = self._rows_words(cap)
+        gs.pen = self._rows_pen(rows)
+        words = self._rows_words(cap, True)  # buffers sized for the longest record
         if len(gs.rows_pin) < self._ROWS_PIN:
             gs.rows_pin.append([torch.empty(words, dtype=torch.int32, pin_memory=True), torch.cuda.Event(), False])
         slot = gs.rows_pin[gs.rows_pin_next % len(gs.rows_pin)]
@@ -1008,6 +1087,11 @@ class StageWorker(racecheck.Shared):
                 a[f0 + 4 * cap: f0 + 4 * cap + n] = [1 if r.greedy else 0 for r in rows]
                 a[f0 + 6 * cap: f0 + 6 * cap + n] = np.asarray([r.top_p for r in rows], np.float32).view(np.int32)
                 a[f0 + 7 * cap: f0 + 7 * cap + n] = np.asarray([r.min_p for r in rows], np.float32).view(np.int32)
+                if gs.pen:
+                    a[f0 + 8 * cap: f0 + 8 * cap + n] = np.asarray([r.presence for r in rows],
+                                                                   np.float32).view(np.int32)
+                    a[f0 + 9 * cap: f0 + 9 * cap + n] = np.asarray([r.frequency for r in rows],
+                                                                   np.float32).view(np.int32)
                 a64 = a[: 4 * cap].view(np.int64)
                 a64[:n] = [r.seed for r in rows]
                 a64[cap: cap + n] = [r.step for r in rows]
@@ -1015,7 +1099,7 @@ class StageWorker(racecheck.Shared):
                 a[f0 + 5 * cap: f0 + 5 * cap + n] = [r.src for r in rows]
         if gs.rows_dev is None:
             gs.rows_dev = torch.empty(words, dtype=torch.int32, device=self.device)
-            gs.rows_args = torch.zeros(14 if self.last else 12, dtype=torch.int64)
+            gs.rows_args = torch.zeros(16 if self.last else 12, dtype=torch.int64)
         r = gs.rows_args.numpy()
         ptr = lambda t: t.data_ptr()  # noqa: E731
         r[0], r[1], r[2] = cap, self.scratch_slot, ptr(gs.rows_dev)
@@ -1023,8 +1107,10 @@ class StageWorker(racecheck.Shared):
         if self.last:
             r[6], r[7], r[8], r[9], r[10] = ptr(gs.temp), ptr(gs.topk), ptr(gs.greedy), ptr(gs.seeds), ptr(gs.sstep)
             r[12], r[13] = ptr(gs.topp), ptr(gs.minp)
+            r[14], r[15] = ptr(gs.presence), ptr(gs.frequency)
         r[11] = ptr(gs.tin) if self.first else 0
-        return slot, gs.rows_args
+        # the record's leading 14 words are what default traffic passes
+        return slot, (gs.rows_args[: 16 if gs.pen else 14] if self.last else gs.rows_args)
 
     def _apply_rows_staged(self, gs: GroupState, rows, b: int, pad: int, sl, pos, act) -> None:
         """_apply_rows on a GPU: every per-row field packed into ONE int32
@@ -1041,6 +1127,9 @@ class StageWorker(racecheck.Shared):
                       np.asarray([1 if r.greedy else 0 for r in rows] + [1] * pad, i32),
                       np.asarray([r.top_p for r in rows] + [1.0] * pad, np.float32).view(i32),
                       np.asarray([r.min_p for r in rows] + [0.0] * pad, np.float32).view(i32)]
+            if gs.pen:  # two more columns: the int64 fields stay 8-byte aligned
+                parts += [np.asarray([r.presence for r in rows] + [0.0] * pad, np.float32).view(i32),
+                          np.asarray([r.frequency for r in rows] + [0.0] * pad, np.float32).view(i32)]
             # the int64 fields start at int32 offset 8 b: 8-byte aligned
             parts += [np.asarray([r.seed for r in rows] + [0] * pad, np.int64).view(i32),
                       np.asarray([r.step for r in rows] + [0] * pad, np.int64).view(i32)]
@@ -1062,6 +1151,10 @@ class StageWorker(racecheck.Shared):
             gs.topp[:b].copy_(buf[o + 3 * b: o + 4 * b].view(torch.float32))
             gs.minp[:b].copy_(buf[o + 4 * b: o + 5 * b].view(torch.float32))
             o += 5 * b
+            if gs.pen:
+                gs.presence[:b].copy_(buf[o: o + b].view(torch.float32))
+                gs.frequency[:b].copy_(buf[o + b: o + 2 * b].view(torch.float32))
+                o += 2 * b
             gs.seeds[:b].copy_(buf[o: o + 2 * b].view(torch.int64))
             gs.sstep[:b].copy_(buf[o + 2 * b: o + 4 * b].view(torch.int64))
             o += 4 * b
@@ -1098,7 +1191,9 @@ class StageWorker(racecheck.Shared):
         samp = SamplingState([c.temperature for c in fc], [c.top_k for c in fc],
                              [c.greedy for c in fc], [c.seed for c in fc], dev,
                              [c.top_p for c in fc], [c.min_p for c in fc])
-        return be.sample(logits, samp, st.cfg.vocab_size)
+        ids = be.sample(logits, samp, st.cfg.vocab_size)
+        self._record_finals(fc, ids)
+        return ids
 
     # Prefill chunks as hipGraphs (the non-steady items):
     # a chunk item whose shape (per-sequence query counts, split variant, input
@@ -1214,8 +1309,10 @@ class StageWorker(racecheck.Shared):
         slot[2] = True
 
     def _decode(self, gp: GroupPlan, gs: GroupState, inp: torch.Tensor, io: bool = False) -> torch.Tensor:
-        key = (gp.b, gp.ctxb, io, gs.cut)
+        key = (gp.b, gp.ctxb, io, gs.cut, gs.pen)
         lane = self.lane_of(gp.g)
+        if gs.pen:
+            self.penalty_launches += 1
 
         def body():
             if io and not self.first:  # the edge receive, inside the graph
@@ -1227,9 +1324,8 @@ class StageWorker(racecheck.Shared):
                 if io:
                     self._send(out, self.r + 1, "fwd", lane, capture=True)
                 return out
-            samp = gs.samp(gp.b)
             # the sampler kernel also advances this stage's positions (no add kernel)
-            self.stage.backend.sample_into(out, samp, self.stage.cfg.vocab_size, gs.tokret[: gp.b], meta)
+            self._sample_rows(gs, out, gp.b, meta)
             if io:
                 self._send(gs.tokret[: gp.b], 0, "ret", lane, capture=True)
             return gs.tokret[: gp.b]

@@ -45,6 +45,8 @@ class Chunk:
     seed: int = 0
     top_p: float = 1.0
     min_p: float = 0.0
+    presence: float = 0.0   # presence / frequency penalties over the generated tokens
+    frequency: float = 0.0
 
     @property
     def qlen(self) -> int:
@@ -68,6 +70,8 @@ class Row:
                         # newly activated rows: prev_b + final-chunk index)
     top_p: float = 1.0
     min_p: float = 0.0
+    presence: float = 0.0
+    frequency: float = 0.0
 
 
 @dataclass
@@ -148,18 +152,25 @@ def _steady_groups(plan: StepPlan):
 def _float_cols(xs):
     """float64 column(s) of Chunks / Rows: [n] temperatures while every entry
     has the default top_p / min_p (the common case stays as small as before),
-    else [n, 3] = (temperature, top_p, min_p)."""
+    else [n, 3] = (temperature, top_p, min_p), or [n, 5] with (presence,
+    frequency) appended when an entry has a penalty."""
     import numpy as np
 
+    if any(x.presence != 0.0 or x.frequency != 0.0 for x in xs):
+        return np.array([(x.temperature, x.top_p, x.min_p, x.presence, x.frequency) for x in xs],
+                        dtype=np.float64).reshape(-1, 5)
     if all(x.top_p == 1.0 and x.min_p == 0.0 for x in xs):
         return np.array([x.temperature for x in xs], dtype=np.float64)
     return np.array([(x.temperature, x.top_p, x.min_p) for x in xs], dtype=np.float64).reshape(-1, 3)
 
 
 def _float_rows(temp):
-    """(temperature, top_p, min_p) per entry of a _float_cols column."""
+    """(temperature, top_p, min_p, presence, frequency) per entry of a
+    _float_cols column."""
     if temp.ndim == 1:
-        return [(t, 1.0, 0.0) for t in temp.tolist()]
+        return [(t, 1.0, 0.0, 0.0, 0.0) for t in temp.tolist()]
+    if temp.shape[1] == 3:
+        return [(t, tp, mp, 0.0, 0.0) for t, tp, mp in temp.tolist()]
     return temp.tolist()
 
 
@@ -196,16 +207,16 @@ def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows) -> GroupPlan:
         ints, temp, seeds, tok = ch
         tok = tok.tolist() if tok is not None else None
         out, o = [], 0
-        for (seq, slot, start, ln, final, top_k, greedy), (t, tp, mp), sd in zip(ints.tolist(), _float_rows(temp),
+        for (seq, slot, start, ln, final, top_k, greedy), (t, tp, mp, pp, fp), sd in zip(ints.tolist(), _float_rows(temp),
                                                                                  seeds.tolist()):
             out.append(Chunk(seq, slot, start, tok[o: o + ln] if tok is not None else range(ln), bool(final),
-                             t, top_k, bool(greedy), sd, tp, mp))
+                             t, top_k, bool(greedy), sd, tp, mp, pp, fp))
             o += ln
         gp.chunks = out
     if rows is not None:
         ints, temp = rows
-        gp.rows = [Row(seq, slot, pos, t, top_k, bool(greedy), seed, step, src, tp, mp)
-                   for (seq, slot, pos, top_k, greedy, seed, step, src), (t, tp, mp) in zip(ints.tolist(),
+        gp.rows = [Row(seq, slot, pos, t, top_k, bool(greedy), seed, step, src, tp, mp, pp, fp)
+                   for (seq, slot, pos, top_k, greedy, seed, step, src), (t, tp, mp, pp, fp) in zip(ints.tolist(),
                                                                                             _float_rows(temp))]
     return gp
 

@@ -518,7 +518,8 @@ class _Meta:
     req: Request
     seed: int
     samp: tuple = ()    # (temperature, top_k, greedy, seed): the chunk / row sampling fields
-    cut: tuple = (1.0, 0.0)  # (top_p, min_p): the trailing chunk / row fields
+    # (top_p, min_p, presence, frequency): the trailing chunk / row fields
+    cut: tuple = (1.0, 0.0, 0.0, 0.0)
     done: bool = False  # finished by this scheduler (plain flag: the readout loop's hot path)
 
 
@@ -609,7 +610,8 @@ class Scheduler(racecheck.Shared):
         for i, req in zip(ids, reqs):
             p = req.params
             seed = p.seed if p.seed is not None else rng.getrandbits(62)
-            meta[i] = _Meta(req, seed, (p.temperature, p.top_k, p.greedy, seed), (p.top_p, p.min_p))
+            meta[i] = _Meta(req, seed, (p.temperature, p.top_k, p.greedy, seed),
+                            (p.top_p, p.min_p, float(p.presence_penalty), float(p.frequency_penalty)))
             lens.append(len(req.prompt_ids))
             wants.append(p.max_new_tokens)
             stops.append(bool(p.stop_at_eos))

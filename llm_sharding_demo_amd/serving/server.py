@@ -15,7 +15,8 @@ Roles (env SHARD_ROLE, `server.py:21`):
   b            blocks[SPLIT_AT:] + ln_f + lm_head                 -> /forward_b
   all          one process answers every endpoint (debug)
 Additions: optional sampling fields on /generate (temperature, top_k, top_p,
-min_p, greedy, seed, stop_at_eos; defaults = reference sampler), 422 on empty/over-long
+min_p, presence_penalty, frequency_penalty, greedy, seed, stop_at_eos; defaults =
+reference sampler), 422 on empty/over-long
 prompts (instead of the reference's 500, quirk Q9), GET /health, GET /metrics
 (Prometheus text).  Concurrent /generate calls are batched at decode-step
 granularity by the engine's continuous-batching scheduler
@@ -59,6 +60,8 @@ class GenerateReq(BaseModel):
     stop_at_eos: bool = False
     top_p: float = 1.0   # nucleus cut inside the top-k candidates (1 = off)
     min_p: float = 0.0   # keep tokens >= min_p x the most likely one (0 = off)
+    presence_penalty: float = 0.0   # off every generated token's logit, once (in [-2, 2])
+    frequency_penalty: float = 0.0  # off it again per occurrence so far (in [-2, 2])
 
 
 class ShardRunner:
@@ -162,7 +165,8 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         ids = tok.encode(req.prompt)
         sp = SamplingParams(temperature=req.temperature, top_k=req.top_k, greedy=req.greedy,
                             seed=req.seed, max_new_tokens=req.max_new_tokens,
-                            stop_at_eos=req.stop_at_eos, top_p=req.top_p, min_p=req.min_p)
+                            stop_at_eos=req.stop_at_eos, top_p=req.top_p, min_p=req.min_p,
+                            presence_penalty=req.presence_penalty, frequency_penalty=req.frequency_penalty)
         if req.max_new_tokens == 0:
             return {"generated": tok.decode(ids, skip_special_tokens=True)}
         if not ids:
@@ -240,7 +244,9 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
 def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams) -> List[int]:
     """Reference-style coordinator loop over remote shards (`server.py:169-206`):
     full-sequence recompute on every step, hidden states relayed through here.
-    Kept for deployments where the shards are separate hosts without xGMI."""
+    Kept for deployments where the shards are separate hosts without xGMI.
+    This relay keeps the reference's sampler: presence_penalty and
+    frequency_penalty are ignored here."""
     import requests
 
     from ..ops import reference as ref

@@ -1,0 +1,286 @@
+"""Per-request presence / frequency penalties on the CPU: the host reference
+(ops/reference.py penalize), validation, the plan wire, the CPU engine and
+the HTTP / client / LLM callers.
+
+Semantics (OpenAI / vLLM rule over generated tokens only): with c(t) the
+number of times the sequence has generated token t so far, every t with
+c(t) > 0 gets, before the draw,
+    logit[t] <- logit[t] - (presence + frequency * float(c(t)))
+in fp32 with one rounding each for the product, the sum and the difference,
+ahead of temperature / top-k / top-p / min-p and of the greedy argmax.
+"""
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+from llm_sharding_demo_amd.config import EngineConfig, SamplingParams
+from llm_sharding_demo_amd.ops import reference as ref
+from llm_sharding_demo_amd.runtime.engine import Engine
+from llm_sharding_demo_amd.runtime.plan import (MAGIC_PICKLE, Chunk, GroupPlan, PlanDecoder, PlanEncoder, Row,
+                                                StepPlan)
+
+V = 16
+
+
+def _greedy(logits, history, presence=0.0, frequency=0.0):
+    """Greedy token of one row after ref.penalize with `history` on KV slot 2."""
+    lg = torch.tensor([logits + [0.0] * (V - len(logits))], dtype=torch.float32)
+    hist = torch.full((4, 8), -7, dtype=torch.int32)  # other slots / later entries: never read
+    hist[2, : len(history)] = torch.tensor(history, dtype=torch.int32)
+    ref.penalize(lg, hist, torch.tensor([2]), torch.tensor([len(history)]), torch.tensor([presence]),
+                 torch.tensor([frequency]), V)
+    one = torch.tensor([1])
+    return int(ref.sample(lg, torch.tensor([1.0]), one, one, torch.tensor([0.5]), V)[0])
+
+
+def test_hand_made_rows():
+    assert _greedy([3.0, 2.5], [0], presence=1.0) == 1
+    assert _greedy([3.0, 2.5], [0], presence=0.4) == 0
+    assert _greedy([3.0, 2.5], [0, 0, 0], frequency=0.2) == 1  # 3.0 - 0.6 < 2.5
+    assert _greedy([3.0, 2.5], [0, 0], frequency=0.2) == 0     # 3.0 - 0.4 > 2.5
+    # a negative presence on a history token that is not the argmax makes it the argmax
+    assert _greedy([3.0, 2.5, 1.5], [2]) == 0
+    assert _greedy([3.0, 2.5, 1.5], [2], presence=-2.0) == 2
+    # empty history: the first generated token is never changed
+    assert _greedy([3.0, 2.5], [], presence=2.0, frequency=2.0) == 0
+    # the prompt does not count: only hist[slot, :count] is read
+    assert _greedy([3.0, 2.5], [1], presence=2.0) == 0
+
+
+def test_formula_is_exact_three_roundings():
+    g = torch.Generator().manual_seed(3)
+    B, W, L = 5, 40, 64
+    lg = (torch.randn(B, W, generator=g) * 7).float()
+    before = lg.clone()
+    hist = torch.randint(0, 33, (7, L), generator=g, dtype=torch.int32)
+    slots = torch.tensor([3, 0, 6, 1, 5], dtype=torch.int32)
+    counts = torch.tensor([64, 1, 0, 37, 20], dtype=torch.int64)
+    pres = torch.tensor([0.7, -1.3, 2.0, 0.0, 0.0], dtype=torch.float32)
+    freq = torch.tensor([0.1, 0.3, 2.0, -0.37, 0.0], dtype=torch.float32)
+    vocab = 33
+    out = ref.penalize(lg, hist, slots, counts, pres, freq, vocab)
+    assert out is lg
+    f32 = np.float32
+    for r in range(B):
+        h = hist[int(slots[r]), : int(counts[r])].tolist()
+        for t in range(W):
+            c = h.count(t) if t < vocab else 0
+            want = f32(before[r, t])
+            if c > 0 and (float(pres[r]) != 0.0 or float(freq[r]) != 0.0):
+                prod = f32(f32(freq[r]) * f32(c))
+                pen = f32(f32(pres[r]) + prod)
+                want = f32(want - pen)
+            assert f32(lg[r, t]).tobytes() == want.tobytes(), (r, t, c)
+    assert torch.equal(lg[2], before[2]) and torch.equal(lg[4], before[4])  # empty history; 0.0 / 0.0
+
+
+def test_segment_maxima_recomputed():
+    g = torch.Generator().manual_seed(4)
+    lg = torch.randn(3, 48, generator=g)
+    lg[0, 9] = 9.0   # the row's argmax, in history: its segment maximum falls
+    lg[1, 20] = -9.0  # made the segment maximum by a negative penalty
+    seg = lg.view(3, 6, 8).max(dim=2).values.clone()
+    seg0 = seg.clone()
+    hist = torch.tensor([[9, 10, 9, 44, 0], [20, 20, 20, 20, 20], [1, 2, 3, 4, 5]], dtype=torch.int32)
+    out, seg_out = ref.penalize(lg, hist, torch.tensor([0, 1, 2]), torch.tensor([5, 5, 5]),
+                                torch.tensor([1.0, -2.0, 0.0]), torch.tensor([0.5, -2.0, 0.0]), 45, seg)
+    assert out is lg and seg_out is seg
+    assert torch.equal(seg, lg.view(3, 6, 8).max(dim=2).values)
+    assert seg[0, 1] < seg0[0, 1] and seg[1, 2] == lg[1, 20] and torch.equal(seg[2], seg0[2])
+
+
+@pytest.mark.parametrize("field", ["presence_penalty", "frequency_penalty"])
+def test_validation(field):
+    for bad in (float("nan"), float("inf"), float("-inf"), 2.5, -2.5):
+        for greedy in (False, True):
+            with pytest.raises(ValueError):
+                SamplingParams(greedy=greedy, **{field: bad}).validate()
+    for ok in (0.0, 2.0, -2.0):
+        SamplingParams(**{field: ok}).validate()
+        SamplingParams(greedy=True, **{field: ok}).validate()
+    assert getattr(SamplingParams(), field) == 0.0
+
+
+def _plan(with_fields: bool, pres=0.0, freq=0.0):
+    ex = (1.0, 0.0, pres, freq) if with_fields else ()
+    return StepPlan(step=7, groups=[
+        GroupPlan(0, ret=2, n=2, b=2, ctxb=256,
+                  chunks=[Chunk(1, 3, 0, [5, 6, 7], True, 0.7, 40, False, 11, *ex),
+                          Chunk(2, 4, 0, [8], True, 0.6, 40, False, 12)],
+                  rows=[Row(3, 5, 9, 0.9, 20, False, 13, 4, 0, *ex),
+                        Row(4, 6, 2, 0.6, 40, True, 14, 1, 1)])])
+
+
+def test_plan_wire():
+    plan = _plan(True, 1.25, -0.123456789012345)
+    rec, payload = PlanEncoder().encode(plan)
+    assert rec[0] == MAGIC_PICKLE
+    out = PlanDecoder().decode(rec, lambda n: payload)
+    assert out == plan and pickle.loads(pickle.dumps(plan)) == plan
+    g0 = out.groups[0]
+    assert (g0.chunks[0].presence, g0.chunks[0].frequency) == (1.25, -0.123456789012345)
+    assert (g0.rows[0].presence, g0.rows[0].frequency) == (1.25, -0.123456789012345)
+    assert (g0.chunks[1].presence, g0.chunks[1].frequency) == (0.0, 0.0)  # built without them
+    assert (g0.rows[1].presence, g0.rows[1].frequency) == (0.0, 0.0)
+    # objects built without the fields equal ones built with 0.0, and the
+    # all-default plan is no longer on the wire than before the fields existed
+    assert _plan(False) == _plan(True)
+    _, p_without = PlanEncoder().encode(_plan(False))
+    _, p_with = PlanEncoder().encode(_plan(True))
+    assert len(p_with) == len(p_without) < len(payload)
+
+
+def _eng(P=1, max_batch=4, **kw):
+    return Engine(EngineConfig(model_id="gpt2-test", num_stages=P, max_batch=max_batch, device="cpu", **kw))
+
+
+PROMPT = [1, 2, 3]
+PEN = SamplingParams(greedy=True, max_new_tokens=24, presence_penalty=2.0, frequency_penalty=2.0)
+PLAIN = SamplingParams(greedy=True, max_new_tokens=24)
+
+
+@pytest.fixture(scope="module")
+def runs():
+    e = _eng()
+    return e, e.generate_ids([PROMPT], [PLAIN])[0], e.generate_ids([PROMPT], [PEN])[0]
+
+
+def test_engine_first_divergence_is_a_repeat(runs):
+    _, plain, pen = runs
+    assert len(plain) == len(pen) == 24
+    assert len(set(plain)) < len(plain)  # precondition: plain greedy repeats a token
+    assert pen != plain                  # the penalty is live
+    i = next(k for k in range(24) if plain[k] != pen[k])
+    # positive penalties only lower tokens already generated, and the outputs
+    # agree before i: the plain choice at i must have been a repeat
+    assert plain[i] in plain[:i]
+
+
+def test_engine_same_tokens_at_every_stage_count(runs):
+    _, _, pen = runs
+    for P in (2, 4):
+        assert _eng(P).generate_ids([PROMPT], [PEN])[0] == pen
+
+
+def test_engine_same_tokens_inside_a_changing_batch(runs):
+    e, plain, pen = runs
+    others = [SamplingParams(temperature=0.7, top_k=5, seed=3, max_new_tokens=4),
+              SamplingParams(greedy=True, max_new_tokens=9),
+              SamplingParams(temperature=1.2, top_k=100, seed=4, max_new_tokens=15, presence_penalty=-1.0)]
+    outs = e.generate_ids([[4], PROMPT, [9, 8, 7, 6], [5, 5]], [others[0], PEN, others[1], others[2]])
+    assert outs[1] == pen
+    # the neighbours draw what they draw without the penalised request
+    assert e.generate_ids([[4], [9, 8, 7, 6], [5, 5]], others) == [outs[0], outs[2], outs[3]]
+
+
+def test_engine_explicit_zeros_are_the_plain_request(runs):
+    e, plain, _ = runs
+    z = SamplingParams(greedy=True, max_new_tokens=24, presence_penalty=0.0, frequency_penalty=0.0)
+    assert e.generate_ids([PROMPT], [z])[0] == plain
+    assert all(w.penalty_launches == 0 for w in _eng().workers)
+    seeded = SamplingParams(temperature=1.0, top_k=40, seed=99, max_new_tokens=8)
+    zs = SamplingParams(temperature=1.0, top_k=40, seed=99, max_new_tokens=8, presence_penalty=0.0,
+                        frequency_penalty=0.0)
+    e2 = _eng()
+    assert e2.generate_ids([PROMPT], [zs]) == e2.generate_ids([PROMPT], [seeded])
+    assert all(w.penalty_launches == 0 for w in e2.workers)
+    assert sum(w.penalty_launches for w in e.workers) > 0  # the module's engine ran penalised requests
+
+
+def test_engine_mixed_steps_match_separate_forwards():
+    """A step that decodes rows and prefills joining prompts in one forward
+    (pipeline.py _mixed) penalises and records like the decode item + separate
+    prefill: same tokens, with penalised and default requests joining a
+    running batch at different steps."""
+    import random
+    import time
+
+    rnd = random.Random(5)
+    prompts = [[rnd.randrange(1, 200) for _ in range(rnd.randint(2, 9))] for _ in range(9)]
+    sps = [SamplingParams(greedy=i % 2 == 0, temperature=0.8, top_k=20, seed=100 + i, max_new_tokens=rnd.randint(4, 12),
+                          presence_penalty=(1.5, 0.0, -1.0)[i % 3], frequency_penalty=(0.5, 0.0, 2.0)[i % 3])
+           for i in range(9)]
+
+    def run(mixed: bool):
+        e = _eng(max_batch=16, num_microbatches=2)
+        for w in e.workers:
+            w.mixed_steps = mixed
+        e.start_loop()
+        try:
+            reqs = []
+            for i, (p, sp) in enumerate(zip(prompts, sps)):
+                reqs.append(e.submit(p, sp))
+                if i % 3 == 2:  # let the running batch advance before more join
+                    st = e.scheduler.stats["steps"]
+                    while e.scheduler.stats["steps"] < st + 2 and not all(r.done for r in reqs):
+                        time.sleep(0.001)
+            out = [r.wait(60) for r in reqs]
+        finally:
+            e.stop_loop()
+        return out, sum(w.mixed_items for w in e.workers)
+
+    sep, n_sep = run(False)
+    mix, n_mix = run(True)
+    assert n_sep == 0 and n_mix > 0
+    assert mix == sep
+    e = _eng(max_batch=16)
+    assert [e.generate_ids([p], [sp])[0] for p, sp in zip(prompts, sps)] == sep  # and each request alone
+
+
+@pytest.fixture(scope="module")
+def client():
+    from fastapi.testclient import TestClient
+
+    from llm_sharding_demo_amd.serving.server import create_app
+
+    cfg = EngineConfig(model_id="gpt2-test", max_batch=4, device="cpu", role="coordinator")
+    return TestClient(create_app(cfg, engine=Engine(cfg)))
+
+
+def test_http_generate_accepts_and_validates(client):
+    body = {"prompt": "Hi, ", "max_new_tokens": 3, "presence_penalty": 0.5, "frequency_penalty": -0.5}
+    r = client.post("/generate", json=body)
+    assert r.status_code == 200 and r.json()["generated"].startswith("Hi, ")
+    for field in ("presence_penalty", "frequency_penalty"):
+        for greedy in (False, True):
+            bad = {"prompt": "Hi, ", "max_new_tokens": 3, "greedy": greedy, field: 3.0}
+            assert client.post("/generate", json=bad).status_code == 422
+    props = client.get("/openapi.json").json()["components"]["schemas"]["GenerateReq"]["properties"]
+    assert "presence_penalty" in props and "frequency_penalty" in props
+
+
+def test_client_and_llm_forward_the_fields(monkeypatch):
+    import requests
+
+    from llm_sharding_demo_amd import LLM
+    from llm_sharding_demo_amd.serving import client as cl
+
+    sent = {}
+
+    class R:
+        status_code = 200
+
+        def json(self):
+            return {"generated": "x"}
+
+    def post(url, json=None, timeout=None):
+        sent.update(json)
+        return R()
+
+    monkeypatch.setattr(requests, "post", post)
+    cl.generate_text("Hi, ", presence_penalty=0.5, frequency_penalty=0.25)
+    assert sent["presence_penalty"] == 0.5 and sent["frequency_penalty"] == 0.25
+    sent.clear()
+    cl.generate_text("Hi, ")
+    assert "presence_penalty" not in sent and "frequency_penalty" not in sent
+    llm = LLM(EngineConfig(model_id="gpt2-test", max_batch=4, device="cpu"))
+    plain = llm.generate_text("Hi, ", max_new_tokens=12, greedy=True)
+    pen = llm.generate_text("Hi, ", max_new_tokens=12, greedy=True, presence_penalty=2.0, frequency_penalty=2.0)
+    ids = llm.engine.generate_ids([llm.tokenizer.encode("Hi, ")], [SamplingParams(
+        greedy=True, max_new_tokens=12, presence_penalty=2.0, frequency_penalty=2.0)])[0]
+    assert pen != plain and pen == {"generated": llm.tokenizer.decode(llm.tokenizer.encode("Hi, ") + ids,
+                                                                       skip_special_tokens=True)}
+    with pytest.raises(ValueError):
+        llm.generate_text("Hi, ", max_new_tokens=4, greedy=True, frequency_penalty=3.0)
