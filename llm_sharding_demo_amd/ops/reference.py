@@ -91,12 +91,14 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     q: [T, nh, hd] packed; sequence i owns rows cu_q[i]:cu_q[i+1], whose
     positions are q_start[i] + j.  Keys/values for sequence i live at
     k_cache[seq_slots[i], :, 0:q_start[i]+len_i].  GQA: nh % n_kv == 0.
-    Returns fp32 [T, nh, hd].
+    Returns fp32 [T, nh, hd]; fp64 when q is fp64 (the tests' high-precision
+    reference).
     """
     nh, hd = q.shape[1], q.shape[2]
     n_kv = k_cache.shape[1]
     grp = nh // n_kv
-    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    dt = torch.float64 if q.dtype == torch.float64 else torch.float32
+    out = torch.empty(q.shape, dtype=dt, device=q.device)
     scale = 1.0 / math.sqrt(hd)
     for i in range(seq_slots.numel()):
         a, b = int(cu_q[i]), int(cu_q[i + 1])
@@ -105,9 +107,9 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
         st = int(q_start[i])
         L = st + (b - a)
         s = int(seq_slots[i])
-        kk = k_cache[s, :, :L].float().repeat_interleave(grp, dim=0)  # [nh, L, hd]
-        vv = v_cache[s, :, :L].float().repeat_interleave(grp, dim=0)
-        qq = q[a:b].float().transpose(0, 1)  # [nh, Lq, hd]
+        kk = k_cache[s, :, :L].to(dt).repeat_interleave(grp, dim=0)  # [nh, L, hd]
+        vv = v_cache[s, :, :L].to(dt).repeat_interleave(grp, dim=0)
+        qq = q[a:b].to(dt).transpose(0, 1)  # [nh, Lq, hd]
         sc = torch.matmul(qq, kk.transpose(1, 2)) * scale  # [nh, Lq, L]
         qpos = torch.arange(st, L, device=q.device)[:, None]
         kpos = torch.arange(L, device=q.device)[None, :]

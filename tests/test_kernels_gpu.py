@@ -8,6 +8,8 @@ import torch
 
 from llm_sharding_demo_amd.ops import reference as ref
 
+from . import attention_probes as ap
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -584,7 +586,7 @@ def test_attention_decode(C, hd, nh, n_kv, splits, max_wg, B, small_waves):
     C.attn_set_small_waves(small_waves)
     C.attn_set_small_waves128(small_waves)
     try:
-        _attention_decode_case(C, hd, nh, n_kv, splits, B)
+        _attention_decode_case(C, hd, nh, n_kv, splits, B, max_wg)
     finally:
         C.attn_set_max_wg(0)
         C.attn_set_small_waves(HipBackend.R.attn_small_waves)
@@ -595,16 +597,44 @@ def test_attention_decode(C, hd, nh, n_kv, splits, max_wg, B, small_waves):
 @pytest.mark.parametrize("lw", [8, 42, 2])
 def test_attention_decode_full_batch_blocks(C, hd, nh, n_kv, lw):
     """Full-batch block shapes of the VALU decode kernel (A/B variants of the
-    4-wave default): 8 waves, 4 waves with 2 keys per wave in flight, 2 waves."""
+    4-wave default): 8 waves, 4 waves with 2 keys per wave in flight, 2 waves.
+    The MFMA kernel is switched off: at its default threshold it would take
+    the grouped 128-dim case with 3 splits (420 waves) away from these blocks."""
     C.attn_set_large_waves(hd, lw)
+    C.attn_set_mfma_min(0)
     try:
-        _attention_decode_case(C, hd, nh, n_kv, 1, 70)
-        _attention_decode_case(C, hd, nh, n_kv, 3, 70)
+        _attention_decode_case(C, hd, nh, n_kv, 1, 70, family="valu")
+        _attention_decode_case(C, hd, nh, n_kv, 3, 70, family="valu")
     finally:
         C.attn_set_large_waves(hd, 4)
+        C.attn_set_mfma_min(256)
 
 
-def _attention_decode_case(C, hd, nh, n_kv, splits, B=5):
+_ATTN_REFS = {}  # case -> (fp32 reference, fp64 reference, attention_bound): computed once, never modified
+
+
+def attn_refs(key, q, kc, vc, seq_slots, q_start, cu_q):
+    if key not in _ATTN_REFS:
+        o_ref = ref.attention(q.cpu(), kc.cpu(), vc.cpu(), seq_slots.cpu(), q_start.cpu(), cu_q.cpu())
+        _ATTN_REFS[key] = (o_ref,) + ap.reference_and_bound(q, kc, vc, seq_slots, q_start, cu_q)
+    return _ATTN_REFS[key]
+
+
+def within_attention_bound(family, o, o64, bound):
+    """|o - fp64 reference| <= 2^-8 (|ref| + A) + 2^-20 A elementwise (A: the
+    attention of |V|): the bf16 store, P rounded to bf16 against an fp32 l on
+    the MFMA kernels, fp32 accumulation -- not a tolerance fitted to the data."""
+    r = ap.bound_ratio(o, o64, bound)
+    print(f"attention_bound[{family}]: err / bound = {r:.3g}")
+    assert r <= 1.0, f"{family}: err / attention_bound = {r:.3g}"
+
+
+def _decode_family(hd, nh, n_kv, B, splits, max_wg=0):
+    """The kernel lsd_attn_decode picks at the default attn_mfma_min of 256."""
+    return "mfma" if hd == 128 and nh // n_kv in (2, 4, 8) and max_wg == 0 and B * n_kv * splits >= 256 else "valu"
+
+
+def _attention_decode_case(C, hd, nh, n_kv, splits, B=5, max_wg=0, family=None):
     slots, S = max(6, B), 300
     kc, vc = bf(slots, n_kv, S, hd, seed=16), bf(slots, n_kv, S, hd, seed=17)
     q = bf(B, nh * hd, seed=18)
@@ -617,8 +647,9 @@ def _attention_decode_case(C, hd, nh, n_kv, splits, B=5):
         pos = torch.randint(0, S, (B,), generator=g).int().to(DEV)
     o = C.attn_decode(q, kc, vc, seq_slots, pos, nh, splits)
     cu = torch.arange(B + 1, dtype=torch.int32)
-    o_ref = ref.attention(q.reshape(B, nh, hd).cpu(), kc.cpu(), vc.cpu(), seq_slots.cpu(), pos.cpu(), cu)
+    o_ref, o64, bound = attn_refs(("decode", hd, nh, n_kv, B), q.reshape(B, nh, hd), kc, vc, seq_slots, pos, cu)
     close(o.reshape(B, nh, hd), o_ref, 2e-2)
+    within_attention_bound(family or _decode_family(hd, nh, n_kv, B, splits, max_wg), o, o64, bound)
 
 
 @pytest.mark.parametrize("nh,n_kv", [(32, 8), (16, 8), (64, 8)])
@@ -636,19 +667,21 @@ def test_attention_decode_mfma_grouped(C, nh, n_kv, B):
     pos = torch.tensor([edge[i] if i < len(edge) else int(torch.randint(0, S, (1,), generator=g))
                         for i in range(B)], dtype=torch.int32, device=DEV)
     cu = torch.arange(B + 1, dtype=torch.int32)
-    o_ref = ref.attention(q.reshape(B, nh, hd).cpu(), kc.cpu(), vc.cpu(), seq_slots.cpu(), pos.cpu(), cu)
+    o_ref, o64, bound = attn_refs(("grouped", nh, n_kv, B), q.reshape(B, nh, hd), kc, vc, seq_slots, pos, cu)
     C.attn_set_mfma_min(1)
     try:
         o = C.attn_decode(q, kc, vc, seq_slots, pos, nh, 1)
     finally:
         C.attn_set_mfma_min(256)
     close(o.reshape(B, nh, hd), o_ref, 2e-2)
+    within_attention_bound("mfma", o, o64, bound)
     C.attn_set_mfma_min(0)
     try:
         o_valu = C.attn_decode(q, kc, vc, seq_slots, pos, nh, 1)
     finally:
         C.attn_set_mfma_min(256)
     close(o, o_valu, 2e-2)
+    within_attention_bound("valu", o_valu, o64, bound)
 
 
 @pytest.mark.parametrize("splits", [2, 5, 16])
@@ -663,7 +696,7 @@ def test_attention_decode_mfma_context_splits(C, splits):
     seq_slots = torch.tensor([7, 0, 3, 5, 1, 2], dtype=torch.int32, device=DEV)
     pos = torch.tensor([1099, 0, 7, 517, 1023, 64], dtype=torch.int32, device=DEV)
     cu = torch.arange(B + 1, dtype=torch.int32)
-    o_ref = ref.attention(q.reshape(B, nh, hd).cpu(), kc.cpu(), vc.cpu(), seq_slots.cpu(), pos.cpu(), cu)
+    o_ref, o64, bound = attn_refs("context_splits", q.reshape(B, nh, hd), kc, vc, seq_slots, pos, cu)
     C.attn_set_mfma_min(1)
     try:
         o = C.attn_decode(q, kc, vc, seq_slots, pos, nh, splits)
@@ -671,6 +704,7 @@ def test_attention_decode_mfma_context_splits(C, splits):
         C.attn_set_mfma_min(256)
     assert torch.isfinite(o.float()).all()
     close(o.reshape(B, nh, hd), o_ref, 2e-2)
+    within_attention_bound("mfma", o, o64, bound)
 
 
 def test_decode_attn_split_policy():
@@ -698,9 +732,10 @@ def test_attention_prefill_ragged_chunked(C, hd, nh, n_kv):
     q = bf(meta.num_tokens, nh * hd, seed=21)
     o = C.attn_prefill(q, kc, vc, prefill_tiles(meta).to(DEV), meta.seq_slots, meta.q_start,
                        meta.cu_q, nh)
-    o_ref = ref.attention(q.reshape(-1, nh, hd).cpu(), kc.cpu(), vc.cpu(), meta.seq_slots.cpu(),
-                          meta.q_start.cpu(), meta.cu_q.cpu())
+    o_ref, o64, bound = attn_refs(("prefill", hd), q.reshape(-1, nh, hd), kc, vc, meta.seq_slots,
+                                  meta.q_start, meta.cu_q)
     close(o.reshape(-1, nh, hd), o_ref, 2e-2)
+    within_attention_bound("prefill", o, o64, bound)
 
 
 def test_attention_prefill_large_logits_stable(C):
@@ -715,10 +750,11 @@ def test_attention_prefill_large_logits_stable(C):
     q = bf(256, nh * hd, scale=3.0, seed=24)
     o = C.attn_prefill(q, kc, vc, prefill_tiles(meta).to(DEV), meta.seq_slots, meta.q_start,
                        meta.cu_q, nh)
-    o_ref = ref.attention(q.reshape(-1, nh, hd).cpu(), kc.cpu(), vc.cpu(), meta.seq_slots.cpu(),
-                          meta.q_start.cpu(), meta.cu_q.cpu())
+    o_ref, o64, bound = attn_refs("prefill_spiky", q.reshape(-1, nh, hd), kc, vc, meta.seq_slots,
+                                  meta.q_start, meta.cu_q)
     assert torch.isfinite(o.float()).all()
     close(o.reshape(-1, nh, hd), o_ref, 3e-2)
+    within_attention_bound("prefill", o, o64, bound)
 
 
 @pytest.mark.parametrize("M,N,K,kind,splits", [(1, 1040, 128, 1, 1), (64, 1040, 640, 1, 1),
@@ -956,12 +992,22 @@ def test_attention_oproj_fused(C, CNT, hd, nh, n_kv, N, B, nc):
         C_ = max(1, -(-256 // n_kv))
         nc = -(-(-(-N // C_)) // 16) * 16
     cu = torch.arange(B + 1, dtype=torch.int32)
-    o_ref = ref.attention(q.reshape(B, nh, hd).cpu(), kc.cpu(), vc.cpu(), seq_slots.cpu(), pos.cpu(), cu)
+    o_ref, o64, o_bound = attn_refs(("oproj", hd, nh, n_kv, B), q.reshape(B, nh, hd), kc, vc, seq_slots, pos, cu)
     y_ref = o_ref.reshape(B, nh * hd).float() @ w.float().cpu().t() + bias.float().cpu()
     x0 = torch.randn(B, N, device=DEV)
     x = x0.clone()
     C.attn_oproj(q, kc, vc, seq_slots, pos, nh, w, bias, x, nc, CNT)
     close(x - x0, y_ref, 2e-2)
+    # attention_bound carried through the projection: |W| . bound(o), plus the
+    # projection's own fp32 sums (at most 64 roundings deep: 16 products per
+    # lane, 6 lane exchanges, <= 25 kv-head partials, bias, residual add) on
+    # |W| . |o| + |b|, plus the fp32 rounding of x and of x - x0
+    w64, b64 = w.cpu().double(), bias.cpu().double()
+    y64 = o64.reshape(B, nh * hd) @ w64.t() + b64
+    y_bound = (o_bound.reshape(B, nh * hd) @ w64.abs().t()
+               + 2.0 ** -18 * (o64.abs().reshape(B, nh * hd) @ w64.abs().t() + b64.abs())
+               + 2.0 ** -22 * (x0.cpu().double().abs() + y64.abs()))
+    within_attention_bound("fused", x.cpu().double() - x0.cpu().double(), y64, y_bound)
     x2 = x0.clone()
     C.attn_oproj(q, kc, vc, seq_slots, pos, nh, w, bias, x2, nc, CNT)
     assert torch.equal(x, x2)
