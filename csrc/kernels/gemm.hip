@@ -1881,6 +1881,17 @@ __global__ __launch_bounds__(512) void gemm_d256_kernel(GemmParams p, int* __res
 // ---------------------------------------------------------------------------
 // Host launchers
 // ---------------------------------------------------------------------------
+// Name of the kernel (and its non-epilogue template arguments) of the last
+// launch, set by every branch below: lsd_gemm_last_launch() lets a test see
+// which kernel its knobs and shape really reached.  A diagnostic: one plain
+// pointer to a string literal, last writer wins across threads.
+static const char* g_last_launch = "";
+#define LSD_LAUNCH(tag, ...)          \
+  do {                                \
+    g_last_launch = tag;              \
+    hipLaunchKernelGGL(__VA_ARGS__);  \
+  } while (0)
+
 static int g_big_min_blocks = 160;  // lsd_gemm_set_big_min(): tuning / tests
 // lsd_gemm_set_big_group(): tile_order() group (0 = M-fastest).  4: XL prefill
 // GEMMs 10-25 % faster than M-fastest, 8 equal, 16+ slower
@@ -1942,12 +1953,12 @@ static hipError_t launch_sk_nw(const GemmParams& p, int* cnt, float* ws, hipStre
   const int MT = sk_mt(p.M, RB);
   dim3 grid((p.N + 64 * NW - 1) / (64 * NW), p.splits, RB), block(256);
   switch (MT) {
-    case 1: hipLaunchKernelGGL((gemm_sk_kernel<1, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    case 2: hipLaunchKernelGGL((gemm_sk_kernel<2, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    case 3: hipLaunchKernelGGL((gemm_sk_kernel<3, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    case 4: hipLaunchKernelGGL((gemm_sk_kernel<4, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    case 6: hipLaunchKernelGGL((gemm_sk_kernel<6, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    case 8: hipLaunchKernelGGL((gemm_sk_kernel<8, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
+    case 1: LSD_LAUNCH(NW == 2 ? "sk<1,2>" : "sk<1,1>", (gemm_sk_kernel<1, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
+    case 2: LSD_LAUNCH(NW == 2 ? "sk<2,2>" : "sk<2,1>", (gemm_sk_kernel<2, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
+    case 3: LSD_LAUNCH(NW == 2 ? "sk<3,2>" : "sk<3,1>", (gemm_sk_kernel<3, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
+    case 4: LSD_LAUNCH(NW == 2 ? "sk<4,2>" : "sk<4,1>", (gemm_sk_kernel<4, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
+    case 6: LSD_LAUNCH(NW == 2 ? "sk<6,2>" : "sk<6,1>", (gemm_sk_kernel<6, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
+    case 8: LSD_LAUNCH(NW == 2 ? "sk<8,2>" : "sk<8,1>", (gemm_sk_kernel<8, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -1975,14 +1986,14 @@ static hipError_t launch_d256_bn(const GemmParams& p, int* cnt, float* ws, hipSt
   const dim3 grid(((p.N + BN - 1) / BN) * ((p.M + 255) / 256) * p.splits), block(512);
   const int slots = BN == 128 ? min(g_d256_slots, 3) : g_d256_slots;
   switch (slots) {
-    case 2: hipLaunchKernelGGL((gemm_d256_kernel<EPI, BN, 2>), grid, block, 0, st, p, cnt, ws); break;
+    case 2: LSD_LAUNCH(BN == 128 ? "d256<128,2>" : "d256<64,2>", (gemm_d256_kernel<EPI, BN, 2>), grid, block, 0, st, p, cnt, ws); break;
     case 4:
       if constexpr (BN == 64) {
-        hipLaunchKernelGGL((gemm_d256_kernel<EPI, BN, 4>), grid, block, 0, st, p, cnt, ws);
+        LSD_LAUNCH("d256<64,4>", (gemm_d256_kernel<EPI, BN, 4>), grid, block, 0, st, p, cnt, ws);
         break;
       }
       [[fallthrough]];
-    default: hipLaunchKernelGGL((gemm_d256_kernel<EPI, BN, 3>), grid, block, 0, st, p, cnt, ws); break;
+    default: LSD_LAUNCH(BN == 128 ? "d256<128,3>" : "d256<64,3>", (gemm_d256_kernel<EPI, BN, 3>), grid, block, 0, st, p, cnt, ws); break;
   }
   return hipGetLastError();
 }
@@ -2002,13 +2013,13 @@ static hipError_t launch_tiled(const GemmParams& p, int* cnt, float* ws, hipStre
   const int bm = (p.M + GBM - 1) / GBM, bn = (p.N + GBN - 1) / GBN;
   if (p.M >= GBM && p.K % 64 == 0 && bm * bn * p.splits >= g_big_min_blocks) {
     if (g_big_kind == 1)
-      hipLaunchKernelGGL((gemm_p8_kernel<EPI, 0>), dim3(bm * bn * p.splits), dim3(512), 0, st, p, bm, bn,
+      LSD_LAUNCH("p8<0>", (gemm_p8_kernel<EPI, 0>), dim3(bm * bn * p.splits), dim3(512), 0, st, p, bm, bn,
                          g_big_group);
     else if (g_big_kind == 4)
-      hipLaunchKernelGGL((gemm_p8_kernel<EPI, 4>), dim3(bm * bn * p.splits), dim3(512), 0, st, p, bm, bn,
+      LSD_LAUNCH("p8<4>", (gemm_p8_kernel<EPI, 4>), dim3(bm * bn * p.splits), dim3(512), 0, st, p, bm, bn,
                          g_big_group);
     else
-      hipLaunchKernelGGL((gemm_big_kernel<EPI>), dim3(bm * bn * p.splits), dim3(512), 0, st, p, bm, bn,
+      LSD_LAUNCH("big", (gemm_big_kernel<EPI>), dim3(bm * bn * p.splits), dim3(512), 0, st, p, bm, bn,
                          g_big_group);
     return hipGetLastError();
   }
@@ -2020,8 +2031,8 @@ static hipError_t launch_tiled(const GemmParams& p, int* cnt, float* ws, hipStre
     const bool narrow = g_ring_tn == 32 || (g_ring_tn == 0 && tm * tn64 * p.splits < g_ring_fill);
     if (narrow && (p.N % 32) == 0) {
       const int tn = (p.N + 31) / 32;
-      if (tm * tn * p.splits <= 2 * g_tiled3_max_blocks) {
-        hipLaunchKernelGGL((gemm_ring_kernel<EPI, 3, 32>), dim3(tm * tn * p.splits), dim3(256), 0, st, p, tm, tn);
+      if (tm * tn * p.splits <= 2L * g_tiled3_max_blocks) {  // long: the tests' "no cap" is 1 << 30
+        LSD_LAUNCH("ring<3,32>", (gemm_ring_kernel<EPI, 3, 32>), dim3(tm * tn * p.splits), dim3(256), 0, st, p, tm, tn);
         return hipGetLastError();
       }
     }
@@ -2036,7 +2047,7 @@ static hipError_t launch_tiled(const GemmParams& p, int* cnt, float* ws, hipStre
     if (p.splits == 1 && p.M > TBM && g_ring_m96 > 0) {
       const int tm96 = (p.M + 95) / 96;
       if (tm96 * tn64 <= g_ring_m96) {
-        hipLaunchKernelGGL((gemm_ring_kernel<EPI, 3, 64, 3>), dim3(tm96 * tn64), dim3(256), 0, st, p, tm96, tn64);
+        LSD_LAUNCH("ring<3,64,m96>", (gemm_ring_kernel<EPI, 3, 64, 3>), dim3(tm96 * tn64), dim3(256), 0, st, p, tm96, tn64);
         return hipGetLastError();
       }
     }
@@ -2046,21 +2057,21 @@ static hipError_t launch_tiled(const GemmParams& p, int* cnt, float* ws, hipStre
       const bool combine = p.splits > 1 && EPI != EPI_SLAB;
       if (combine && (g_ring8 != 2 || cnt == nullptr || ws == nullptr)) return hipErrorInvalidValue;
       if (g_ring8 == 1)
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 1, 3>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
+        LSD_LAUNCH("ring8<1,3>", (gemm_ring8_kernel<EPI, 1, 3>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
       else if (g_ring8 == 2 && g_ring8_pack == 1)
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 2, 3, 0, 1>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
+        LSD_LAUNCH("ring8<2,3,pk1>", (gemm_ring8_kernel<EPI, 2, 3, 0, 1>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
       else if (g_ring8 == 2 && g_ring8_pack == 2)
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 2, 3, 0, 2>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
+        LSD_LAUNCH("ring8<2,3,pk2>", (gemm_ring8_kernel<EPI, 2, 3, 0, 2>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
       else if (g_ring8 == 2 && g_ring8_pack == 3)
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 2, 3, 0, 3>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
+        LSD_LAUNCH("ring8<2,3,pk3>", (gemm_ring8_kernel<EPI, 2, 3, 0, 3>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
       else if (g_ring8 == 2 && (g_ring8_flags & 4))
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 2, 3, 0, 0, true>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
+        LSD_LAUNCH("ring8<2,3,bl>", (gemm_ring8_kernel<EPI, 2, 3, 0, 0, true>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
       else if (g_ring8 == 2 && (g_ring8_flags & 2))
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 2, 3, 1>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
+        LSD_LAUNCH("ring8<2,3,nt>", (gemm_ring8_kernel<EPI, 2, 3, 1>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
       else if (g_ring8 == 2)
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 2, 3>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
+        LSD_LAUNCH("ring8<2,3>", (gemm_ring8_kernel<EPI, 2, 3>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
       else
-        hipLaunchKernelGGL((gemm_ring_kernel<EPI, 3, 64>), dim3(tm * tn64 * p.splits), dim3(256), 0, st, p, tm, tn64);
+        LSD_LAUNCH("ring<3,64>", (gemm_ring_kernel<EPI, 3, 64>), dim3(tm * tn64 * p.splits), dim3(256), 0, st, p, tm, tn64);
       return hipGetLastError();
     }
   }
@@ -2071,11 +2082,11 @@ static hipError_t launch_tiled(const GemmParams& p, int* cnt, float* ws, hipStre
   // 2-blocks/CU kernel; profiles/r1_ab_ring_n64.log)
   const int cap128 = g_tiled3_max_blocks / 2;
   if (tm * tn * p.splits <= cap128 && g_ring_slots == 4)
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI, 4, 128>), grid, block, 0, st, p, tm, tn);
+    LSD_LAUNCH("ring<4,128>", (gemm_ring_kernel<EPI, 4, 128>), grid, block, 0, st, p, tm, tn);
   else if (tm * tn * p.splits <= cap128)
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI, 3, 128>), grid, block, 0, st, p, tm, tn);
+    LSD_LAUNCH("ring<3,128>", (gemm_ring_kernel<EPI, 3, 128>), grid, block, 0, st, p, tm, tn);
   else
-    hipLaunchKernelGGL((gemm_tiled_kernel<EPI>), grid, block, 0, st, p, tm, tn);
+    LSD_LAUNCH("tiled", (gemm_tiled_kernel<EPI>), grid, block, 0, st, p, tm, tn);
   return hipGetLastError();
 }
 
@@ -2083,6 +2094,7 @@ static hipError_t launch_tiled(const GemmParams& p, int* cnt, float* ws, hipStre
 
 using namespace lsd;
 
+extern "C" const char* lsd_gemm_last_launch() { return g_last_launch; }
 extern "C" void lsd_gemm_set_big_min(int v) { g_big_min_blocks = v; }
 extern "C" void lsd_gemm_set_big_group(int v) { g_big_group = v < 0 ? 0 : v; }
 extern "C" void lsd_gemm_set_big_kind(int v) { g_big_kind = (v == 1 || v == 4) ? v : 0; }
@@ -2108,7 +2120,7 @@ extern "C" int lsd_gemm_ring8_tiles(int M, int N, int K, int S) {
   if (!(g_ring_tn == 64 || g_ring_tn == 32 || g_ring_tn == 0)) return 0;
   const int tm = (M + TBM - 1) / TBM, tn64 = (N + 63) / 64;
   const bool narrow = g_ring_tn == 32 || (g_ring_tn == 0 && tm * tn64 * S < g_ring_fill);
-  if (narrow && (N % 32) == 0 && tm * ((N + 31) / 32) * S <= 2 * g_tiled3_max_blocks) return 0;
+  if (narrow && (N % 32) == 0 && tm * ((N + 31) / 32) * S <= 2L * g_tiled3_max_blocks) return 0;
   if (S == 1 && M > TBM && g_ring_m96 > 0 && ((M + 95) / 96) * tn64 <= g_ring_m96) return 0;
   return tm * tn64 * S <= g_tiled3_max_blocks ? tm * tn64 : 0;
 }

@@ -165,14 +165,28 @@ def test_linear_residual_bf16_slabs(C, CNT, tiled, M, splits):
     """bf16 partial slabs: each split's partial rounded once to bf16 (a bf16
     GEMM output's precision), folded into the fp32 residual by the norm.  One
     split with defer: the prefill form (the GEMM writes one bf16 slab instead
-    of a read-modify-write of the fp32 residual)."""
+    of a read-modify-write of the fp32 residual).  The kernels named above
+    are the engine's routing (HipBackend's knobs), set here: at the library
+    defaults every tiled case below would run the 128x128 kernel instead."""
     C.gemm_set_slab_bf16(1)
+    C.gemm_set_tiled3_max(512)
+    C.gemm_set_ring_tn(0)
+    C.gemm_set_ring8(2)
     N, K = 1600, 1600
     a, w, bias = bf(M, K, seed=8), bf(N, K, scale=0.05, seed=9), bf(N, scale=0.1, seed=10)
     x = torch.randn(M, N, device=DEV)
     y = ref.linear(a, w, bias)
     x_ref = x + y
-    slab = C.linear_residual(a, w, bias, x, splits, tiled, CNT, not tiled or splits == 1)
+    try:
+        slab = C.linear_residual(a, w, bias, x, splits, tiled, CNT, not tiled or splits == 1)
+        # 3000 rows: 600 128x64 tiles are past the rings' cap, the 128x128 kernel takes them
+        assert C.gemm_last_launch() == {(256, 3): "ring8<2,3>", (256, 5): "ring8<2,3>", (130, 3): "ring8<2,3>",
+                                        (64, 5): "sk<4,1>", (1024, 6): "p8<4>", (1024, 1): "ring8<2,3>",
+                                        (3000, 1): "tiled"}[(M, splits)]
+    finally:
+        C.gemm_set_tiled3_max(0)
+        C.gemm_set_ring_tn(128)
+        C.gemm_set_ring8(0)
     assert slab is not None and slab.dtype == torch.bfloat16 and slab.shape == (splits, M, N)
     C.norm(x, slab, bias, None, None, 0.0, True, None, False)
     # error of S bf16 roundings of partials of |y| / sqrt(S)-ish size
@@ -297,7 +311,7 @@ def RING(C, request):
 
 @pytest.mark.parametrize("M", [100, 256, 300])
 @pytest.mark.parametrize("K", [64, 128, 192, 256, 640])
-def test_ring_gemm_epilogues(RING, CNT, M, K):
+def test_ring_gemm_epilogues(RING, CNT, M, K, request):
     """Ring 128x128 kernel: every epilogue, M/N tails, 1, 2, 3, 4 and 10
     k-steps (fewer than, equal to and more than the ring), split-K slabs."""
     from llm_sharding_demo_amd.ops.hip import interleave_gate_up
@@ -307,6 +321,9 @@ def test_ring_gemm_epilogues(RING, CNT, M, K):
     a, w, bias = bf(M, K, seed=60), bf(N, K, scale=0.05, seed=61), bf(N, scale=0.1, seed=62)
     y_ref = ref.linear(a, w, bias)
     close(C.linear(a, w, bias, 0, True, 1, CNT), y_ref, 3e-2)
+    # the variant the fixture names (auto width: 18 64-wide workgroups are below ring_fill, so 32-wide)
+    slots, tn = request.node.callspec.params["RING"]
+    assert C.gemm_last_launch() == (f"ring<{slots},128>" if tn == 128 else "ring<3,64>" if tn == 64 else "ring<3,32>")
     close(C.linear(a, w, bias, 1, True, 1, CNT), ref.gelu_new(y_ref), 3e-2)
     w2 = w[:256].contiguous()
     y = C.linear(a, interleave_gate_up(w2, 128).contiguous(), None, 2, True, 1, CNT)
