@@ -19,6 +19,7 @@ using lsd::GemvParams;
 extern "C" {
 hipError_t lsd_gemm(const GemmParams* p, int epi, int tiled, int* cnt, float* ws, hipStream_t st);
 const char* lsd_gemm_last_launch();
+const char* lsd_norm_last_launch();
 void lsd_gemm_set_big_min(int v);
 void lsd_gemm_set_big_group(int v);
 void lsd_gemm_set_big_kind(int v);
@@ -871,6 +872,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_stamps", &set_stamps);
   // tiled GEMMs with >= this many 256x256 tiles use the pipelined 256^2 kernel
   m.def("gemm_last_launch", [] { return std::string(lsd_gemm_last_launch()); });
+  m.def("norm_last_launch", [] { return std::string(lsd_norm_last_launch()); });
   m.def("gemm_set_big_min", [](int64_t v) { lsd_gemm_set_big_min((int)v); });
   // large-GEMM tile order: groups of this many row panels (0 = M-fastest)
   m.def("gemm_set_big_group", [](int64_t v) { lsd_gemm_set_big_group((int)v); });

@@ -10,6 +10,8 @@
 //   y[t]  = norm(x[t]) * w (+ b)          (bf16, the next GEMM's A operand)
 // in one pass over the row -- the "combine in the next kernel's prologue"
 // launch-boundary reduce (guide §5 Projection GEMM item 2), deterministic.
+#include <cstdio>
+
 #include "common.h"
 
 namespace lsd {
@@ -313,9 +315,43 @@ static int norm_wave_rows(int H) {
   return m;
 }
 
-extern "C" hipError_t lsd_norm(float* x, const void* slab, int slab_bf16, int splits, const bf16* pbias,
-                               const bf16* w, const bf16* b, bf16* out, int T, int H, float eps,
-                               int rms, const int* rows, int nrows, hipStream_t st) {
+// The kernel(s) of the calling thread's last lsd_norm, recorded by every launch
+// branch below as a few small integers and spelled out by
+// lsd_norm_last_launch(): lets a test see which instantiation its thresholds
+// and shape really reached.  A diagnostic; nothing reads it on the hot path.
+//   block<MAXV,ln|rms|fold,sSPL|loop[,f32|bf16]>   (fold: no output requested)
+//   wave<MAXC,ln|rms[,sSPL,f32|bf16]>
+// joined by '+' when one call launches two kernels (fold first, then wave).
+struct NormTag {
+  signed char wave, width, kind, spl, sb;  // kind 0 ln, 1 rms, 2 fold; spl -1 loop; sb -1 none
+};
+static thread_local NormTag g_norm_tags[2];
+static thread_local int g_norm_ntags = 0;
+static void norm_tag(int wave, int width, int kind, int spl, int sb) {
+  if (g_norm_ntags < 2) g_norm_tags[g_norm_ntags++] = NormTag{(signed char)wave, (signed char)width, (signed char)kind,
+                                                             (signed char)spl, (signed char)sb};
+}
+
+extern "C" const char* lsd_norm_last_launch() {
+  static thread_local char text[96];
+  static const char* const kinds[3] = {"ln", "rms", "fold"};
+  int off = 0;
+  text[0] = 0;
+  for (int i = 0; i < g_norm_ntags && off < (int)sizeof(text); ++i) {
+    const NormTag& t = g_norm_tags[i];
+    char spl[12] = "", sb[8] = "";
+    if (t.spl < 0) snprintf(spl, sizeof(spl), ",loop");
+    else if (!t.wave || t.spl > 0) snprintf(spl, sizeof(spl), ",s%d", t.spl);
+    if (t.sb >= 0) snprintf(sb, sizeof(sb), ",%s", t.sb ? "bf16" : "f32");
+    off += snprintf(text + off, sizeof(text) - off, "%s%s<%d,%s%s%s>", i ? "+" : "", t.wave ? "wave" : "block", t.width,
+                    kinds[t.kind], spl, sb);
+  }
+  return text;
+}
+
+static hipError_t norm_launch(float* x, const void* slab, int slab_bf16, int splits, const bf16* pbias,
+                              const bf16* w, const bf16* b, bf16* out, int T, int H, float eps,
+                              int rms, const int* rows, int nrows, hipStream_t st) {
   const int n = rows ? nrows : T;
   if (n == 0) return hipSuccess;
   const int wmin = norm_wave_rows(H);
@@ -334,6 +370,7 @@ extern "C" hipError_t lsd_norm(float* x, const void* slab, int slab_bf16, int sp
   } else {                 \
     LSD_NORM_WS(S, false)  \
   }
+    norm_tag(1, 4, rms ? 1 : 0, splits, slab_bf16 ? 1 : 0);
     switch (splits) {
       case 1: LSD_NORM_WB(1) break;
       case 2: LSD_NORM_WB(2) break;
@@ -351,8 +388,8 @@ extern "C" hipError_t lsd_norm(float* x, const void* slab, int slab_bf16, int sp
   if (wave && slab) {
     // other slab counts / widths: fold first (the block kernel's combine-only
     // pass, the same add order), then the slab-free wave kernel below
-    const hipError_t e = lsd_norm(x, slab, slab_bf16, splits, pbias, nullptr, nullptr, nullptr, T, H, eps, rms,
-                                  nullptr, 0, st);
+    const hipError_t e = norm_launch(x, slab, slab_bf16, splits, pbias, nullptr, nullptr, nullptr, T, H, eps, rms,
+                                     nullptr, 0, st);
     if (e != hipSuccess) return e;
     slab = nullptr;
   }
@@ -361,6 +398,7 @@ extern "C" hipError_t lsd_norm(float* x, const void* slab, int slab_bf16, int sp
 #define LSD_NORM_W(MC)                                                                                           \
   if (rms) hipLaunchKernelGGL((norm_wave_kernel<MC, true>), wg, wb, 0, st, x, nullptr, nullptr, w, b, out, T, H, eps); \
   else hipLaunchKernelGGL((norm_wave_kernel<MC, false>), wg, wb, 0, st, x, nullptr, nullptr, w, b, out, T, H, eps);
+    norm_tag(1, nch <= 256 ? 4 : nch <= 512 ? 8 : 16, rms ? 1 : 0, 0, -1);
     if (nch <= 256) {
       LSD_NORM_W(4)
     } else if (nch <= 512) {
@@ -398,6 +436,11 @@ extern "C" hipError_t lsd_norm(float* x, const void* slab, int slab_bf16, int sp
     case 8: LSD_NORM_S(MV, 8) break;   \
     default: LSD_NORM_S(MV, -1) break; \
   }
+  if (maxv <= 8) {
+    const int ns = slab ? splits : 0;
+    norm_tag(0, maxv <= 2 ? 2 : maxv <= 4 ? 4 : 8, out ? (rms ? 1 : 0) : 2, ns <= 8 ? ns : -1,
+             slab ? (slab_bf16 ? 1 : 0) : -1);
+  }
   if (maxv <= 2) {
     LSD_NORM(2)
   } else if (maxv <= 4) {
@@ -411,4 +454,11 @@ extern "C" hipError_t lsd_norm(float* x, const void* slab, int slab_bf16, int sp
 #undef LSD_NORM_S
 #undef LSD_NORM
   return hipGetLastError();
+}
+
+extern "C" hipError_t lsd_norm(float* x, const void* slab, int slab_bf16, int splits, const bf16* pbias,
+                               const bf16* w, const bf16* b, bf16* out, int T, int H, float eps,
+                               int rms, const int* rows, int nrows, hipStream_t st) {
+  g_norm_ntags = 0;
+  return norm_launch(x, slab, slab_bf16, splits, pbias, w, b, out, T, H, eps, rms, rows, nrows, st);
 }

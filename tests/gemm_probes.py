@@ -320,14 +320,15 @@ def rope_rotate(v: torch.Tensor, tpos: torch.Tensor, table: torch.Tensor) -> tor
     return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1)
 
 
-def qkv_expected(y: torch.Tensor, N: int, tslot, tpos, slots: int, S: int, table=None, guard: int = 1):
+def qkv_expected(y: torch.Tensor, N: int, tslot, tpos, slots: int, S: int, table=None, guard: int = 1, dims=None):
     """From the exact y + bias [M, N] in the model's column order: q fp64
     [M, q_size] and the two whole cache buffers (guard slots included,
     SENTINEL wherever nothing is written) as bf16.  With a table, q and K are
-    rotated and returned in the kernel's pair order."""
+    rotated and returned in the kernel's pair order.  dims: (q_size, kv_size,
+    hd, n_heads, n_kv) when they are not qkv_dims(N)."""
     from llm_sharding_demo_amd.ops.hip import rope_pair_permutation
 
-    qs, kvs, hd, nh, nkv = qkv_dims(N)
+    qs, kvs, hd, nh, nkv = dims or qkv_dims(N)
     M = y.shape[0]
     y = y.double()
     q = y[:, :qs].reshape(M, nh, hd)

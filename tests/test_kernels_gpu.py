@@ -36,8 +36,22 @@ def test_embed(C):
     wte, wpe = bf(V, H, seed=1), bf(P, H, seed=2)
     ids = torch.randint(0, V, (T,), dtype=torch.int32, device=DEV)
     pos = torch.randint(0, P, (T,), dtype=torch.int32, device=DEV)
-    close(C.embed(ids, pos, wte, wpe), ref.embed(ids, pos, wte, wpe), 1e-6)
-    close(C.embed(ids, pos, wte, None), ref.embed(ids, pos, wte, None), 1e-6)
+    assert torch.equal(C.embed(ids, pos, wte, wpe), ref.embed(ids, pos, wte, wpe))  # one fp32 add: exact
+    assert torch.equal(C.embed(ids, pos, wte, None), ref.embed(ids, pos, wte, None))
+
+
+def _norm_tag(C, family, H, rms, S=0, sdt=None, fold_first=False):
+    """The C.norm_last_launch() of the kernel a norm test means to run."""
+    kind = "rms" if rms else "ln"
+    slabs = "" if S == 0 else "," + ("bf16" if sdt == torch.bfloat16 else "f32")
+    block = f"block<{2 if H <= 2048 else 4 if H <= 4096 else 8},{'fold' if fold_first else kind},"
+    block += (f"s{S}" if S <= 8 else "loop") + slabs + ">"
+    wave = f"wave<{4 if H <= 1024 else 8 if H <= 2048 else 16},{kind}"
+    if family == "block":
+        return block
+    if fold_first:
+        return block + "+" + wave + ">"
+    return wave + (f",s{S}{slabs}" if S else "") + ">"
 
 
 @pytest.mark.parametrize("H", [128, 768, 1600, 4096, 8192])
@@ -53,10 +67,12 @@ def test_norm_with_slab_combine(C, H, rms, S, sdt):
     x_ref = x + slab.float().sum(0) + pb.float()
     y_ref = ref.rmsnorm(x_ref, w, 1e-5) if rms else ref.layernorm(x_ref, w, b, 1e-5)
     y = C.norm(x, slab, pb, w, None if rms else b, 1e-5, rms, None, True)
+    assert C.norm_last_launch() == _norm_tag(C, "block", H, rms, S, sdt)
     close(x, x_ref, 1e-5)
     close(y, y_ref, 2e-2)
     rows = torch.tensor([3, 0, 18], dtype=torch.int32, device=DEV)
     y2 = C.norm(x, None, None, w, None if rms else b, 1e-5, rms, rows, True)
+    assert C.norm_last_launch() == _norm_tag(C, "block", H, rms)
     close(y2, y_ref[rows.long()], 2e-2)
 
 
@@ -81,10 +97,13 @@ def test_norm_wave_with_slabs(C, H, rms, S, sdt):
     C.norm_set_wave_narrow_min(0)
     xb = x0.clone()
     yb = C.norm(xb, slab, pb, w, None if rms else b, 1e-5, rms, None, True)  # block kernel
+    assert C.norm_last_launch() == _norm_tag(C, "block", H, rms, S, sdt)
     C.norm_set_wave_narrow_min(1)
     try:
         x = x0.clone()
         y = C.norm(x, slab, pb, w, None if rms else b, 1e-5, rms, None, True)
+        assert C.norm_last_launch() == (_norm_tag(C, "block", H, rms, S, sdt) if H > 1024 else
+                                        _norm_tag(C, "wave", H, rms, S, sdt, fold_first=S > 8))
     finally:
         _norm_defaults(C)
     assert torch.equal(x, xb)
@@ -135,6 +154,7 @@ def test_norm_wave_per_row(C, H, rms, T):
         x0 = x.clone()
         w, b = (1 + 0.1 * torch.randn(H, device=DEV)).bfloat16(), bf(H, scale=0.1, seed=5)
         y = C.norm(x, None, None, w, None if rms else b, 1e-5, rms, None, True)
+        assert C.norm_last_launch() == _norm_tag(C, "wave", H, rms)
         y_ref = ref.rmsnorm(x, w, 1e-5) if rms else ref.layernorm(x, w, b, 1e-5)
         close(y, y_ref, 2e-2)
         assert torch.equal(x, x0)
