@@ -43,8 +43,15 @@ namespace lsd {
 constexpr int SMAX = 1024;   // max top_k on device (host validates)
 constexpr int NT = 1024;     // threads per row
 
+// Order-preserving key of the radix select.  -0.0 takes +0.0's key: every
+// other comparison here (threshold filter, rank selection, bitonic network,
+// greedy) is numeric, where the two are equal and the lower index goes first;
+// keyed apart, a k boundary among zeros would select the +0.0 entries ahead of
+// lower-index -0.0 ones and the radix path would differ from the threshold
+// paths on the same row.  Every other input keeps its key.
 __device__ __forceinline__ unsigned fkey(float x) {
   unsigned u = __float_as_uint(x);
+  if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 

@@ -197,10 +197,13 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
             out[r] = int(torch.argmax(row))
             continue
         k = int(top_k[r])
-        vals, idx = torch.topk(row / float(temperature[r]), k)
-        # stable ordering for ties: by value desc then index asc
-        order = sorted(range(k), key=lambda j: (-float(vals[j]), int(idx[j])))
-        vals, idx = vals[order], idx[order]
+        # logit desc (numeric: -0.0 == +0.0), index asc, through a stable sort of
+        # the whole row: torch.topk leaves open which of several equal values at
+        # the k boundary it returns (not the lowest index).  The order is that
+        # of the logits themselves, as on the device (two logits an ulp apart
+        # can round to one quotient)
+        vals, idx = torch.sort(row, descending=True, stable=True)
+        vals, idx = vals[:k] / float(temperature[r]), idx[:k]
         tp = float(top_p[r]) if top_p is not None else 1.0
         mp = float(min_p[r]) if min_p is not None else 0.0
         if tp < 1.0 or mp > 0.0:
