@@ -81,6 +81,9 @@ hipError_t lsd_penalize(float* logits, long ld, int B, int V, const int* hist, i
                         long ldseg, hipStream_t st);
 hipError_t lsd_record_tokens(int* hist, int L, int nslots, const int* slots, const long long* step, int back,
                              const int* tokens, const int* active, int B, hipStream_t st);
+hipError_t lsd_logprobs(const float* logits, long ld, int B, int V, const int* tokens, const int* nlp, const int* slots,
+                        const long long* step, int back, const int* active, float* lp_tok, int* lp_top_id,
+                        float* lp_top, int L, int nslots, int W, hipStream_t st);
 }
 
 namespace {
@@ -714,9 +717,9 @@ torch::Tensor qkv_post(torch::Tensor y, c10::optional<torch::Tensor> bias, torch
 // elementwise.hip lsd_apply_rows (CPU tensor), on the current stream.
 void apply_rows(torch::Tensor args, int64_t b) {
   TORCH_CHECK(args.device().is_cpu() && args.scalar_type() == torch::kInt64 && args.is_contiguous() &&
-                  (args.numel() == 12 || args.numel() == 14 || args.numel() == 16),
-              "apply_rows: args must be a contiguous CPU int64[12] (or [14], with top_p / min_p, or [16], "
-              "with the penalties too) record");
+                  (args.numel() == 12 || args.numel() == 14 || args.numel() == 16 || args.numel() == 17),
+              "apply_rows: args must be a contiguous CPU int64[12] (or [14], with top_p / min_p, [16], "
+              "with the penalties too, or [17], with the logprob counts) record");
   check_hip(lsd_apply_rows(args.data_ptr<int64_t>(), (int)args.numel(), (int)b, cur_stream()), "apply_rows");
 }
 
@@ -779,6 +782,47 @@ void record_tokens(torch::Tensor hist, torch::Tensor slots, c10::optional<torch:
   }
   check_hip(lsd_record_tokens(hist.data_ptr<int>(), (int)hist.size(1), (int)hist.size(0), slots.data_ptr<int>(), sp,
                               (int)back, tokens.data_ptr<int>(), act, (int)B, cur_stream()), "record_tokens");
+}
+
+// Token logprobs and top-N alternatives (logprob.hip) of the rows with
+// nlp >= 0, from the fp32 logits the sampler drew `tokens` from, into record
+// step[i] - back (step absent = 0, the prefill draw) of KV slot slots[i]:
+// lp_tok [slots, L], lp_top_id / lp_top [slots, L, W].
+void logprobs(torch::Tensor logits, int64_t V, torch::Tensor tokens, torch::Tensor nlp, torch::Tensor slots,
+              c10::optional<torch::Tensor> step, c10::optional<torch::Tensor> active, torch::Tensor lp_tok,
+              torch::Tensor lp_top_id, torch::Tensor lp_top, int64_t back) {
+  need(logits, torch::kFloat32, "logits");
+  need(tokens, torch::kInt32, "tokens");
+  need(nlp, torch::kInt32, "nlp");
+  need(slots, torch::kInt32, "slots");
+  need(lp_tok, torch::kFloat32, "lp_tok");
+  need(lp_top_id, torch::kInt32, "lp_top_id");
+  need(lp_top, torch::kFloat32, "lp_top");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= 1, "logits [B, >=V]");
+  const int64_t B = logits.size(0);
+  for (const torch::Tensor* t : {&tokens, &nlp, &slots})
+    TORCH_CHECK(t->numel() == B && t->is_contiguous(), "logprobs: row vectors must be contiguous [B]");
+  TORCH_CHECK(lp_tok.dim() == 2 && lp_tok.is_contiguous() && lp_top_id.dim() == 3 && lp_top_id.is_contiguous() &&
+                  lp_top.dim() == 3 && lp_top.is_contiguous() && lp_top_id.sizes() == lp_top.sizes() &&
+                  lp_top.size(0) == lp_tok.size(0) && lp_top.size(1) == lp_tok.size(1),
+              "logprobs: records are contiguous lp_tok [slots, L], lp_top_id / lp_top [slots, L, W]");
+  const long long* sp = nullptr;
+  if (step.has_value()) {
+    need(*step, torch::kInt64, "step");
+    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
+    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
+  }
+  const int* act = nullptr;
+  if (active.has_value()) {
+    need(*active, torch::kInt32, "active");
+    TORCH_CHECK(active->numel() == B && active->is_contiguous(), "active must be contiguous int32 [B]");
+    act = active->data_ptr<int>();
+  }
+  // W > 20 and V beyond the row are the wrapper's to refuse (hipErrorInvalidValue)
+  check_hip(lsd_logprobs(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V, tokens.data_ptr<int>(),
+                         nlp.data_ptr<int>(), slots.data_ptr<int>(), sp, (int)back, act, lp_tok.data_ptr<float>(),
+                         lp_top_id.data_ptr<int>(), lp_top.data_ptr<float>(), (int)lp_tok.size(1), (int)lp_tok.size(0),
+                         (int)lp_top.size(2), cur_stream()), "logprobs");
 }
 
 torch::Tensor silu_mul(torch::Tensor y) {
@@ -864,6 +908,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("counts"), py::arg("presence"), py::arg("frequency"), py::arg("segmax") = py::none());
   m.def("record_tokens", &record_tokens, py::arg("hist"), py::arg("slots"), py::arg("step"), py::arg("tokens"),
         py::arg("active") = py::none(), py::arg("back") = 0);
+  m.def("logprobs", &logprobs, py::arg("logits"), py::arg("V"), py::arg("tokens"), py::arg("nlp"), py::arg("slots"),
+        py::arg("step"), py::arg("active"), py::arg("lp_tok"), py::arg("lp_top_id"), py::arg("lp_top"),
+        py::arg("back") = 0);
   m.def("qkv_post", &qkv_post);
   // GEMV weight stream with non-temporal loads (A/B knob, LSD_GEMV_NT)
   m.def("gemv_set_nt", [](int64_t v) { lsd_gemv_set_nt((int)v); });

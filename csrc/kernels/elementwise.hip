@@ -117,9 +117,11 @@ namespace lsd {
 //   the 14-word record names their row vectors)
 //   f[8 cap, 9 cap) presence penalty  f[9 cap, 10 cap) frequency penalty (fp32 bits; only
 //   with the 16-word record, csrc/kernels/penalty.hip)
+//   f[10 cap, 11 cap) alternatives asked of the logprob pass, -1 = none (only with the
+//   17-word record, csrc/kernels/logprob.hip)
 // and this kernel scatters it into the group's row-state vectors: rows [0, n)
 // live, pad rows [n, b) idle on the scratch slot (position 0, inactive,
-// temperature 1, top-k 1, greedy, seed 0, step 0, top-p 1, min-p 0, penalties 0, gather index 0).  Stage 0
+// temperature 1, top-k 1, greedy, seed 0, step 0, top-p 1, min-p 0, penalties 0, no logprobs, gather index 0).  Stage 0
 // also gathers the rows' input tokens out of the previous token-return vector
 // in place (tin[i] = tin[src[i]], staged through LDS: a source may be a row
 // this same launch overwrites).  One workgroup: b <= 16384 (64 KB of LDS).
@@ -132,7 +134,7 @@ __global__ __launch_bounds__(1024) void apply_rows_kernel(const int* __restrict_
                                                           long long* __restrict__ seeds, long long* __restrict__ sstep,
                                                           int* tin, float* __restrict__ topp,
                                                           float* __restrict__ minp, float* __restrict__ presence,
-                                                          float* __restrict__ frequency) {
+                                                          float* __restrict__ frequency, int* __restrict__ nlp) {
   extern __shared__ int gath[];
   const int n = buf[4 * cap];
   const int* f = buf + 4 * cap + 1;
@@ -153,6 +155,7 @@ __global__ __launch_bounds__(1024) void apply_rows_kernel(const int* __restrict_
     if (minp != nullptr) minp[i] = live ? __int_as_float(f[7 * cap + i]) : 0.0f;
     if (presence != nullptr) presence[i] = live ? __int_as_float(f[8 * cap + i]) : 0.0f;
     if (frequency != nullptr) frequency[i] = live ? __int_as_float(f[9 * cap + i]) : 0.0f;
+    if (nlp != nullptr) nlp[i] = live ? f[10 * cap + i] : -1;
     if (tin != nullptr) gath[i] = tin[live ? f[5 * cap + i] : 0];
   }
   if (tin == nullptr) return;  // uniform across the workgroup
@@ -164,11 +167,12 @@ __global__ __launch_bounds__(1024) void apply_rows_kernel(const int* __restrict_
 
 // args: the host int64 record [cap, scratch, buf, slots, pos, act, temp, topk,
 // greedy, seeds, sstep, tin] (device pointers; 0 = the field is absent on this
-// stage), nargs = 12, 14 with [topp, minp] appended, or 16 with [presence,
-// frequency] after those (the buffer then carries their columns) -- the native
-// executor passes the same record it got from Python.
+// stage), nargs = 12, 14 with [topp, minp] appended, 16 with [presence,
+// frequency] after those, or 17 with [nlp] after those (the buffer then carries
+// their columns) -- the native executor passes the same record it got from
+// Python.
 extern "C" hipError_t lsd_apply_rows(const int64_t* args, int nargs, int b, hipStream_t st) {
-  if (nargs != 12 && nargs != 14 && nargs != 16) return hipErrorInvalidValue;
+  if (nargs != 12 && nargs != 14 && nargs != 16 && nargs != 17) return hipErrorInvalidValue;
   if (b <= 0) return hipSuccess;
   const int cap = (int)args[0];
   if (b > cap || b > 16384 || args[2] == 0 || args[3] == 0 || args[4] == 0 || args[5] == 0) return hipErrorInvalidValue;
@@ -181,6 +185,6 @@ extern "C" hipError_t lsd_apply_rows(const int64_t* args, int nargs, int b, hipS
                      static_cast<float*>(P(6)), static_cast<int*>(P(7)), static_cast<int*>(P(8)),
                      static_cast<long long*>(P(9)), static_cast<long long*>(P(10)), static_cast<int*>(P(11)),
                      static_cast<float*>(P(12)), static_cast<float*>(P(13)), static_cast<float*>(P(14)),
-                     static_cast<float*>(P(15)));
+                     static_cast<float*>(P(15)), static_cast<int*>(P(16)));
   return hipGetLastError();
 }

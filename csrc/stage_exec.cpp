@@ -64,7 +64,7 @@ enum : int {
   X_ROWS_SRC,    //   pinned host source of the packed row state
   X_ROWS_BYTES,  //   bytes
   X_ROWS_B,      //   bucket rows
-  X_ROWS_NARGS,  //   words of the record: 12, 14 with the top_p / min_p row vectors, 16 with the penalties (0 = 12)
+  X_ROWS_NARGS,  //   words of the record: 12, 14 with the top_p / min_p row vectors, 16 with the penalties, 17 with the logprob counts (0 = 12)
   X_FIELDS
 };
 

@@ -45,12 +45,19 @@ class LLM:
                       presence_penalty: float = 0.0, frequency_penalty: float = 0.0, **sampling) -> dict:
         """Same return contract as the reference /generate: prompt + continuation.
         top_p / min_p, the presence / frequency penalties (over the generated
-        tokens) and the other SamplingParams fields are per call."""
+        tokens) and the other SamplingParams fields are per call.  With
+        logprobs=n the dict also has "logprobs", as the /generate response."""
         ids = self.tokenizer.encode(prompt)
         sp = SamplingParams(max_new_tokens=max_new_tokens, top_p=top_p, min_p=min_p,
                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, **sampling)
         if max_new_tokens == 0:
             return {"generated": self.tokenizer.decode(ids, skip_special_tokens=True)}
+        if sp.logprobs is not None:
+            from .serving.server import logprobs_json
+
+            req = self.engine.generate_requests([ids], [sp])[0]
+            return {"generated": self.tokenizer.decode(ids + req.output, skip_special_tokens=True),
+                    "logprobs": logprobs_json(req.logprobs)}
         out = self.engine.generate_ids([ids], [sp])[0]
         return {"generated": self.tokenizer.decode(ids + out, skip_special_tokens=True)}
 

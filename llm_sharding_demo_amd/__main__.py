@@ -66,6 +66,8 @@ def main(argv=None) -> int:
                    help="subtracted once from the logit of every token generated so far ([-2, 2])")
     g.add_argument("--frequency-penalty", type=float, default=0.0,
                    help="subtracted per earlier occurrence of a generated token ([-2, 2])")
+    g.add_argument("--logprobs", type=int, default=None, metavar="N",
+                   help="also print every generated token's logprob and its N most likely alternatives")
     g.add_argument("--seed", type=int)
     args = p.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(levelname)s %(message)s")
@@ -82,7 +84,7 @@ def main(argv=None) -> int:
         out = llm.generate_text(args.prompt, args.max_new_tokens, greedy=args.greedy,
                                 temperature=args.temperature, top_k=args.top_k, seed=args.seed,
                                 top_p=args.top_p, min_p=args.min_p, presence_penalty=args.presence_penalty,
-                                frequency_penalty=args.frequency_penalty)
+                                frequency_penalty=args.frequency_penalty, logprobs=args.logprobs)
         print(out)
         llm.engine.shutdown()
         return 0

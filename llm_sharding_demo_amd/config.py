@@ -173,6 +173,9 @@ def model_config_from_hf_json(path: str) -> ModelConfig:
 # Sampling
 # ---------------------------------------------------------------------------
 
+MAX_LOGPROBS_CEILING = 20  # alternatives per token the logprob kernel's record can hold
+
+
 @dataclass
 class SamplingParams:
     """Per-request sampling.  Defaults reproduce `server.py:187-205`.
@@ -190,7 +193,21 @@ class SamplingParams:
     logit[t] -= presence_penalty + frequency_penalty * c(t), on the raw logits,
     ahead of temperature, top-k, top-p, min-p and the greedy argmax -- greedy
     requests are penalised too.  Both default to 0.0 (off) and must be finite
-    and in [-2, 2]; negative values raise the logits of repeated tokens."""
+    and in [-2, 2]; negative values raise the logits of repeated tokens.
+
+    logprobs: None (off; nothing changes for the request) or n in
+    [0, EngineConfig.max_logprobs]: every generated token, the prefill draw
+    included, comes back with its logprob and with the n most likely tokens and
+    theirs (Request.logprobs).  Logprobs are the log-softmax over the whole
+    vocabulary of the fp32 logits the sampler drew from: after the presence /
+    frequency penalties, at temperature 1, before the top-k / top-p / min-p
+    cuts -- for an unpenalised request the model's own distribution.  The
+    alternatives come most likely first, equal logits (-0.0 == +0.0) by
+    ascending token id; when the drawn token is among them its logprob is
+    bit-equal to that entry's; a -inf logit has logprob -inf; a vocabulary of
+    fewer than n tokens pads with id -1 and -inf (trimmed from
+    Request.logprobs).  Asking never changes a draw: the same seed gives the
+    same tokens with and without."""
 
     temperature: float = 0.6
     top_k: int = 40
@@ -202,10 +219,15 @@ class SamplingParams:
     min_p: float = 0.0
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    logprobs: Optional[int] = None
 
-    def validate(self) -> None:
+    def validate(self, max_logprobs: int = MAX_LOGPROBS_CEILING) -> None:
         if self.max_new_tokens < 0:
             raise ValueError("max_new_tokens must be >= 0")
+        if self.logprobs is not None:
+            n = self.logprobs
+            if isinstance(n, bool) or not isinstance(n, int) or not (0 <= n <= max_logprobs):
+                raise ValueError(f"logprobs must be None or an integer in [0, {max_logprobs}] (max_logprobs)")
         for name in ("presence_penalty", "frequency_penalty"):  # greedy requests too
             v = getattr(self, name)
             if not (isinstance(v, (int, float)) and math.isfinite(v) and -2.0 <= v <= 2.0):
@@ -306,6 +328,14 @@ class EngineConfig:
     # Serving: record per-stage busy / bubble timing on one pipeline session
     # in this many (0 = never) -- it costs a control-plane gather per session.
     metrics_every: int = 16
+    # Most alternatives a request may ask for per token (SamplingParams.logprobs);
+    # sizes the last stage's logprob records, slots x max_seq x (4 + 8 W) bytes,
+    # allocated when the first such request arrives.  At most 20.
+    max_logprobs: int = 5
+
+    def __post_init__(self):
+        if not (0 <= self.max_logprobs <= MAX_LOGPROBS_CEILING):
+            raise ValueError(f"max_logprobs must be in [0, {MAX_LOGPROBS_CEILING}]")
 
     @property
     def model(self) -> ModelConfig:
@@ -339,6 +369,7 @@ class EngineConfig:
             join_max_wait=int(_env("JOIN_MAX_WAIT", "4")),
             kv_fraction=float(_env("KV_FRACTION", "0.85")),
             metrics_every=int(_env("METRICS_EVERY", "16")),
+            max_logprobs=int(_env("MAX_LOGPROBS", "5")),
         )
         if cfg.split_points and cfg.num_stages == 1:
             cfg.num_stages = len(cfg.split_points) + 1

@@ -126,6 +126,13 @@ class ReferenceBackend(Backend):
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         ref.record_tokens(hist, slots, step, tokens, active, back)
 
+    def logprobs(self, logits, tokens, nlp, slots, step, active, rec, vocab: int, back: int = 0) -> None:
+        """Logprob records of the rows with nlp >= 0 (ops/reference.py logprobs),
+        after the sampler wrote `tokens`: into rec = (lp_tok, lp_top_id,
+        lp_top) at [slots[i], step[i] - back]."""
+        W = rec[1].shape[2]
+        ref.record_logprobs(rec, slots, step, nlp, *ref.logprobs(logits, tokens, nlp, vocab, W), active, back)
+
     def gather_rows(self, x, idx):
         return x.index_select(0, idx.long())
 

@@ -383,5 +383,10 @@ class HipBackend(Backend):
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         self.C.record_tokens(hist, slots, step, tokens, active, back)
 
+    def logprobs(self, logits, tokens, nlp, slots, step, active, rec, vocab: int, back: int = 0) -> None:
+        # logprob.hip: one workgroup per row, after the sampler; rows with
+        # nlp < 0 return at once
+        self.C.logprobs(logits, vocab, tokens, nlp, slots, step, active, rec[0], rec[1], rec[2], back)
+
     def gather_rows(self, x, idx):
         return x.index_select(0, idx.long())

@@ -171,6 +171,73 @@ def record_tokens(hist: torch.Tensor, slots: torch.Tensor, step: Optional[torch.
             hist[int(slots[i]), j] = int(tokens[i])
 
 
+def lse64(row: torch.Tensor) -> torch.Tensor:
+    """m + log(sum exp(x - m)) of one row in float64, m its maximum (-inf for
+    a row of -inf)."""
+    x = row.double()
+    m = x.max()
+    if float(m) == float("-inf"):
+        return m
+    return m + torch.log(torch.exp(x - m).sum())
+
+
+def logprobs(logits: torch.Tensor, tokens: torch.Tensor, nlp, vocab: int, W: int):
+    """Token logprobs and top-N alternatives of fp32 logit rows [B, >= vocab].
+
+    Over [0, vocab) of each row: lse = m + log(sum exp(x - m)) with m the row
+    maximum, the sum taken in float64 and lse rounded once to fp32; the
+    logprob of x is fl32(x - lse), -inf for x = -inf (-inf entries add 0 to
+    the sum).  Row r with n = min(nlp[r], W) >= 0 gets its n most likely ids
+    and their logprobs in the sampler's contract order -- logit descending by
+    numeric comparison (-0.0 == +0.0), index ascending: a stable sort -- and
+    entries [n, W), or past the vocabulary, hold id -1 and -inf.  Rows with
+    nlp < 0 did not ask: logprob -inf and a padded record.
+
+    -> (tok_lp [B] fp32, top_id [B, W] int32, top_lp [B, W] fp32), tok_lp the
+    logprob of tokens[r]: bit-equal to its entry among the alternatives.
+    """
+    B = logits.shape[0]
+    tok_lp = torch.full((B,), float("-inf"), dtype=torch.float32)
+    top_id = torch.full((B, W), -1, dtype=torch.int32)
+    top_lp = torch.full((B, W), float("-inf"), dtype=torch.float32)
+    neg = torch.tensor(float("-inf"))
+    for r in range(B):
+        n = int(nlp[r])
+        if n < 0:
+            continue
+        n = min(n, W)
+        row = logits[r, :vocab].detach().float().cpu()
+        lse = lse64(row).float()
+        lp = torch.where(row == neg, neg, row - lse)
+        t = int(tokens[r])
+        if 0 <= t < vocab:
+            tok_lp[r] = lp[t]
+        if n:
+            _, idx = torch.sort(row, descending=True, stable=True)
+            idx = idx[:n]
+            top_id[r, : idx.numel()] = idx.to(torch.int32)
+            top_lp[r, : idx.numel()] = lp[idx]
+    return tok_lp, top_id, top_lp
+
+
+def record_logprobs(rec, slots: torch.Tensor, step: Optional[torch.Tensor], nlp, tok_lp, top_id, top_lp,
+                    active: Optional[torch.Tensor] = None, back: int = 0) -> None:
+    """Store `logprobs` results of the rows with nlp >= 0 as record
+    step[i] - back (step None = 0, the prefill draw) of KV slot slots[i] in
+    rec = (lp_tok [slots, L], lp_top_id [slots, L, W], lp_top [slots, L, W]);
+    inactive rows, and records outside [0, L), are skipped."""
+    lt, li, lv = rec
+    for i in range(tok_lp.shape[0]):
+        if int(nlp[i]) < 0 or (active is not None and int(active[i]) == 0):
+            continue
+        j = int(step[i]) - back if step is not None else 0
+        s = int(slots[i])
+        if 0 <= j < lt.shape[1] and 0 <= s < lt.shape[0]:
+            lt[s, j] = tok_lp[i]
+            li[s, j] = top_id[i]
+            lv[s, j] = top_lp[i]
+
+
 def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
            greedy: torch.Tensor, uniforms: torch.Tensor, vocab: int,
            top_p: Optional[torch.Tensor] = None, min_p: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -202,7 +202,12 @@ class GroupState(racecheck.Shared):
         # penalty (last stage): only then do penalize and record_tokens run
         # around the sampler, and the decode graphs are keyed on it too
         self.pen = False
+        # any row of the current composition that asked for logprobs (last
+        # stage): only then does the logprob kernel run after the sampler, and
+        # the decode graphs are keyed on it as well
+        self.lp = False
         if w.last:
+            self.nlp = torch.full((cap,), -1, **i32)   # alternatives per row (-1 = no record)
             self.presence = torch.zeros(cap, dtype=torch.float32, device=dev)   # penalties (0 = off)
             self.frequency = torch.zeros(cap, dtype=torch.float32, device=dev)
             self.temp = torch.ones(cap, dtype=torch.float32, device=dev)
@@ -412,6 +417,14 @@ class StageWorker(racecheck.Shared):
         # sampler ran with the penalty pass around it
         self.pen_hist: Optional[torch.Tensor] = None
         self.penalty_launches = 0
+        # last stage: logprob records per KV slot, indexed like the history
+        # (_lp_rec: allocated when the first logprob request arrives) --
+        # (lp_tok [slots, L] fp32, lp_top_id [slots, L, W] int32, lp_top
+        # [slots, L, W] fp32), W = max_logprobs -- and the items whose sampler
+        # was followed by the logprob kernel
+        self.lp_rec: Optional[tuple] = None
+        self.max_logprobs = 5
+        self.logprob_launches = 0
 
     # ------------------------------------------------------------------
     def configure(self, groups: int, cap: int) -> None:
@@ -627,7 +640,8 @@ class StageWorker(racecheck.Shared):
             gs = self.groups[gp.g]
             cut = gs.cut if gp.rows is None else self._rows_cut(gp.rows)  # after this item's change
             pen = gs.pen if gp.rows is None else self._rows_pen(gp.rows)
-            key = (gp.b, gp.ctxb, io, cut, pen)
+            lp = gs.lp if gp.rows is None else self._rows_lp(gp.rows)
+            key = (gp.b, gp.ctxb, io, cut, pen, lp)
             ent = gs.graphs.get(key)
             if ent is None:
                 return False
@@ -688,12 +702,14 @@ class StageWorker(racecheck.Shared):
                     # after the readout, ahead of the graph (csrc/stage_exec.cpp)
                     slot, args = self._rows_pack(gs, gp.rows, gp.b)
                     d[14], d[15], d[16], d[17] = (args.data_ptr(), slot[0].data_ptr(),
-                                                  4 * self._rows_words(gs.cap, gs.pen), gp.b)
+                                                  4 * self._rows_words(gs.cap, gs.pen, gs.lp), gp.b)
                     d[18] = args.numel()
                     packed.append((slot, lane))
                     self.native_changes += 1
                 if gs.pen:
                     self.penalty_launches += 1
+                if gs.lp:
+                    self.logprob_launches += 1
                 rows.append(d)
             try:
                 with (self.t.issuing() if self.t is not None else contextlib.nullcontext()):
@@ -925,6 +941,8 @@ class StageWorker(racecheck.Shared):
         self._sample_rows(gs, ld, b, dec)
         if gs.pen:
             self.penalty_launches += 1
+        if gs.lp:
+            self.logprob_launches += 1
         if J:
             lf = logits[b:]
             if seg is not None:
@@ -934,7 +952,7 @@ class StageWorker(racecheck.Shared):
                                  [c.greedy for c in fc], [c.seed for c in fc], dev,
                                  [c.top_p for c in fc], [c.min_p for c in fc])
             ids = be.sample(lf, samp, V)
-            self._record_finals(fc, ids)
+            self._record_finals(fc, ids, lf)
             gs.tokret[b: b + J].copy_(ids)
         self.mixed_items += 1
 
@@ -947,6 +965,7 @@ class StageWorker(racecheck.Shared):
         n, b = gp.n, max(gp.b, gp.n)
         gs.cut = self._rows_cut(rows)
         gs.pen = self._rows_pen(rows)
+        gs.lp = self._rows_lp(rows)
         pad = b - n
         sl = [r.slot for r in rows] + [self.scratch_slot] * pad
         pos = [r.pos for r in rows] + [0] * pad
@@ -956,7 +975,7 @@ class StageWorker(racecheck.Shared):
         if dev.type == "cuda":
             if hasattr(self.stage.backend, "C"):
                 slot, args = self._rows_pack(gs, rows, b)
-                words = self._rows_words(gs.cap, gs.pen)
+                words = self._rows_words(gs.cap, gs.pen, gs.lp)
                 gs.rows_dev[:words].copy_(slot[0][:words], non_blocking=True)
                 self.stage.backend.C.apply_rows(args, b)
                 slot[1].record()
@@ -981,6 +1000,9 @@ class StageWorker(racecheck.Shared):
                                       non_blocking=True)
                 gs.frequency[:b].copy_(_h2d([r.frequency for r in rows] + [0.0] * pad, torch.float32, dev),
                                        non_blocking=True)
+            if gs.lp:
+                gs.nlp[:b].copy_(_h2d([r.logprobs for r in rows] + [-1] * pad, torch.int32, dev),
+                                 non_blocking=True)
             gs.greedy[:b].copy_(_h2d([1 if r.greedy else 0 for r in rows] + [1] * pad, torch.int32,
                                      dev), non_blocking=True)
             gs.seeds[:b].copy_(_h2d([r.seed for r in rows] + [0] * pad, torch.int64, dev),
@@ -1005,6 +1027,40 @@ class StageWorker(racecheck.Shared):
             self._hist()
         return pen
 
+    def _rows_lp(self, rows) -> bool:
+        """Whether a row of this composition asked for logprobs; the records
+        are allocated here, on the host side of the change (never inside a
+        capture)."""
+        lp = self.last and any(r.logprobs >= 0 for r in rows)
+        if lp:
+            self._lp_rec()
+        return lp
+
+    def _lp_rec(self) -> tuple:
+        """Logprob records of the last stage: (lp_tok [KV slots, max_seq] fp32,
+        lp_top_id [.., W] int32, lp_top [.., W] fp32), record j of a slot = the
+        draw with sampler counter j.  Records at or past a sequence's token
+        count are never fetched, so no initial value and no clearing."""
+        if self.lp_rec is None:
+            L, W = self.stage.max_seq, self.max_logprobs
+            slots = max(self.scratch_slot, self.compat_slot) + 1
+            dev = self.device
+            # no fill: one enqueued on this lane could land after another lane's first record
+            self.lp_rec = (torch.empty(slots, L, dtype=torch.float32, device=dev),
+                           torch.empty(slots, L, W, dtype=torch.int32, device=dev),
+                           torch.empty(slots, L, W, dtype=torch.float32, device=dev))
+        return self.lp_rec
+
+    def fetch_logprobs(self, slot: int, n: int) -> tuple:
+        """Host copies of records [0, n) of KV slot `slot`: (lp_tok [n],
+        lp_top_id [n, W], lp_top [n, W]).  For the coordinator thread, once it
+        has read the n-th token back: each record is written ahead of its
+        token's return in stream order.  Holds the capture gate shared (a
+        sibling stage thread may be capturing)."""
+        rec = self._lp_rec()
+        with self._gpu():
+            return tuple(t[slot, :n].cpu() for t in rec)
+
     def _hist(self) -> torch.Tensor:
         """Generated-token history of the last stage, [KV slots (scratch and
         compat included), max_seq] int32.  Entries at or past a row's sampler
@@ -1024,35 +1080,50 @@ class StageWorker(racecheck.Shared):
         """Decode rows of a group: draw into the token-return vector, advance
         the sampler counters and positions.  A composition with a penalised
         row runs lm_head, penalize, sample_into, record_tokens; any other the
-        sampler alone, as before."""
+        sampler alone, as before.  A composition with a logprob row then runs
+        the logprob kernel over the logits the sampler drew from."""
         be, V = self.stage.backend, self.stage.cfg.vocab_size
         if not gs.pen:
             be.sample_into(logits, gs.samp(b), V, gs.tokret[:b], meta)
-            return
-        hist = self.pen_hist
-        be.penalize(logits, hist, gs.slots[:b], gs.sstep[:b], gs.presence[:b], gs.frequency[:b], V)
-        be.sample_into(logits, gs.samp(b), V, gs.tokret[:b], meta)
-        # the sampler has advanced the counters: the draw used counter - 1
-        be.record_tokens(hist, gs.slots[:b], gs.sstep[:b], gs.tokret[:b], gs.active[:b], 1)
+        else:
+            hist = self.pen_hist
+            be.penalize(logits, hist, gs.slots[:b], gs.sstep[:b], gs.presence[:b], gs.frequency[:b], V)
+            be.sample_into(logits, gs.samp(b), V, gs.tokret[:b], meta)
+            # the sampler has advanced the counters: the draw used counter - 1
+            be.record_tokens(hist, gs.slots[:b], gs.sstep[:b], gs.tokret[:b], gs.active[:b], 1)
+        if gs.lp:
+            be.logprobs(logits, gs.tokret[:b], gs.nlp[:b], gs.slots[:b], gs.sstep[:b], gs.active[:b],
+                        self.lp_rec, V, 1)
 
-    def _record_finals(self, fc, ids: torch.Tensor) -> None:
+    def _record_finals(self, fc, ids: torch.Tensor, logits: torch.Tensor) -> None:
         """First generated token (draw 0) of the final chunks `fc` into the
         history, when one of them carries a penalty (its history is empty, so
-        the prefill draw itself needs no penalty pass)."""
-        if not any(c.presence != 0.0 or c.frequency != 0.0 for c in fc):
+        the prefill draw itself needs no penalty pass), and its logprob record
+        from `logits`, the rows `ids` were drawn from, when one of them asked.
+        Eager, outside any graph."""
+        pen = any(c.presence != 0.0 or c.frequency != 0.0 for c in fc)
+        lp = any(c.logprobs >= 0 for c in fc)
+        if not (pen or lp):
             return
         slots = _h2d([c.slot for c in fc], torch.int32, self.device)
         slots = slots.to(self.device, non_blocking=True)
-        self.stage.backend.record_tokens(self._hist(), slots, None, ids, None, 0)
-        self.penalty_launches += 1
+        if pen:
+            self.stage.backend.record_tokens(self._hist(), slots, None, ids, None, 0)
+            self.penalty_launches += 1
+        if lp:
+            nlp = _h2d([c.logprobs for c in fc], torch.int32, self.device).to(self.device, non_blocking=True)
+            self.stage.backend.logprobs(logits, ids, nlp, slots, None, None, self._lp_rec(),
+                                        self.stage.cfg.vocab_size, 0)
+            self.logprob_launches += 1
 
     _ROWS_PIN = 4  # packed row-state buffers per group: reused 4 composition changes later
 
-    def _rows_words(self, cap: int, pen: bool = False) -> int:
+    def _rows_words(self, cap: int, pen: bool = False, lp: bool = False) -> int:
         """int32 words of a group's packed row state: the last stage's also
         carries the top-p / min-p columns and, for a composition with a
-        penalised row, the presence / frequency columns."""
-        return ((14 if pen else 12) if self.last else 10) * cap + 1
+        penalised row, the presence / frequency columns; one with a logprob
+        row those and the logprob counts."""
+        return ((15 if lp else 14 if pen else 12) if self.last else 10) * cap + 1
 
     def _rows_pack(self, gs: GroupState, rows, b: int):
         """Composition change on a GPU, host side: the new rows' state packed
@@ -1061,13 +1132,14 @@ class StageWorker(racecheck.Shared):
         copy and the kernel depend on the bucket only), and the kernel's
         argument record.  -> (pinned ring slot, CPU int64 record: 14 words on
         the last stage, which owns the top-p / min-p vectors, 16 while the
-        composition has a penalised row, else 12); the
+        composition has a penalised row, 17 while it has a logprob row, else 12); the
         caller enqueues the copy + kernel (eagerly, or in exec_items) and then
         records the slot's event."""
         cap = gs.cap
         gs.cut = self._rows_cut(rows)
         gs.pen = self._rows_pen(rows)
-        words = self._rows_words(cap, True)  # buffers sized for the longest record
+        gs.lp = self._rows_lp(rows)
+        words = self._rows_words(cap, True, True)  # buffers sized for the longest record
         if len(gs.rows_pin) < self._ROWS_PIN:
             gs.rows_pin.append([torch.empty(words, dtype=torch.int32, pin_memory=True), torch.cuda.Event(), False])
         slot = gs.rows_pin[gs.rows_pin_next % len(gs.rows_pin)]
@@ -1087,11 +1159,13 @@ class StageWorker(racecheck.Shared):
                 a[f0 + 4 * cap: f0 + 4 * cap + n] = [1 if r.greedy else 0 for r in rows]
                 a[f0 + 6 * cap: f0 + 6 * cap + n] = np.asarray([r.top_p for r in rows], np.float32).view(np.int32)
                 a[f0 + 7 * cap: f0 + 7 * cap + n] = np.asarray([r.min_p for r in rows], np.float32).view(np.int32)
-                if gs.pen:
+                if gs.pen or gs.lp:
                     a[f0 + 8 * cap: f0 + 8 * cap + n] = np.asarray([r.presence for r in rows],
                                                                    np.float32).view(np.int32)
                     a[f0 + 9 * cap: f0 + 9 * cap + n] = np.asarray([r.frequency for r in rows],
                                                                    np.float32).view(np.int32)
+                if gs.lp:
+                    a[f0 + 10 * cap: f0 + 10 * cap + n] = [r.logprobs for r in rows]
                 a64 = a[: 4 * cap].view(np.int64)
                 a64[:n] = [r.seed for r in rows]
                 a64[cap: cap + n] = [r.step for r in rows]
@@ -1099,7 +1173,7 @@ class StageWorker(racecheck.Shared):
                 a[f0 + 5 * cap: f0 + 5 * cap + n] = [r.src for r in rows]
         if gs.rows_dev is None:
             gs.rows_dev = torch.empty(words, dtype=torch.int32, device=self.device)
-            gs.rows_args = torch.zeros(16 if self.last else 12, dtype=torch.int64)
+            gs.rows_args = torch.zeros(17 if self.last else 12, dtype=torch.int64)
         r = gs.rows_args.numpy()
         ptr = lambda t: t.data_ptr()  # noqa: E731
         r[0], r[1], r[2] = cap, self.scratch_slot, ptr(gs.rows_dev)
@@ -1108,9 +1182,10 @@ class StageWorker(racecheck.Shared):
             r[6], r[7], r[8], r[9], r[10] = ptr(gs.temp), ptr(gs.topk), ptr(gs.greedy), ptr(gs.seeds), ptr(gs.sstep)
             r[12], r[13] = ptr(gs.topp), ptr(gs.minp)
             r[14], r[15] = ptr(gs.presence), ptr(gs.frequency)
+            r[16] = ptr(gs.nlp)
         r[11] = ptr(gs.tin) if self.first else 0
         # the record's leading 14 words are what default traffic passes
-        return slot, (gs.rows_args[: 16 if gs.pen else 14] if self.last else gs.rows_args)
+        return slot, (gs.rows_args[: 17 if gs.lp else 16 if gs.pen else 14] if self.last else gs.rows_args)
 
     def _apply_rows_staged(self, gs: GroupState, rows, b: int, pad: int, sl, pos, act) -> None:
         """_apply_rows on a GPU: every per-row field packed into ONE int32
@@ -1135,6 +1210,8 @@ class StageWorker(racecheck.Shared):
                       np.asarray([r.step for r in rows] + [0] * pad, np.int64).view(i32)]
         if self.first:
             parts.append(np.asarray([r.src for r in rows] + [0] * pad, i32))
+        if self.last and gs.lp:  # behind everything else: the int64 fields keep their alignment
+            parts.append(np.asarray([r.logprobs for r in rows] + [-1] * pad, i32))
         arr = np.concatenate(parts)
         buf = getattr(gs, "_rows_buf", None)
         if buf is None or buf.numel() < arr.size:
@@ -1161,6 +1238,9 @@ class StageWorker(racecheck.Shared):
         if self.first:
             gathered = gs.tin.index_select(0, buf[o: o + b])
             gs.tin[:b].copy_(gathered)
+            o += b
+        if self.last and gs.lp:
+            gs.nlp[:b].copy_(buf[o: o + b])
 
     def _prefill(self, gp: GroupPlan, gs: GroupState, inp: Optional[torch.Tensor]):
         st, be, dev = self.stage, self.stage.backend, self.device
@@ -1192,7 +1272,7 @@ class StageWorker(racecheck.Shared):
                              [c.greedy for c in fc], [c.seed for c in fc], dev,
                              [c.top_p for c in fc], [c.min_p for c in fc])
         ids = be.sample(logits, samp, st.cfg.vocab_size)
-        self._record_finals(fc, ids)
+        self._record_finals(fc, ids, logits)
         return ids
 
     # Prefill chunks as hipGraphs (the non-steady items):
@@ -1309,10 +1389,12 @@ class StageWorker(racecheck.Shared):
         slot[2] = True
 
     def _decode(self, gp: GroupPlan, gs: GroupState, inp: torch.Tensor, io: bool = False) -> torch.Tensor:
-        key = (gp.b, gp.ctxb, io, gs.cut, gs.pen)
+        key = (gp.b, gp.ctxb, io, gs.cut, gs.pen, gs.lp)
         lane = self.lane_of(gp.g)
         if gs.pen:
             self.penalty_launches += 1
+        if gs.lp:
+            self.logprob_launches += 1
 
         def body():
             if io and not self.first:  # the edge receive, inside the graph

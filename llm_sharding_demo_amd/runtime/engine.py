@@ -348,6 +348,7 @@ class Engine(racecheck.Shared):
                         compat_slot=self.kv_slots + 1,
                         wire=torch.bfloat16 if self.cfg.wire_dtype == "bf16" else None)
         w.merge_prefill = w.MERGE_PREFILL and self.cfg.merge_prefill
+        w.max_logprobs = self.cfg.max_logprobs
         return w
 
     @property
@@ -367,7 +368,12 @@ class Engine(racecheck.Shared):
     # requests
     # ------------------------------------------------------------------
     def _validate(self, prompt: List[int], sp: SamplingParams) -> None:
-        sp.validate()
+        sp.validate(self.cfg.max_logprobs)
+        if sp.logprobs is not None and self.mode == "dist":
+            # the records stay on the last stage until the request finishes and
+            # are read from there directly; fetching them over the control
+            # plane from a rank process is not built
+            raise ValueError("logprobs need the last stage in the coordinator process")
         if len(prompt) == 0:
             raise ValueError("prompt must contain at least one token")
         if len(prompt) + sp.max_new_tokens > self.max_seq:
@@ -412,6 +418,35 @@ class Engine(racecheck.Shared):
         if ph is not None:
             self._phase("collect", tp)
         return out
+
+    def generate_requests(self, prompts: List[List[int]], params, microbatches: Optional[int] = None,
+                          record_timing: bool = False) -> List[Request]:
+        """generate_ids, returning the finished requests instead of their token
+        lists: `Request.output` is what generate_ids returns for the prompt and
+        `Request.logprobs` the records of a request that asked for them."""
+        if isinstance(params, SamplingParams):
+            params = [params] * len(prompts)
+        for p, sp in zip(prompts, params):
+            self._validate(p, sp)
+        if not self.healthy:
+            raise RuntimeError(f"engine unhealthy: {self.last_error}")
+        if microbatches and microbatches != self.M and self.loop_thread is None:
+            self.set_groups(microbatches)
+        reqs = self.scheduler.submit_many(prompts, params)
+        if self.loop_thread is None:
+            with self._lock:
+                self._drive(lambda: all(r.done for r in reqs), timing=record_timing)
+        for r in reqs:
+            r.wait(None if self.loop_thread is not None else 0)
+        return reqs
+
+    def fetch_logprobs(self, replica: int, slot: int, n: int) -> tuple:
+        """Logprob records [0, n) of KV slot `slot` from the replica's last
+        stage, which lives in this process (local mode; _validate refuses the
+        request otherwise): host (lp_tok [n], lp_top_id [n, W], lp_top [n, W])."""
+        if self.mode != "local" or replica != 0:
+            raise RuntimeError("logprob records: the last stage is not in this process")
+        return self.workers[-1].fetch_logprobs(slot, n)
 
     def _phase(self, name: str, t0: float) -> float:
         """LSD_HOST_PROFILE: add the host time since t0 to session phase `name`."""

@@ -47,6 +47,7 @@ class Chunk:
     min_p: float = 0.0
     presence: float = 0.0   # presence / frequency penalties over the generated tokens
     frequency: float = 0.0
+    logprobs: int = -1      # alternatives recorded with every draw's logprob (-1: no record)
 
     @property
     def qlen(self) -> int:
@@ -72,6 +73,7 @@ class Row:
     min_p: float = 0.0
     presence: float = 0.0
     frequency: float = 0.0
+    logprobs: int = -1
 
 
 @dataclass
@@ -174,6 +176,17 @@ def _float_rows(temp):
     return temp.tolist()
 
 
+def _int_cols(rows, xs, width: int):
+    """int64 columns of Chunks / Rows, [n, width]; a trailing column of the
+    logprob counts only when some entry asks (all-default traffic packs what
+    it did before the column existed)."""
+    import numpy as np
+
+    if any(x.logprobs >= 0 for x in xs):
+        return np.array([r + (x.logprobs,) for r, x in zip(rows, xs)], dtype=np.int64).reshape(-1, width + 1)
+    return np.array(rows, dtype=np.int64).reshape(-1, width)
+
+
 def _pack_group(gp: GroupPlan, ids: bool):
     import numpy as np
 
@@ -186,15 +199,13 @@ def _pack_group(gp: GroupPlan, ids: bool):
 
             tok = np.fromiter(itertools.chain.from_iterable(x.ids for x in c), dtype=np.int32,
                               count=sum(len(x.ids) for x in c))
-        ch = (np.array([(x.seq, x.slot, x.start, len(x.ids), x.final, x.top_k, x.greedy) for x in c],
-                       dtype=np.int64).reshape(-1, 7),
+        ch = (_int_cols([(x.seq, x.slot, x.start, len(x.ids), x.final, x.top_k, x.greedy) for x in c], c, 7),
               _float_cols(c),
               np.array([x.seed for x in c], dtype=np.int64), tok)
     rows = None
     if gp.rows is not None:
         r = gp.rows
-        rows = (np.array([(x.seq, x.slot, x.pos, x.top_k, x.greedy, x.seed, x.step, x.src) for x in r],
-                         dtype=np.int64).reshape(-1, 8),
+        rows = (_int_cols([(x.seq, x.slot, x.pos, x.top_k, x.greedy, x.seed, x.step, x.src) for x in r], r, 8),
                 _float_cols(r))
     return (gp.g, gp.ret, gp.n, gp.b, gp.ctxb, gp.kind, gp.fwd_rows, ch, rows)
 
@@ -207,17 +218,17 @@ def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows) -> GroupPlan:
         ints, temp, seeds, tok = ch
         tok = tok.tolist() if tok is not None else None
         out, o = [], 0
-        for (seq, slot, start, ln, final, top_k, greedy), (t, tp, mp, pp, fp), sd in zip(ints.tolist(), _float_rows(temp),
-                                                                                 seeds.tolist()):
+        for (seq, slot, start, ln, final, top_k, greedy, *lp), (t, tp, mp, pp, fp), sd in zip(
+                ints.tolist(), _float_rows(temp), seeds.tolist()):
             out.append(Chunk(seq, slot, start, tok[o: o + ln] if tok is not None else range(ln), bool(final),
-                             t, top_k, bool(greedy), sd, tp, mp, pp, fp))
+                             t, top_k, bool(greedy), sd, tp, mp, pp, fp, *lp))
             o += ln
         gp.chunks = out
     if rows is not None:
         ints, temp = rows
-        gp.rows = [Row(seq, slot, pos, t, top_k, bool(greedy), seed, step, src, tp, mp, pp, fp)
-                   for (seq, slot, pos, top_k, greedy, seed, step, src), (t, tp, mp, pp, fp) in zip(ints.tolist(),
-                                                                                            _float_rows(temp))]
+        gp.rows = [Row(seq, slot, pos, t, top_k, bool(greedy), seed, step, src, tp, mp, pp, fp, *lp)
+                   for (seq, slot, pos, top_k, greedy, seed, step, src, *lp), (t, tp, mp, pp, fp) in zip(
+                       ints.tolist(), _float_rows(temp))]
     return gp
 
 

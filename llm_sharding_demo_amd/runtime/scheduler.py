@@ -53,6 +53,16 @@ class RequestTimeout(RuntimeError):
 _FINISH = threading.Lock()  # orders Request.finish against a waiter creating its event
 
 
+@dataclass
+class Logprobs:
+    """Records of a request that asked for logprobs (SamplingParams.logprobs = n),
+    one entry per generated token: the token, its logprob, and the n most likely
+    tokens at that draw as (id, logprob), most likely first."""
+    tokens: List[int]
+    token_logprobs: List[float]
+    top_logprobs: List[List[tuple]]
+
+
 @dataclass(eq=False)
 class Request:
     """One generation request.  Light on purpose: a 4096-sequence session
@@ -68,6 +78,7 @@ class Request:
     t_done: float = 0.0
     output: Optional[List[int]] = None
     error: Optional[BaseException] = None
+    logprobs: Optional[Logprobs] = None  # set before finish() when params.logprobs is not None
     _flag: bool = False
     _ev: Optional[threading.Event] = None
 
@@ -519,7 +530,10 @@ class _Meta:
     seed: int
     samp: tuple = ()    # (temperature, top_k, greedy, seed): the chunk / row sampling fields
     # (top_p, min_p, presence, frequency): the trailing chunk / row fields
-    cut: tuple = (1.0, 0.0, 0.0, 0.0)
+    # then the logprob count (-1: none)
+    cut: tuple = (1.0, 0.0, 0.0, 0.0, -1)
+    rep: int = 0        # replica and KV slot, from the request's first prefill chunk
+    slot: int = -1
     done: bool = False  # finished by this scheduler (plain flag: the readout loop's hot path)
 
 
@@ -611,7 +625,8 @@ class Scheduler(racecheck.Shared):
             p = req.params
             seed = p.seed if p.seed is not None else rng.getrandbits(62)
             meta[i] = _Meta(req, seed, (p.temperature, p.top_k, p.greedy, seed),
-                            (p.top_p, p.min_p, float(p.presence_penalty), float(p.frequency_penalty)))
+                            (p.top_p, p.min_p, float(p.presence_penalty), float(p.frequency_penalty),
+                             -1 if p.logprobs is None else int(p.logprobs)))
             lens.append(len(req.prompt_ids))
             wants.append(p.max_new_tokens)
             stops.append(bool(p.stop_at_eos))
@@ -637,7 +652,7 @@ class Scheduler(racecheck.Shared):
             now = time.monotonic()
             for sid in admitted:
                 self.meta[sid].req.t_start = now
-        plans = [StepPlan(step=s, groups=[self._group(go) for go in gos], replica=rep,
+        plans = [StepPlan(step=s, groups=[self._group(go, rep) for go in gos], replica=rep,
                           timing=self.timing) for rep, gos in enumerate(per_rep)]
         c = self.core
         self.stats.update(steps=self.stats["steps"] + 1, joins=c.joins, leaves=c.leaves,
@@ -646,10 +661,13 @@ class Scheduler(racecheck.Shared):
             self.step_log.append((s, any(gp.chunks for p in plans for gp in p.groups)))
         return plans
 
-    def _group(self, go) -> GroupPlan:
+    def _group(self, go, rep: int = 0) -> GroupPlan:
         g, ret, n, b, ctxb, changed, chunks, rows = go
         gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb)
         meta = self.meta
+        for sid, slot, start, _, _ in chunks:
+            if start == 0 and meta[sid].cut[4] >= 0:  # where _finish fetches the logprob records
+                meta[sid].rep, meta[sid].slot = rep, slot
         gp.chunks = [Chunk(sid, slot, start, m.req.prompt_ids[start:start + ln], final, *m.samp, *m.cut)
                      for sid, slot, start, ln, final in chunks for m in (meta[sid],)]
         if changed:
@@ -739,7 +757,7 @@ class Scheduler(racecheck.Shared):
                 m = self.meta.pop(sid, None)
                 if m is not None and flags & EV_FINISH and not m.done:
                     m.done = True
-                    m.req.finish(done.get(sid, []))
+                    self._finish(m, done.get(sid, []))
                 continue
             m = get(sid)
             if m is None or m.done:
@@ -748,7 +766,25 @@ class Scheduler(racecheck.Shared):
                 m.req.t_first = now
             if flags & EV_FINISH:
                 m.done = True
-                m.req.finish(done[sid])
+                self._finish(m, done[sid])
+
+    def _finish(self, m: _Meta, toks: List[int]) -> None:
+        """Finish a request with its tokens; one that asked for logprobs gets
+        records [0, len(toks)) of its KV slot from the last stage first.  The
+        slot is still the request's: it goes back to the pool after this
+        readout at the earliest, and draws issued past the last token write
+        records at or past len(toks) only."""
+        n = m.cut[4]
+        if n >= 0:
+            try:
+                lt, li, lv = self.eng.fetch_logprobs(m.rep, m.slot, len(toks))
+            except BaseException as e:  # noqa: BLE001 - the request fails, the engine goes on
+                m.req.finish(error=e)
+                return
+            ids, vals = li[:, :n].tolist(), lv[:, :n].tolist()
+            m.req.logprobs = Logprobs(list(toks), lt.tolist(),
+                                      [[(i, v) for i, v in zip(a, b) if i >= 0] for a, b in zip(ids, vals)])
+        m.req.finish(toks)
 
     # -- failure -----------------------------------------------------------------
     def fail_all(self, err: BaseException) -> None:

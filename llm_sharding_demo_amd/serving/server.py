@@ -15,8 +15,9 @@ Roles (env SHARD_ROLE, `server.py:21`):
   b            blocks[SPLIT_AT:] + ln_f + lm_head                 -> /forward_b
   all          one process answers every endpoint (debug)
 Additions: optional sampling fields on /generate (temperature, top_k, top_p,
-min_p, presence_penalty, frequency_penalty, greedy, seed, stop_at_eos; defaults =
-reference sampler), 422 on empty/over-long
+min_p, presence_penalty, frequency_penalty, logprobs, greedy, seed, stop_at_eos;
+defaults = reference sampler; with logprobs the response gains a "logprobs" object
+beside "generated"), 422 on empty/over-long
 prompts (instead of the reference's 500, quirk Q9), GET /health, GET /metrics
 (Prometheus text).  Concurrent /generate calls are batched at decode-step
 granularity by the engine's continuous-batching scheduler
@@ -62,6 +63,18 @@ class GenerateReq(BaseModel):
     min_p: float = 0.0   # keep tokens >= min_p x the most likely one (0 = off)
     presence_penalty: float = 0.0   # off every generated token's logit, once (in [-2, 2])
     frequency_penalty: float = 0.0  # off it again per occurrence so far (in [-2, 2])
+    # alternatives returned with every generated token's logprob (None = no "logprobs" in the response)
+    logprobs: Optional[int] = None
+
+
+def logprobs_json(lp) -> dict:
+    """The "logprobs" object of a /generate response from a request's records
+    (runtime/scheduler.py Logprobs); non-finite values go out as null."""
+    import math
+
+    num = lambda v: v if math.isfinite(v) else None  # noqa: E731
+    return {"tokens": list(lp.tokens), "token_logprobs": [num(v) for v in lp.token_logprobs],
+            "top_logprobs": [[{"id": i, "logprob": num(v)} for i, v in alts] for alts in lp.top_logprobs]}
 
 
 class ShardRunner:
@@ -166,26 +179,33 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         sp = SamplingParams(temperature=req.temperature, top_k=req.top_k, greedy=req.greedy,
                             seed=req.seed, max_new_tokens=req.max_new_tokens,
                             stop_at_eos=req.stop_at_eos, top_p=req.top_p, min_p=req.min_p,
-                            presence_penalty=req.presence_penalty, frequency_penalty=req.frequency_penalty)
-        if req.max_new_tokens == 0:
+                            presence_penalty=req.presence_penalty, frequency_penalty=req.frequency_penalty,
+                            logprobs=req.logprobs)
+        if req.max_new_tokens == 0 and req.logprobs is None:
             return {"generated": tok.decode(ids, skip_special_tokens=True)}
         if not ids:
             raise HTTPException(422, "prompt must encode to at least one token")
         t0 = time.perf_counter()
         from ..runtime.scheduler import RequestTimeout
 
+        lp = None
         try:
-            sp.validate()
-            if engine is not None:
+            sp.validate(cfg.max_logprobs)
+            if req.max_new_tokens == 0:
+                from ..runtime.scheduler import Logprobs
+
+                out, lp = [], Logprobs([], [], [])
+            elif engine is not None:
                 if len(ids) + sp.max_new_tokens > engine.max_seq:
                     raise ValueError(f"prompt ({len(ids)}) + max_new_tokens ({sp.max_new_tokens}) "
                                      f"exceeds the context limit {engine.max_seq}")
                 req_ = engine.submit(ids, sp)
                 out = req_.wait(timeout=cfg.request_timeout_s)
+                lp = req_.logprobs
                 metrics.observe_request(len(out), time.perf_counter() - t0,
                                         ttft_s=(req_.t_first - req_.t_submit) if req_.t_first else None)
             else:
-                out = http_generate(cfg, ids, sp)
+                out, lp = http_generate(cfg, ids, sp, records=True)
                 metrics.observe_request(len(out), time.perf_counter() - t0)
         except ValueError as e:
             raise HTTPException(422, str(e))
@@ -195,7 +215,10 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
             if engine is not None and not engine.healthy:
                 raise HTTPException(503, f"engine unhealthy: {engine.last_error}")
             raise
-        return {"generated": tok.decode(ids + out, skip_special_tokens=True)}
+        body = {"generated": tok.decode(ids + out, skip_special_tokens=True)}
+        if lp is not None:
+            body["logprobs"] = logprobs_json(lp)
+        return body
 
     @app.get("/health")
     def health():
@@ -241,12 +264,14 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
     return app
 
 
-def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams) -> List[int]:
+def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records: bool = False):
     """Reference-style coordinator loop over remote shards (`server.py:169-206`):
     full-sequence recompute on every step, hidden states relayed through here.
     Kept for deployments where the shards are separate hosts without xGMI.
     This relay keeps the reference's sampler: presence_penalty and
-    frequency_penalty are ignored here."""
+    frequency_penalty are ignored here.  records=True: -> (tokens, the logprob
+    records of a request that asked for them or None), computed on the host
+    from the logits this loop already holds (ops/reference.py logprobs)."""
     import requests
 
     from ..ops import reference as ref
@@ -255,6 +280,11 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams) -> List
     seed = sp.seed if sp.seed is not None else int.from_bytes(__import__("os").urandom(7), "little")
     vocab = cfg.model.vocab_size
     out: List[int] = []
+    lp = None
+    if sp.logprobs is not None:
+        from ..runtime.scheduler import Logprobs
+
+        lp = Logprobs(out, [], [])
     seq = list(ids)
     url_a = f"http://{cfg.shard_a_service}:{cfg.shard_port}/forward"
     url_b = f"http://{cfg.shard_b_service}:{cfg.shard_port}/forward_b"
@@ -271,4 +301,8 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams) -> List
                              torch.tensor([sp.top_p]), torch.tensor([sp.min_p]))[0])
         seq.append(nxt)
         out.append(nxt)
-    return out
+        if lp is not None:
+            t, ti, tv = ref.logprobs(logits, torch.tensor([nxt]), [sp.logprobs], vocab, sp.logprobs)
+            lp.token_logprobs.append(float(t[0]))
+            lp.top_logprobs.append([(i, v) for i, v in zip(ti[0].tolist(), tv[0].tolist()) if i >= 0])
+    return (out, lp) if records else out
