@@ -43,7 +43,8 @@ import torch
 
 from ..models.stage import StageModel
 from ..runtime.batch import BatchMeta, MixedMeta, SamplingState
-from ..runtime.plan import GroupPlan, StepPlan
+from ..runtime.plan import (NO_FEATURES, ROW_FIELDS, GroupPlan, StepPlan, device_fields, pack_rows, packed_size,
+                            row_features)
 from ..utils.tracing import trace_range
 from ..utils import racecheck
 from .comm import Handle, SendHandle, Transport
@@ -167,10 +168,10 @@ class SamplingView:
     """Sampler parameters of a decode bucket: views of the group's persistent
     per-row tensors (graph-capturable); pad rows never advance."""
 
-    def __init__(self, temperature, top_k, greedy, seeds, step, active, top_p=None, min_p=None):
+    def __init__(self, active, temperature, top_k, greedy, seed, step, top_p=None, min_p=None):
         self.temperature, self.top_k, self.greedy = temperature, top_k, greedy
         self.top_p, self.min_p = top_p, min_p
-        self.seeds, self.step, self.active = seeds, step, active
+        self.seeds, self.step, self.active = seed, step, active
         self.num_rows = temperature.shape[0]
 
     def uniforms(self) -> torch.Tensor:
@@ -194,29 +195,15 @@ class GroupState(racecheck.Shared):
         self.pos = torch.zeros(cap, **i32)
         self.active = torch.zeros(cap, **i32)
         self.cu = torch.arange(cap + 1, **i32)
-        # any row of the current composition with a top-p / min-p cut (last
-        # stage): the sampler gets the two vectors only then, and the decode
-        # graphs are keyed on it -- all-default traffic runs the sampler without them
-        self.cut = False
-        # any row of the current composition with a presence / frequency
-        # penalty (last stage): only then do penalize and record_tokens run
-        # around the sampler, and the decode graphs are keyed on it too
-        self.pen = False
-        # any row of the current composition that asked for logprobs (last
-        # stage): only then does the logprob kernel run after the sampler, and
-        # the decode graphs are keyed on it as well
-        self.lp = False
+        # features of the current composition (last stage; runtime/plan.py
+        # row_features), each part of the decode graphs' key: a row with a top-p /
+        # min-p cut (only then does the sampler get the two vectors), with a
+        # penalty (penalize and record_tokens run around the sampler), one that
+        # asked for logprobs (the logprob kernel runs after the sampler)
+        self.cut = self.pen = self.lp = False
         if w.last:
-            self.nlp = torch.full((cap,), -1, **i32)   # alternatives per row (-1 = no record)
-            self.presence = torch.zeros(cap, dtype=torch.float32, device=dev)   # penalties (0 = off)
-            self.frequency = torch.zeros(cap, dtype=torch.float32, device=dev)
-            self.temp = torch.ones(cap, dtype=torch.float32, device=dev)
-            self.topk = torch.ones(cap, **i32)
-            self.topp = torch.ones(cap, dtype=torch.float32, device=dev)   # nucleus cut (1 = off)
-            self.minp = torch.zeros(cap, dtype=torch.float32, device=dev)  # min-p cut (0 = off)
-            self.greedy = torch.ones(cap, **i32)
-            self.seeds = torch.zeros(cap, dtype=torch.int64, device=dev)
-            self.sstep = torch.zeros(cap, dtype=torch.int64, device=dev)
+            for f in ROW_FIELDS:  # the sampler's row vectors, idle: temp, topk, greedy, seeds, sstep, ...
+                setattr(self, f.vec, torch.full((cap,), f.idle, dtype=getattr(torch, f.dtype), device=dev))
             self.tokret = torch.zeros(cap, **i32)  # [decode rows | final prefill chunks]
         if w.first:
             # decode input ids; with P > 1 also the token-return receive buffer
@@ -291,9 +278,25 @@ class GroupState(racecheck.Shared):
         return m
 
     def samp(self, b: int) -> SamplingView:
-        tp, mp = (self.topp[:b], self.minp[:b]) if self.cut else (None, None)
-        return SamplingView(self.temp[:b], self.topk[:b], self.greedy[:b], self.seeds[:b],
-                            self.sstep[:b], self.active[:b], tp, mp)
+        return SamplingView(self.active[:b], **{f.name: getattr(self, f.vec)[:b] for f in ROW_FIELDS
+                                                if f.gate == "last" or (f.gate == "cut" and self.cut)})
+
+    def rows_record(self, w: "StageWorker") -> torch.Tensor:
+        """apply_rows' argument record (CPU int64, elementwise.hip lsd_apply_rows)
+        and the device buffer it names, both for the longest composition: a
+        composition passes the leading plan.packed_size words."""
+        fields = device_fields(w.last, (True, True, True))
+        if self.rows_args is None:
+            words, nargs = packed_size(self.cap, fields)
+            self.rows_dev = torch.empty(words, dtype=torch.int32, device=w.device)
+            self.rows_args = torch.zeros(nargs, dtype=torch.int64)
+        r = self.rows_args.numpy()
+        r[0], r[1], r[2] = self.cap, w.scratch_slot, self.rows_dev.data_ptr()
+        r[3], r[4], r[5] = self.slots.data_ptr(), self.pos.data_ptr(), self.active.data_ptr()
+        for f in fields:
+            r[f.word] = getattr(self, f.vec).data_ptr()
+        r[11] = self.tin.data_ptr() if w.first else 0
+        return self.rows_args
 
 
 class StepStats:
@@ -638,10 +641,7 @@ class StageWorker(racecheck.Shared):
             if self.P > 1 and not io:
                 return False
             gs = self.groups[gp.g]
-            cut = gs.cut if gp.rows is None else self._rows_cut(gp.rows)  # after this item's change
-            pen = gs.pen if gp.rows is None else self._rows_pen(gp.rows)
-            lp = gs.lp if gp.rows is None else self._rows_lp(gp.rows)
-            key = (gp.b, gp.ctxb, io, cut, pen, lp)
+            key = (gp.b, gp.ctxb, io, *self._features(gp, gs))  # after this item's change
             ent = gs.graphs.get(key)
             if ent is None:
                 return False
@@ -700,9 +700,9 @@ class StageWorker(racecheck.Shared):
                 if gp.rows is not None:
                     # composition change: packed row state copied and applied
                     # after the readout, ahead of the graph (csrc/stage_exec.cpp)
-                    slot, args = self._rows_pack(gs, gp.rows, gp.b)
-                    d[14], d[15], d[16], d[17] = (args.data_ptr(), slot[0].data_ptr(),
-                                                  4 * self._rows_words(gs.cap, gs.pen, gs.lp), gp.b)
+                    self._set_features(gs, self._features(gp, gs))
+                    slot, words, args = self._rows_pack(gs, gp)
+                    d[14], d[15], d[16], d[17] = args.data_ptr(), slot[0].data_ptr(), 4 * words, gp.b
                     d[18] = args.numel()
                     packed.append((slot, lane))
                     self.native_changes += 1
@@ -948,93 +948,80 @@ class StageWorker(racecheck.Shared):
             if seg is not None:
                 lf._lsd_segmax = seg[b:]
             fc = [ch[i] for i in finals]
-            samp = SamplingState([c.temperature for c in fc], [c.top_k for c in fc],
-                                 [c.greedy for c in fc], [c.seed for c in fc], dev,
-                                 [c.top_p for c in fc], [c.min_p for c in fc])
-            ids = be.sample(lf, samp, V)
+            ids = be.sample(lf, SamplingState.of(fc, dev), V)
             self._record_finals(fc, ids, lf)
             gs.tokret[b: b + J].copy_(ids)
         self.mixed_items += 1
+
+    def _features(self, gp: GroupPlan, gs: GroupState) -> tuple:
+        """(cut, pen, lp) of the group once this item ran: the current ones, or
+        those of the item's new composition -- one pass over its rows, kept
+        with the plan item, so whichever path runs it reads the same triple."""
+        if gp.rows is None:
+            return gs.cut, gs.pen, gs.lp
+        if not self.last:
+            return NO_FEATURES
+        if gp.feats is None:
+            gp.feats = row_features(gp.rows)
+        return gp.feats
+
+    def _set_features(self, gs: GroupState, feats: tuple) -> None:
+        """A composition change is being applied: the group's features from
+        now on, and what they need -- the token history, the logprob records --
+        allocated here, on the host side of the change (never inside a capture)."""
+        gs.cut, gs.pen, gs.lp = feats
+        if gs.pen:
+            self._hist()
+        if gs.lp:
+            self._lp_rec()
 
     def _apply_rows(self, gp: GroupPlan, gs: GroupState) -> None:
         """New composition: rows [0, n) from the plan, pad rows [n, b) idle on
         the scratch slot.  Stage 0 also gathers the rows' input token ids out
         of the token-return vector (kept rows move, joined rows take their
         prefill sample)."""
-        dev, rows = self.device, gp.rows
-        n, b = gp.n, max(gp.b, gp.n)
-        gs.cut = self._rows_cut(rows)
-        gs.pen = self._rows_pen(rows)
-        gs.lp = self._rows_lp(rows)
-        pad = b - n
-        sl = [r.slot for r in rows] + [self.scratch_slot] * pad
-        pos = [r.pos for r in rows] + [0] * pad
-        act = [1] * n + [0] * pad
+        b = max(gp.b, gp.n)
+        self._set_features(gs, self._features(gp, gs))
         if b == 0:
             return
-        if dev.type == "cuda":
-            if hasattr(self.stage.backend, "C"):
-                slot, args = self._rows_pack(gs, rows, b)
-                words = self._rows_words(gs.cap, gs.pen, gs.lp)
-                gs.rows_dev[:words].copy_(slot[0][:words], non_blocking=True)
-                self.stage.backend.C.apply_rows(args, b)
-                slot[1].record()
-                slot[2] = True
-                return
-            self._apply_rows_staged(gs, rows, b, pad, sl, pos, act)
+        if self.device.type == "cuda" and hasattr(self.stage.backend, "C"):
+            slot, words, args = self._rows_pack(gs, gp)
+            gs.rows_dev[:words].copy_(slot[0][:words], non_blocking=True)
+            self.stage.backend.C.apply_rows(args, b)
+            slot[1].record()
+            slot[2] = True
             return
-        gs.slots[:b].copy_(_h2d(sl, torch.int32, dev), non_blocking=True)
-        gs.pos[:b].copy_(_h2d(pos, torch.int32, dev), non_blocking=True)
-        gs.active[:b].copy_(_h2d(act, torch.int32, dev), non_blocking=True)
-        if self.last:
-            gs.temp[:b].copy_(_h2d([r.temperature for r in rows] + [1.0] * pad, torch.float32, dev),
-                              non_blocking=True)
-            gs.topk[:b].copy_(_h2d([r.top_k for r in rows] + [1] * pad, torch.int32, dev),
-                              non_blocking=True)
-            gs.topp[:b].copy_(_h2d([r.top_p for r in rows] + [1.0] * pad, torch.float32, dev),
-                              non_blocking=True)
-            gs.minp[:b].copy_(_h2d([r.min_p for r in rows] + [0.0] * pad, torch.float32, dev),
-                              non_blocking=True)
-            if gs.pen:
-                gs.presence[:b].copy_(_h2d([r.presence for r in rows] + [0.0] * pad, torch.float32, dev),
-                                      non_blocking=True)
-                gs.frequency[:b].copy_(_h2d([r.frequency for r in rows] + [0.0] * pad, torch.float32, dev),
-                                       non_blocking=True)
-            if gs.lp:
-                gs.nlp[:b].copy_(_h2d([r.logprobs for r in rows] + [-1] * pad, torch.int32, dev),
-                                 non_blocking=True)
-            gs.greedy[:b].copy_(_h2d([1 if r.greedy else 0 for r in rows] + [1] * pad, torch.int32,
-                                     dev), non_blocking=True)
-            gs.seeds[:b].copy_(_h2d([r.seed for r in rows] + [0] * pad, torch.int64, dev),
-                               non_blocking=True)
-            gs.sstep[:b].copy_(_h2d([r.step for r in rows] + [0] * pad, torch.int64, dev),
-                               non_blocking=True)
-        if self.first:
-            src = _h2d([r.src for r in rows] + [0] * pad, torch.int64, dev)
-            gathered = gs.tin.index_select(0, src.to(dev, non_blocking=True))
-            gs.tin[:b].copy_(gathered)
+        self._apply_rows_torch(gs, gp.rows, b)
 
-    def _rows_cut(self, rows) -> bool:
-        """Whether the sampler of this composition needs the top-p / min-p vectors."""
-        return self.last and any(r.top_p < 1.0 or r.min_p > 0.0 for r in rows)
-
-    def _rows_pen(self, rows) -> bool:
-        """Whether this composition has a row with a presence / frequency
-        penalty; the history is allocated here, on the host side of the change
-        (never inside a capture)."""
-        pen = self.last and any(r.presence != 0.0 or r.frequency != 0.0 for r in rows)
-        if pen:
-            self._hist()
-        return pen
-
-    def _rows_lp(self, rows) -> bool:
-        """Whether a row of this composition asked for logprobs; the records
-        are allocated here, on the host side of the change (never inside a
-        capture)."""
-        lp = self.last and any(r.logprobs >= 0 for r in rows)
-        if lp:
-            self._lp_rec()
-        return lp
+    def _apply_rows_torch(self, gs: GroupState, rows, b: int) -> None:
+        """_apply_rows without the kernel (CPU, or the torch backend on a GPU):
+        the composition's plan.device_fields, pad rows idle, packed into ONE
+        int32 array (the int64 fields first, floats as their bits) that reaches
+        the device in one copy -- on a GPU through the group's pinned staging
+        ring (profiles/r5_profile_issue.log) -- and is copied into the vectors."""
+        n, pad = len(rows), b - len(rows)
+        fields = sorted(device_fields(self.last, (gs.cut, gs.pen, gs.lp)), key=lambda f: f.dtype != "int64")
+        cols = [(getattr(gs, f.vec), f.dtype, [getattr(r, f.name) for r in rows], f.idle) for f in fields]
+        cols += [(gs.slots, "int32", [r.slot for r in rows], self.scratch_slot),
+                 (gs.pos, "int32", [r.pos for r in rows], 0), (gs.active, "int32", [1] * n, 0)]
+        if self.first:  # no vector of its own: the index of the token gather below
+            cols.append((None, "int32", [r.src for r in rows], 0))
+        arr = np.concatenate([np.asarray(v + [idle] * pad, dt).view(np.int32) for _, dt, v, idle in cols])
+        if self.device.type == "cuda":
+            buf = getattr(gs, "_rows_buf", None)
+            if buf is None or buf.numel() < arr.size:
+                buf = gs._rows_buf = torch.empty(2 * arr.size, dtype=torch.int32, device=self.device)
+            self._stage_h2d(gs, arr, buf[: arr.size])
+        else:
+            buf = torch.from_numpy(arr)
+        o = 0
+        for vec, dt, _, _ in cols:
+            part = buf[o: o + b * (2 if dt == "int64" else 1)]
+            o += part.numel()
+            if vec is None:
+                gs.tin[:b].copy_(gs.tin.index_select(0, part))
+            else:
+                vec[:b].copy_(part.view(vec.dtype))
 
     def _lp_rec(self) -> tuple:
         """Logprob records of the last stage: (lp_tok [KV slots, max_seq] fp32,
@@ -1101,8 +1088,7 @@ class StageWorker(racecheck.Shared):
         the prefill draw itself needs no penalty pass), and its logprob record
         from `logits`, the rows `ids` were drawn from, when one of them asked.
         Eager, outside any graph."""
-        pen = any(c.presence != 0.0 or c.frequency != 0.0 for c in fc)
-        lp = any(c.logprobs >= 0 for c in fc)
+        _, pen, lp = row_features(fc)
         if not (pen or lp):
             return
         slots = _h2d([c.slot for c in fc], torch.int32, self.device)
@@ -1118,129 +1104,24 @@ class StageWorker(racecheck.Shared):
 
     _ROWS_PIN = 4  # packed row-state buffers per group: reused 4 composition changes later
 
-    def _rows_words(self, cap: int, pen: bool = False, lp: bool = False) -> int:
-        """int32 words of a group's packed row state: the last stage's also
-        carries the top-p / min-p columns and, for a composition with a
-        penalised row, the presence / frequency columns; one with a logprob
-        row those and the logprob counts."""
-        return ((15 if lp else 14 if pen else 12) if self.last else 10) * cap + 1
-
-    def _rows_pack(self, gs: GroupState, rows, b: int):
+    def _rows_pack(self, gs: GroupState, gp: GroupPlan):
         """Composition change on a GPU, host side: the new rows' state packed
-        into one pinned int32 buffer in the layout of elementwise.hip
-        apply_rows_kernel (fixed offsets by the group capacity, so the device
-        copy and the kernel depend on the bucket only), and the kernel's
-        argument record.  -> (pinned ring slot, CPU int64 record: 14 words on
-        the last stage, which owns the top-p / min-p vectors, 16 while the
-        composition has a penalised row, 17 while it has a logprob row, else 12); the
-        caller enqueues the copy + kernel (eagerly, or in exec_items) and then
-        records the slot's event."""
-        cap = gs.cap
-        gs.cut = self._rows_cut(rows)
-        gs.pen = self._rows_pen(rows)
-        gs.lp = self._rows_lp(rows)
-        words = self._rows_words(cap, True, True)  # buffers sized for the longest record
+        into a pinned buffer of the group's ring (plan.pack_rows: the layout
+        above apply_rows_kernel in elementwise.hip, fixed offsets by the group
+        capacity, so the device copy and the kernel depend on the bucket only),
+        and the kernel's argument record.  -> (ring slot, int32 words to copy,
+        CPU int64 record); the caller enqueues the copy + kernel (eagerly, or
+        in exec_items) and then records the slot's event."""
+        record = gs.rows_record(self)
         if len(gs.rows_pin) < self._ROWS_PIN:
-            gs.rows_pin.append([torch.empty(words, dtype=torch.int32, pin_memory=True), torch.cuda.Event(), False])
+            gs.rows_pin.append([torch.empty(gs.rows_dev.numel(), dtype=torch.int32, pin_memory=True),
+                                torch.cuda.Event(), False])
         slot = gs.rows_pin[gs.rows_pin_next % len(gs.rows_pin)]
         gs.rows_pin_next += 1
         if slot[2]:
             slot[1].synchronize()  # its previous copy has long landed
-        a = slot[0].numpy()
-        n = len(rows)
-        a[4 * cap] = n
-        if n:
-            f0 = 4 * cap + 1
-            a[f0: f0 + n] = [r.slot for r in rows]
-            a[f0 + cap: f0 + cap + n] = [r.pos for r in rows]
-            if self.last:
-                a[f0 + 2 * cap: f0 + 2 * cap + n] = np.asarray([r.temperature for r in rows], np.float32).view(np.int32)
-                a[f0 + 3 * cap: f0 + 3 * cap + n] = [r.top_k for r in rows]
-                a[f0 + 4 * cap: f0 + 4 * cap + n] = [1 if r.greedy else 0 for r in rows]
-                a[f0 + 6 * cap: f0 + 6 * cap + n] = np.asarray([r.top_p for r in rows], np.float32).view(np.int32)
-                a[f0 + 7 * cap: f0 + 7 * cap + n] = np.asarray([r.min_p for r in rows], np.float32).view(np.int32)
-                if gs.pen or gs.lp:
-                    a[f0 + 8 * cap: f0 + 8 * cap + n] = np.asarray([r.presence for r in rows],
-                                                                   np.float32).view(np.int32)
-                    a[f0 + 9 * cap: f0 + 9 * cap + n] = np.asarray([r.frequency for r in rows],
-                                                                   np.float32).view(np.int32)
-                if gs.lp:
-                    a[f0 + 10 * cap: f0 + 10 * cap + n] = [r.logprobs for r in rows]
-                a64 = a[: 4 * cap].view(np.int64)
-                a64[:n] = [r.seed for r in rows]
-                a64[cap: cap + n] = [r.step for r in rows]
-            if self.first:
-                a[f0 + 5 * cap: f0 + 5 * cap + n] = [r.src for r in rows]
-        if gs.rows_dev is None:
-            gs.rows_dev = torch.empty(words, dtype=torch.int32, device=self.device)
-            gs.rows_args = torch.zeros(17 if self.last else 12, dtype=torch.int64)
-        r = gs.rows_args.numpy()
-        ptr = lambda t: t.data_ptr()  # noqa: E731
-        r[0], r[1], r[2] = cap, self.scratch_slot, ptr(gs.rows_dev)
-        r[3], r[4], r[5] = ptr(gs.slots), ptr(gs.pos), ptr(gs.active)
-        if self.last:
-            r[6], r[7], r[8], r[9], r[10] = ptr(gs.temp), ptr(gs.topk), ptr(gs.greedy), ptr(gs.seeds), ptr(gs.sstep)
-            r[12], r[13] = ptr(gs.topp), ptr(gs.minp)
-            r[14], r[15] = ptr(gs.presence), ptr(gs.frequency)
-            r[16] = ptr(gs.nlp)
-        r[11] = ptr(gs.tin) if self.first else 0
-        # the record's leading 14 words are what default traffic passes
-        return slot, (gs.rows_args[: 17 if gs.lp else 16 if gs.pen else 14] if self.last else gs.rows_args)
-
-    def _apply_rows_staged(self, gs: GroupState, rows, b: int, pad: int, sl, pos, act) -> None:
-        """_apply_rows on a GPU: every per-row field packed into ONE int32
-        buffer (float32 temperatures as their bits, int64 seeds / steps as
-        int32 pairs at an even offset) uploaded through the group's pinned
-        staging ring, then device copies into the row state -- instead of one
-        pinned host tensor per field (profiles/r5_profile_issue.log).  The
-        int64 fields start at int32 offset 8 b, so their views are aligned."""
-        i32 = np.int32
-        parts = [np.asarray(sl, i32), np.asarray(pos, i32), np.asarray(act, i32)]
-        if self.last:
-            parts += [np.asarray([r.temperature for r in rows] + [1.0] * pad, np.float32).view(i32),
-                      np.asarray([r.top_k for r in rows] + [1] * pad, i32),
-                      np.asarray([1 if r.greedy else 0 for r in rows] + [1] * pad, i32),
-                      np.asarray([r.top_p for r in rows] + [1.0] * pad, np.float32).view(i32),
-                      np.asarray([r.min_p for r in rows] + [0.0] * pad, np.float32).view(i32)]
-            if gs.pen:  # two more columns: the int64 fields stay 8-byte aligned
-                parts += [np.asarray([r.presence for r in rows] + [0.0] * pad, np.float32).view(i32),
-                          np.asarray([r.frequency for r in rows] + [0.0] * pad, np.float32).view(i32)]
-            # the int64 fields start at int32 offset 8 b: 8-byte aligned
-            parts += [np.asarray([r.seed for r in rows] + [0] * pad, np.int64).view(i32),
-                      np.asarray([r.step for r in rows] + [0] * pad, np.int64).view(i32)]
-        if self.first:
-            parts.append(np.asarray([r.src for r in rows] + [0] * pad, i32))
-        if self.last and gs.lp:  # behind everything else: the int64 fields keep their alignment
-            parts.append(np.asarray([r.logprobs for r in rows] + [-1] * pad, i32))
-        arr = np.concatenate(parts)
-        buf = getattr(gs, "_rows_buf", None)
-        if buf is None or buf.numel() < arr.size:
-            buf = gs._rows_buf = torch.empty(2 * arr.size, dtype=torch.int32, device=self.device)
-        self._stage_h2d(gs, arr, buf[: arr.size])
-        gs.slots[:b].copy_(buf[:b])
-        gs.pos[:b].copy_(buf[b: 2 * b])
-        gs.active[:b].copy_(buf[2 * b: 3 * b])
-        o = 3 * b
-        if self.last:
-            gs.temp[:b].copy_(buf[o: o + b].view(torch.float32))
-            gs.topk[:b].copy_(buf[o + b: o + 2 * b])
-            gs.greedy[:b].copy_(buf[o + 2 * b: o + 3 * b])
-            gs.topp[:b].copy_(buf[o + 3 * b: o + 4 * b].view(torch.float32))
-            gs.minp[:b].copy_(buf[o + 4 * b: o + 5 * b].view(torch.float32))
-            o += 5 * b
-            if gs.pen:
-                gs.presence[:b].copy_(buf[o: o + b].view(torch.float32))
-                gs.frequency[:b].copy_(buf[o + b: o + 2 * b].view(torch.float32))
-                o += 2 * b
-            gs.seeds[:b].copy_(buf[o: o + 2 * b].view(torch.int64))
-            gs.sstep[:b].copy_(buf[o + 2 * b: o + 4 * b].view(torch.int64))
-            o += 4 * b
-        if self.first:
-            gathered = gs.tin.index_select(0, buf[o: o + b])
-            gs.tin[:b].copy_(gathered)
-            o += b
-        if self.last and gs.lp:
-            gs.nlp[:b].copy_(buf[o: o + b])
+        words, nargs = pack_rows(gp.rows, gs.cap, self.first, self.last, (gs.cut, gs.pen, gs.lp), slot[0].numpy())
+        return slot, words, record[:nargs]
 
     def _prefill(self, gp: GroupPlan, gs: GroupState, inp: Optional[torch.Tensor]):
         st, be, dev = self.stage, self.stage.backend, self.device
@@ -1268,10 +1149,7 @@ class StageWorker(racecheck.Shared):
             be.decode = False
             logits = st.head(x, meta, rows=rows)
         fc = [ch[i] for i in finals]
-        samp = SamplingState([c.temperature for c in fc], [c.top_k for c in fc],
-                             [c.greedy for c in fc], [c.seed for c in fc], dev,
-                             [c.top_p for c in fc], [c.min_p for c in fc])
-        ids = be.sample(logits, samp, st.cfg.vocab_size)
+        ids = be.sample(logits, SamplingState.of(fc, dev), st.cfg.vocab_size)
         self._record_finals(fc, ids, logits)
         return ids
 

@@ -131,6 +131,12 @@ class SamplingState:
             self.min_p = torch.tensor(min_p, dtype=torch.float32, device=device)
         self.num_rows = B
 
+    @classmethod
+    def of(cls, chunks, device) -> "SamplingState":
+        """The state that samples the final prefill chunks `chunks` (runtime/plan.py Chunk)."""
+        t, k, g, sd, tp, mp = zip(*((c.temperature, c.top_k, c.greedy, c.seed, c.top_p, c.min_p) for c in chunks))
+        return cls(t, k, g, sd, device, tp, mp)
+
     def uniforms(self) -> torch.Tensor:
         """U[0,1) per row from (seed, step); host reference of the device hash."""
         return counter_uniform(self.seeds, self.step)

@@ -26,9 +26,11 @@ mode), so all stages agree on shapes without any device->host sync.
 from __future__ import annotations
 
 import io
+import itertools
+import operator
 import pickle
-from dataclasses import dataclass, field
-from typing import List, Optional
+from dataclasses import dataclass, field, fields
+from typing import List, NamedTuple, Optional
 
 
 @dataclass
@@ -88,6 +90,8 @@ class GroupPlan:
     # compat forward (reference /forward_b through stages 1..P-1): hidden rows
     kind: str = "step"                      # "step" | "fwd_b"
     fwd_rows: int = 0
+    # row_features(rows), once a last stage has computed it (not part of the plan: never sent)
+    feats: Optional[tuple] = field(default=None, compare=False, repr=False)
 
     @property
     def n_final(self) -> int:
@@ -111,6 +115,111 @@ class StepPlan:
     timing: bool = False                    # record per-item compute events
     end: bool = False                       # session end: followers return
     stop: bool = False                      # shut the follower down
+
+
+# ---------------------------------------------------------------------------
+# Per-row sampler fields: THE list.  The plan wire, the scheduler's request
+# state, GroupState's vectors, apply_rows' packed buffer and its argument
+# record all read it: a new field is one line here, the dataclass field on Row
+# / Chunk (same order) and the SamplingParams plumbing in sampler_values.
+# ---------------------------------------------------------------------------
+class RowField(NamedTuple):
+    name: str    # attribute of Row / Chunk
+    dtype: str   # on the device, torch's and numpy's name: "float32" | "int32" | "int64"
+    idle: float  # pad rows' value: what apply_rows_kernel writes for i >= n
+    gate: str    # travels always ("last": on the last stage) or while a row has a "cut" / "pen" / "lp"
+    col: int     # packed buffer (layout: above apply_rows_kernel, csrc/kernels/elementwise.hip):
+                 # f[col cap, (col + 1) cap); an int64 field: the col-th int64 vector
+    word: int    # the word of apply_rows' argument record that holds the row vector's address
+    vec: str     # the row vector, an attribute of parallel/pipeline.py GroupState
+
+
+ROW_FIELDS = (
+    RowField("temperature", "float32", 1.0, "last", 2, 6, "temp"),
+    RowField("top_k", "int32", 1, "last", 3, 7, "topk"),
+    RowField("greedy", "int32", 1, "last", 4, 8, "greedy"),
+    RowField("seed", "int64", 0, "last", 0, 9, "seeds"),
+    RowField("step", "int64", 0, "last", 1, 10, "sstep"),
+    RowField("top_p", "float32", 1.0, "cut", 6, 12, "topp"),
+    RowField("min_p", "float32", 0.0, "cut", 7, 13, "minp"),
+    RowField("presence", "float32", 0.0, "pen", 8, 14, "presence"),
+    RowField("frequency", "float32", 0.0, "pen", 9, 15, "frequency"),
+    RowField("logprobs", "int32", -1, "lp", 10, 16, "nlp"),
+)
+_GATES = ("last", "cut", "pen", "lp")
+NO_FEATURES = (False, False, False)
+_STEP = [f.name for f in ROW_FIELDS].index("step")
+
+
+def _through(gate: str) -> tuple:
+    """The fields up to a gate.  Record and wire are positional: what travels
+    with a gate travels with every later one (logprobs carry the penalties)."""
+    return tuple(f for f in ROW_FIELDS if _GATES.index(f.gate) <= _GATES.index(gate))
+
+
+def device_fields(last: bool, feats=NO_FEATURES) -> tuple:
+    """The fields a composition with the features (cut, pen, lp) writes to the
+    device: none off the last stage; on it the top-p / min-p vectors always
+    (the sampler reads them only with a cut)."""
+    return _through("lp" if feats[2] else "pen" if feats[1] else "cut") if last else ()
+
+
+def packed_size(cap: int, fields: tuple) -> tuple:
+    """(int32 words of the packed buffer to copy, words of the argument record)
+    of a composition that writes `fields`; without any: KV slot, position and
+    stage 0's gather index (column 5), record words [0, 12)."""
+    cols = max([6] + [f.col + 1 for f in fields if f.dtype != "int64"])
+    return (4 + cols) * cap + 1, max([12] + [f.word + 1 for f in fields])
+
+
+_SCAN = operator.attrgetter("top_p", "min_p", "presence", "frequency", "logprobs")
+_SCAN_OFF = (1.0, 0.0, 0.0, 0.0, -1)
+
+
+def _scan(xs) -> tuple:
+    """(cut, pen, lp, wide) of Rows / Chunks in one pass that stops once all
+    are set; wide: an entry's top_p / min_p is not the default (what the wire
+    must carry to be exact, whether or not it cuts)."""
+    cut = pen = lp = wide = False
+    for tp, mp, pp, fp, n in itertools.filterfalse(_SCAN_OFF.__eq__, map(_SCAN, xs)):
+        wide = wide or tp != 1.0 or mp != 0.0
+        cut = cut or tp < 1.0 or mp > 0.0
+        pen = pen or pp != 0.0 or fp != 0.0
+        lp = lp or n >= 0
+        if cut and pen and lp:
+            break
+    return cut, pen, lp, wide
+
+
+def row_features(xs) -> tuple:
+    """(cut, pen, lp) of a list of Rows or Chunks, one pass, no side effect:
+    some entry has top_p < 1 or min_p > 0; a nonzero penalty; logprobs >= 0."""
+    return _scan(xs)[:3]
+
+
+def sampler_values(p, seed: int) -> tuple:
+    """A request's values of ROW_FIELDS in the order Chunk and Row declare
+    them, as (those ahead of the per-draw step, those behind it): a Chunk takes
+    both in a row, a Row its step and src between them.  p: its SamplingParams."""
+    v = (p.temperature, p.top_k, p.greedy, seed, p.top_p, p.min_p, float(p.presence_penalty),
+         float(p.frequency_penalty), -1 if p.logprobs is None else int(p.logprobs))
+    return v[:_STEP], v[_STEP:]
+
+
+def pack_rows(rows, cap: int, first: bool, last: bool, feats, a) -> tuple:
+    """Fill the int32 array `a` with the rows' state in the layout documented
+    above apply_rows_kernel (pad rows are the kernel's) -> packed_size."""
+    import numpy as np
+
+    fields = device_fields(last, feats)
+    n, f0 = len(rows), 4 * cap + 1
+    a[4 * cap] = n
+    cols = [("slot", "int32", 0), ("pos", "int32", 1)] + ([("src", "int32", 5)] if first else [])
+    for name, dtype, c in cols + [(f.name, f.dtype, f.col) for f in fields] if n else ():
+        dst = (a[: 4 * cap] if dtype == "int64" else a[f0:]).view(dtype)
+        # np.fromiter over the attribute: the cheapest way from 4096 objects to a column
+        dst[c * cap: c * cap + n] = np.fromiter(map(operator.attrgetter(name), rows), dtype, n)
+    return packed_size(cap, fields)
 
 
 # ---------------------------------------------------------------------------
@@ -151,40 +260,57 @@ def _steady_groups(plan: StepPlan):
 # follower as objects (631 KB: too big for a plan-ring slot, so it went over
 # gloo to each follower); as columns without the token ids -- which only a
 # replica's stage 0 reads -- ~6 / ~7 ms and 182 KB, inline in the ring.
-def _float_cols(xs):
-    """float64 column(s) of Chunks / Rows: [n] temperatures while every entry
-    has the default top_p / min_p (the common case stays as small as before),
-    else [n, 3] = (temperature, top_p, min_p), or [n, 5] with (presence,
-    frequency) appended when an entry has a penalty."""
+# The columns come from ROW_FIELDS: float64 [n] temperatures while every entry
+# has the default top_p / min_p (the common case stays as small as before),
+# else [n, 3], or [n, 5] when an entry has a penalty; int64 columns of the
+# entry's own fields and the integer ones of the list, the gated ones (the
+# logprob counts) only when some entry asks.  A chunk has no step, and its
+# seeds travel as a column of their own.
+_FLOATS = tuple(f.name for f in ROW_FIELDS if f.dtype == "float32")
+_INTS = tuple(f.name for f in _through("last") if f.dtype != "float32")
+_ASKED_INTS = tuple(f.name for f in ROW_FIELDS if f.dtype != "float32" and f.gate != "last")
+_CHUNK_INTS = ("seq", "slot", "start", "qlen", "final") + tuple(n for n in _INTS if n not in ("seed", "step"))
+_ROW_INTS = ("seq", "slot", "pos") + _INTS + ("src",)
+_DEFAULTS = {cls: tuple((f.name, f.default) for f in fields(cls)) for cls in (Chunk, Row)}
+# sampler_values' order is the order both dataclasses declare the fields in
+assert all([n for n, _ in _DEFAULTS[cls] if n in _FLOATS + _INTS + _ASKED_INTS and n != "step"]
+           == [f.name for f in ROW_FIELDS if f.name != "step"] for cls in (Chunk, Row))
+
+
+def _pack_cols(xs, ints: tuple) -> tuple:
+    """(int64 [n, w], float64 [n] or [n, w]) columns of Chunks / Rows."""
     import numpy as np
 
-    if any(x.presence != 0.0 or x.frequency != 0.0 for x in xs):
-        return np.array([(x.temperature, x.top_p, x.min_p, x.presence, x.frequency) for x in xs],
-                        dtype=np.float64).reshape(-1, 5)
-    if all(x.top_p == 1.0 and x.min_p == 0.0 for x in xs):
-        return np.array([x.temperature for x in xs], dtype=np.float64)
-    return np.array([(x.temperature, x.top_p, x.min_p) for x in xs], dtype=np.float64).reshape(-1, 3)
+    _, pen, lp, wide = _scan(xs)
+    if lp:
+        ints = ints + _ASKED_INTS
+    floats = [f.name for f in _through("pen" if pen else "cut" if wide else "last") if f.dtype == "float32"]
+    fl = np.array(list(map(operator.attrgetter(*floats), xs)), dtype=np.float64)
+    return (np.array(list(map(operator.attrgetter(*ints), xs)), dtype=np.int64).reshape(-1, len(ints)),
+            fl if len(floats) == 1 else fl.reshape(-1, len(floats)))
 
 
-def _float_rows(temp):
-    """(temperature, top_p, min_p, presence, frequency) per entry of a
-    _float_cols column."""
-    if temp.ndim == 1:
-        return [(t, 1.0, 0.0, 0.0, 0.0) for t in temp.tolist()]
-    if temp.shape[1] == 3:
-        return [(t, tp, mp, 0.0, 0.0) for t, tp, mp in temp.tolist()]
-    return temp.tolist()
-
-
-def _int_cols(rows, xs, width: int):
-    """int64 columns of Chunks / Rows, [n, width]; a trailing column of the
-    logprob counts only when some entry asks (all-default traffic packs what
-    it did before the column existed)."""
-    import numpy as np
-
-    if any(x.logprobs >= 0 for x in xs):
-        return np.array([r + (x.logprobs,) for r, x in zip(rows, xs)], dtype=np.int64).reshape(-1, width + 1)
-    return np.array(rows, dtype=np.int64).reshape(-1, width)
+def _unpack_cols(cls, ints_names: tuple, ints, floats, **more) -> list:
+    """Inverse of _pack_cols (`more`: further columns by field name): the
+    entries, fields that did not travel at their defaults."""
+    if ints.shape[1] > len(ints_names):
+        ints_names = ints_names + _ASKED_INTS
+    cols = dict(zip(ints_names, ints.T.tolist()), **more)
+    if floats.ndim == 1:
+        cols[_FLOATS[0]] = floats.tolist()
+    else:
+        cols.update(zip(_FLOATS, floats.T.tolist()))
+    for nm in ("final", "greedy"):
+        if nm in cols:
+            cols[nm] = map(bool, cols[nm])
+    if "qlen" in cols:
+        lens, tok = cols.pop("qlen"), cols.pop("tok")
+        if tok is None:
+            cols["ids"] = map(range, lens)
+        else:
+            cols["ids"] = (tok[e - ln: e] for ln, e in zip(lens, itertools.accumulate(lens)))
+    return list(itertools.starmap(cls, zip(*(cols[nm] if nm in cols else itertools.repeat(d)
+                                             for nm, d in _DEFAULTS[cls]))))
 
 
 def _pack_group(gp: GroupPlan, ids: bool):
@@ -195,18 +321,10 @@ def _pack_group(gp: GroupPlan, ids: bool):
         c = gp.chunks
         tok = None
         if ids:
-            import itertools
-
             tok = np.fromiter(itertools.chain.from_iterable(x.ids for x in c), dtype=np.int32,
                               count=sum(len(x.ids) for x in c))
-        ch = (_int_cols([(x.seq, x.slot, x.start, len(x.ids), x.final, x.top_k, x.greedy) for x in c], c, 7),
-              _float_cols(c),
-              np.array([x.seed for x in c], dtype=np.int64), tok)
-    rows = None
-    if gp.rows is not None:
-        r = gp.rows
-        rows = (_int_cols([(x.seq, x.slot, x.pos, x.top_k, x.greedy, x.seed, x.step, x.src) for x in r], r, 8),
-                _float_cols(r))
+        ch = _pack_cols(c, _CHUNK_INTS) + (np.array([x.seed for x in c], dtype=np.int64), tok)
+    rows = _pack_cols(gp.rows, _ROW_INTS) if gp.rows is not None else None
     return (gp.g, gp.ret, gp.n, gp.b, gp.ctxb, gp.kind, gp.fwd_rows, ch, rows)
 
 
@@ -215,20 +333,11 @@ def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows) -> GroupPlan:
     range(len) in their place (their stage reads only the lengths)."""
     gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb, kind=kind, fwd_rows=fwd_rows)
     if ch is not None:
-        ints, temp, seeds, tok = ch
-        tok = tok.tolist() if tok is not None else None
-        out, o = [], 0
-        for (seq, slot, start, ln, final, top_k, greedy, *lp), (t, tp, mp, pp, fp), sd in zip(
-                ints.tolist(), _float_rows(temp), seeds.tolist()):
-            out.append(Chunk(seq, slot, start, tok[o: o + ln] if tok is not None else range(ln), bool(final),
-                             t, top_k, bool(greedy), sd, tp, mp, pp, fp, *lp))
-            o += ln
-        gp.chunks = out
+        ints, floats, seeds, tok = ch
+        gp.chunks = _unpack_cols(Chunk, _CHUNK_INTS, ints, floats, seed=seeds.tolist(),
+                                 tok=tok.tolist() if tok is not None else None)
     if rows is not None:
-        ints, temp = rows
-        gp.rows = [Row(seq, slot, pos, t, top_k, bool(greedy), seed, step, src, tp, mp, pp, fp, *lp)
-                   for (seq, slot, pos, top_k, greedy, seed, step, src, *lp), (t, tp, mp, pp, fp) in zip(
-                       ints.tolist(), _float_rows(temp))]
+        gp.rows = _unpack_cols(Row, _ROW_INTS, *rows)
     return gp
 
 

@@ -41,7 +41,7 @@ import torch
 
 from ..config import SamplingParams
 from ..utils import racecheck
-from .plan import Chunk, GroupPlan, Row, StepPlan
+from .plan import Chunk, GroupPlan, Row, StepPlan, sampler_values
 
 log = logging.getLogger("llm_sharding_demo_amd.scheduler")
 
@@ -528,10 +528,8 @@ def make_sched_core(replicas: int, groups: int, cap: int, prefill_budget: int, c
 class _Meta:
     req: Request
     seed: int
-    samp: tuple = ()    # (temperature, top_k, greedy, seed): the chunk / row sampling fields
-    # (top_p, min_p, presence, frequency): the trailing chunk / row fields
-    # then the logprob count (-1: none)
-    cut: tuple = (1.0, 0.0, 0.0, 0.0, -1)
+    values: tuple = ((), ())  # plan.sampler_values: the chunk / row sampler fields
+    logprobs: int = -1  # alternatives asked with every token's logprob (-1: no records)
     rep: int = 0        # replica and KV slot, from the request's first prefill chunk
     slot: int = -1
     done: bool = False  # finished by this scheduler (plain flag: the readout loop's hot path)
@@ -624,9 +622,7 @@ class Scheduler(racecheck.Shared):
         for i, req in zip(ids, reqs):
             p = req.params
             seed = p.seed if p.seed is not None else rng.getrandbits(62)
-            meta[i] = _Meta(req, seed, (p.temperature, p.top_k, p.greedy, seed),
-                            (p.top_p, p.min_p, float(p.presence_penalty), float(p.frequency_penalty),
-                             -1 if p.logprobs is None else int(p.logprobs)))
+            meta[i] = _Meta(req, seed, sampler_values(p, seed), -1 if p.logprobs is None else int(p.logprobs))
             lens.append(len(req.prompt_ids))
             wants.append(p.max_new_tokens)
             stops.append(bool(p.stop_at_eos))
@@ -666,13 +662,13 @@ class Scheduler(racecheck.Shared):
         gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb)
         meta = self.meta
         for sid, slot, start, _, _ in chunks:
-            if start == 0 and meta[sid].cut[4] >= 0:  # where _finish fetches the logprob records
+            if start == 0 and meta[sid].logprobs >= 0:  # where _finish fetches the logprob records
                 meta[sid].rep, meta[sid].slot = rep, slot
-        gp.chunks = [Chunk(sid, slot, start, m.req.prompt_ids[start:start + ln], final, *m.samp, *m.cut)
-                     for sid, slot, start, ln, final in chunks for m in (meta[sid],)]
+        gp.chunks = [Chunk(sid, slot, start, m.req.prompt_ids[start:start + ln], final, *h, *t)
+                     for sid, slot, start, ln, final in chunks for m in (meta[sid],) for h, t in (m.values,)]
         if changed:
-            gp.rows = [Row(sid, slot, pos, *meta[sid].samp, sstep, src, *meta[sid].cut)
-                       for sid, slot, pos, sstep, src in rows]
+            gp.rows = [Row(sid, slot, pos, *h, sstep, src, *t)
+                       for sid, slot, pos, sstep, src in rows for h, t in (meta[sid].values,)]
         return gp
 
     # -- token readout -----------------------------------------------------------
@@ -774,7 +770,7 @@ class Scheduler(racecheck.Shared):
         slot is still the request's: it goes back to the pool after this
         readout at the earliest, and draws issued past the last token write
         records at or past len(toks) only."""
-        n = m.cut[4]
+        n = m.logprobs
         if n >= 0:
             try:
                 lt, li, lv = self.eng.fetch_logprobs(m.rep, m.slot, len(toks))
