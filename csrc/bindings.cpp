@@ -11,13 +11,17 @@
 #include <cmath>
 
 #include "kernels/gemm_params.h"
+#include "kernels/gemm_plan.h"
 
 typedef lsd_bf16_t bf16;
 using lsd::GemmParams;
+using lsd::GemmPlan;
 using lsd::GemvParams;
 
 extern "C" {
-hipError_t lsd_gemm(const GemmParams* p, int epi, int tiled, int* cnt, float* ws, hipStream_t st);
+// the one launch decision (kernels/gemm_plan.h) under the current tuning, and the launch of exactly that plan
+void lsd_gemm_plan(int M, int N, int K, int splits, int epi, int kind, GemmPlan* out);
+hipError_t lsd_gemm(const GemmParams* p, const GemmPlan* plan, int* cnt, float* ws, hipStream_t st);
 const char* lsd_gemm_last_launch();
 const char* lsd_norm_last_launch();
 void lsd_gemm_set_big_min(int v);
@@ -41,7 +45,6 @@ void lsd_attn_set_small_waves(int v);
 void lsd_attn_set_small_waves128(int v);
 void lsd_attn_set_large_waves(int hd, int v);
 void lsd_attn_set_mfma_min(int v);
-int lsd_gemm_sk_rows(int M, int N, int S);
 int lsd_gemm_sk_rblocks(int M, int N, int S);
 int lsd_gemm_sk_nw(int M, int epi);
 void lsd_gemm_set_nw2_rows(int v);
@@ -88,8 +91,7 @@ hipError_t lsd_logprobs(const float* logits, long ld, int B, int V, const int* t
 
 namespace {
 
-enum Epi : int { EPI_BF16 = 0, EPI_GELU = 1, EPI_SILU_MUL = 2, EPI_F32 = 3, EPI_RESID = 4,
-                 EPI_SLAB = 5, EPI_QKV = 6 };
+using lsd::EPI_BF16, lsd::EPI_GELU, lsd::EPI_SILU_MUL, lsd::EPI_F32, lsd::EPI_RESID, lsd::EPI_SLAB, lsd::EPI_QKV;
 
 hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
@@ -163,56 +165,38 @@ GemmParams base_params(const torch::Tensor& a, const torch::Tensor& w, int64_t t
   return p;
 }
 
-// Launch with split-K bookkeeping: the decode path needs persistent zeroed
-// ticket counters (one per column tile) and an fp32 partial-tile workspace.
+// Launch with split-K bookkeeping: an in-kernel combine needs persistent
+// zeroed ticket counters (one per output tile) and an fp32 partial-tile
+// workspace, both sized from the plan that is then launched.
 void run_gemm(GemmParams& p, int epi, int64_t tiled, int64_t splits,
               const c10::optional<torch::Tensor>& counters, const torch::Tensor& like,
               const char* what) {
   const int kt = tiled ? p.K / 64 : p.K / 32;
   TORCH_CHECK(splits >= 1 && splits <= kt, what, ": splits must be in [1, ", kt, "], got ", splits);
   p.splits = (int)splits;
+  GemmPlan plan;
+  lsd_gemm_plan(p.M, p.N, p.K, p.splits, epi, (int)tiled, &plan);
+  TORCH_CHECK(!(tiled && splits > 1 && epi != EPI_SLAB) || (plan.valid && plan.combine_tiles > 0),
+              what, ": tiled split-K with an in-kernel combine needs the 256-row "
+              "kernel (kind 2 / 3) or the 8-wave decode ring");
+  TORCH_CHECK(plan.valid, what, ": no GEMM kernel takes this shape");
+  if (plan.kernel == lsd::GK_SK && epi == EPI_SILU_MUL)  // column tile = 64 * nw (partial last tile masked otherwise)
+    TORCH_CHECK(p.N % (64 * plan.nw) == 0, what, ": N must be a multiple of ", 64 * plan.nw);
   int* cnt = nullptr;
   float* ws = nullptr;
   torch::Tensor wsbuf;
-  if (tiled && splits > 1 && epi != EPI_SLAB) {
-    // tiled split-K with an in-kernel combine: the 256-row decode kernel
-    // (gemm_d256, kind 2 / 3) or the 8-wave 128x64 ring (kind 1) -- ticket
-    // counters + fp32 partial tiles per split
-    const int bn = lsd_gemm_d256_bn((int)tiled, p.M, p.N, p.K);
-    const int r8 = tiled == 1 ? lsd_gemm_ring8_tiles(p.M, p.N, p.K, (int)splits) : 0;
-    TORCH_CHECK(bn > 0 || r8 > 0, what, ": tiled split-K with an in-kernel combine needs the 256-row "
-                "kernel (kind 2 / 3) or the 8-wave decode ring");
-    const long tiles = r8 > 0 ? r8 : (long)((p.N + bn - 1) / bn) * ((p.M + 255) / 256);
-    const long tile_floats = r8 > 0 ? 128L * 64 : 256L * bn;
+  if (plan.combine_tiles > 0) {
     TORCH_CHECK(counters.has_value(), what, ": split-K needs the ticket counter buffer");
     need(*counters, torch::kInt32, "counters");
-    TORCH_CHECK(counters->is_contiguous() && counters->numel() >= tiles,
-                what, ": counter buffer too small (", counters->numel(), " < ", tiles, ")");
+    TORCH_CHECK(counters->is_contiguous() && counters->numel() >= plan.combine_tiles,
+                what, ": counter buffer too small (", counters->numel(), " < ", plan.combine_tiles, ")");
     cnt = counters->data_ptr<int>();
-    TORCH_CHECK(splits * tile_floats * 4 < (1L << 31), what, ": split workspace too large");
-    wsbuf = torch::empty({tiles * splits * tile_floats}, like.options().dtype(torch::kFloat32));
+    TORCH_CHECK(splits * plan.tile_floats * 4 < (1L << 31), what, ": split workspace too large");
+    wsbuf = torch::empty({plan.combine_tiles * splits * plan.tile_floats}, like.options().dtype(torch::kFloat32));
     ws = wsbuf.data_ptr<float>();
   }
-  if (!tiled && epi != EPI_SLAB) {
-    const int nw = lsd_gemm_sk_nw(p.M, epi);  // column tile = 64 * nw (partial last tile masked)
-    if (epi == EPI_SILU_MUL)
-      TORCH_CHECK(p.N % (64 * nw) == 0, what, ": N must be a multiple of ", 64 * nw);
-    const long tiles = (p.N + 64 * nw - 1) / (64 * nw) * lsd_gemm_sk_rblocks(p.M, p.N, (int)splits);
-    if (splits > 1) {
-      TORCH_CHECK(counters.has_value(), what, ": split-K needs the ticket counter buffer");
-      need(*counters, torch::kInt32, "counters");
-      TORCH_CHECK(counters->is_contiguous() && counters->numel() >= tiles,
-                  what, ": counter buffer too small (", counters->numel(), " < ", tiles, ")");
-      cnt = counters->data_ptr<int>();
-      const long rows = lsd_gemm_sk_rows(p.M, p.N, (int)splits);  // rows per row block
-      const long bytes = tiles * splits * rows * 64 * nw * 4;
-      TORCH_CHECK(splits * rows * 64 * nw * 4 < (1L << 31), what, ": split workspace too large");
-      wsbuf = torch::empty({bytes / 4}, like.options().dtype(torch::kFloat32));
-      ws = wsbuf.data_ptr<float>();
-    }
-  }
   p.stamps = g_stamps;
-  check_hip(lsd_gemm(&p, epi, (int)tiled, cnt, ws, cur_stream()), what);
+  check_hip(lsd_gemm(&p, &plan, cnt, ws, cur_stream()), what);
 }
 
 
@@ -917,9 +901,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_ok", [](int64_t M, int64_t K, int64_t epi, int64_t norm) {
     return lsd_gemv_ok((int)M, (int)K, (int)epi, (int)norm) != 0; });
   m.def("set_stamps", &set_stamps);
-  // tiled GEMMs with >= this many 256x256 tiles use the pipelined 256^2 kernel
   m.def("gemm_last_launch", [] { return std::string(lsd_gemm_last_launch()); });
   m.def("norm_last_launch", [] { return std::string(lsd_norm_last_launch()); });
+  // tiled GEMMs with >= this many 256x256 tiles use the pipelined 256^2 kernel
   m.def("gemm_set_big_min", [](int64_t v) { lsd_gemm_set_big_min((int)v); });
   // large-GEMM tile order: groups of this many row panels (0 = M-fastest)
   m.def("gemm_set_big_group", [](int64_t v) { lsd_gemm_set_big_group((int)v); });
@@ -960,6 +944,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // decode GEMM column tile 128 (NW = 2) above this many rows
   m.def("gemm_set_nw2_rows", [](int64_t v) { lsd_gemm_set_nw2_rows((int)v); });
   m.def("gemm_sk_nw", [](int64_t M, int64_t epi) { return lsd_gemm_sk_nw((int)M, (int)epi); });
+  // the launch run_gemm would make of this shape under the current knobs (kernels/gemm_plan.h)
+  m.def("gemm_plan", [](int64_t M, int64_t N, int64_t K, int64_t splits, int64_t epi, int64_t kind) {
+    GemmPlan pl;
+    lsd_gemm_plan((int)M, (int)N, (int)K, (int)splits, (int)epi, (int)kind, &pl);
+    TORCH_CHECK(pl.valid, "gemm_plan: no GEMM kernel takes this shape");
+    py::dict d;
+    d["tag"] = std::string(pl.tag);
+    d["grid"] = py::make_tuple(pl.grid[0], pl.grid[1], pl.grid[2]);
+    d["block"] = pl.block;
+    d["combine_tiles"] = pl.combine_tiles;
+    d["tile_floats"] = pl.tile_floats;
+    return d;
+  });
   // A HIP stream whose kernels may only run on the CUs set in `mask` (32-bit
   // words; bit i = CU i of the device's mask numbering) -- spatial
   // partitioning of the chip between microbatch lanes (parallel/pipeline.py

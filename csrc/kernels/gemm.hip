@@ -27,19 +27,9 @@
 // shard-local KV cache at (slot, position).
 #include "common.h"
 #include "gemm_params.h"
+#include "gemm_plan.h"  // Epi, tile constants, GemmTuning / GemmPlan / plan_gemm()
 
 namespace lsd {
-
-enum Epi : int {
-  EPI_BF16 = 0,      // out bf16 = acc + bias
-  EPI_GELU = 1,      // out bf16 = gelu_new(acc + bias)
-  EPI_SILU_MUL = 2,  // out bf16 [M, N/2] = silu(gate) * up; W rows interleaved in 16-row blocks
-  EPI_F32 = 3,       // out f32 = acc
-  EPI_RESID = 4,     // x f32 += acc + bias
-  EPI_SLAB = 5,      // slab[split][M][N] = acc
-  EPI_QKV = 6,       // q -> out bf16, k/v -> KV cache (+ RoPE)
-};
-
 
 // (head, dim) of column c inside the q / k / v block: shifts and a mask for the
 // power-of-two head dims of every model here (a wave-uniform branch; integer
@@ -634,7 +624,7 @@ __global__ __launch_bounds__(256) void gemm_sk_kernel(GemmParams p, int* __restr
 // ---------------------------------------------------------------------------
 // Tiled GEMM (M > 64): 128x128x64, glds-staged, swizzled, double-buffered
 // ---------------------------------------------------------------------------
-constexpr int TBM = 128, TBN = 128, TBK = 64;
+constexpr int TBK = 64;  // TBM, TBN: gemm_plan.h
 constexpr int TILE_BYTES = TBM * TBK * 2;  // 16 KiB per operand tile
 constexpr int CT_LD = TBN + 4;              // epilogue fp32 C tile row stride (bank skew)
 constexpr int SMEM_TILED = TBM * CT_LD * 4 > 4 * TILE_BYTES ? TBM * CT_LD * 4 : 4 * TILE_BYTES;
@@ -1169,7 +1159,7 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmParams p, int tiles
 // lane groups of CDNA4 ({0-3,12-15,20-27}, {4-11,16-19,28-31}, and +32)
 // every group of a fragment read covers 16 distinct 16-B bank slots.  glds
 // writes lane-linear, so the swizzle goes on the per-lane source address.
-constexpr int GBM = 256, GBN = 256, GBK = 32, GSLOTS = 4;
+constexpr int GBK = 32, GSLOTS = 4;  // GBM, GBN: gemm_plan.h
 constexpr int GOP_BYTES = GBM * GBK * 2;           // 16 KiB per operand per slot
 constexpr int GSLOT_BYTES = 2 * GOP_BYTES;         // A | W
 constexpr int GSMEM = GSLOTS * GSLOT_BYTES;        // 128 KiB (== 256 x 128 fp32 C half-tile)
@@ -1881,273 +1871,146 @@ __global__ __launch_bounds__(512) void gemm_d256_kernel(GemmParams p, int* __res
 // ---------------------------------------------------------------------------
 // Host launchers
 // ---------------------------------------------------------------------------
-// Name of the kernel (and its non-epilogue template arguments) of the last
-// launch, set by every branch below: lsd_gemm_last_launch() lets a test see
-// which kernel its knobs and shape really reached.  A diagnostic: one plain
-// pointer to a string literal, last writer wins across threads.
+// Which kernel instance runs, on which grid and with how much split-K
+// workspace is decided in ONE place, plan_gemm() in gemm_plan.h.  The code
+// below only maps a GemmPlan's selectors to the template instantiation they
+// name; it reads no tuning knob.
+
+// Tag of the last launch (GemmPlan::tag: the kernel and its non-epilogue
+// template arguments): lsd_gemm_last_launch() lets a test see which kernel its
+// knobs and shape really reached.  A diagnostic: one plain pointer to a string
+// literal, last writer wins across threads.
 static const char* g_last_launch = "";
-#define LSD_LAUNCH(tag, ...)          \
-  do {                                \
-    g_last_launch = tag;              \
-    hipLaunchKernelGGL(__VA_ARGS__);  \
+#define LSD_LAUNCH(...)                                                   \
+  do {                                                                    \
+    g_last_launch = pl.tag;                                               \
+    hipLaunchKernelGGL(__VA_ARGS__);                                      \
+    return hipGetLastError();                                             \
   } while (0)
 
-static int g_big_min_blocks = 160;  // lsd_gemm_set_big_min(): tuning / tests
-// lsd_gemm_set_big_group(): tile_order() group (0 = M-fastest).  4: XL prefill
-// GEMMs 10-25 % faster than M-fastest, 8 equal, 16+ slower
-// (profiles/r2_prefill_tile_order.log)
-static int g_big_group = 4;
-// lsd_gemm_set_big_kind(): 0 = BK=32 ring kernel (gemm_big), 1 = phase-pipelined BK=64 (gemm_p8)
-// with global_load_lds, 4 (default) = the same with buffer_load ... lds staging (+6 % on the GPT-2 XL
-// prefill projections and +25 % at 4096^3 over kind 1; profiles/r3_p8_buffer_lds.log)
-static int g_big_kind = 4;
-// 128x128 launches of at most this many workgroups use the 3-slot ring kernel
-// (1 block/CU); larger grids keep the 2-blocks/CU double-buffered one.
-// lsd_gemm_set_tiled3_max(): tuning / tests; 0 = off
-static int g_tiled3_max_blocks = 0;
-static int g_ring_slots = 3;  // lsd_gemm_set_ring_slots(): 3 or 4
-static int g_ring_tn = 128;   // lsd_gemm_set_ring_tn(): ring tile columns, 128, 64, 32 or 0 (auto 32/64)
-static int g_ring_fill = 128; // auto: 32-wide tiles below this many 64-wide workgroups
-static int g_ring_m96 = 0;    // lsd_gemm_set_ring_m96(): largest 96-row-tile ring grid (0 = off)
-// lsd_gemm_set_ring8(): 128x64 decode ring on 8 waves (gemm_ring8_kernel): 0 off, 1 loader waves, 2 all compute
-static int g_ring8 = 0;
-// lsd_gemm_set_ring8_flags(): A/B bits, 1 = rotate each tile's K start, 2 = weights staged nt
-static int g_ring8_flags = 0;
-// lsd_gemm_set_ring8_pack(): operands in k-block-packed layouts (bit 0 W, bit 1 A; A/B only)
-static int g_ring8_pack = 0;
-static int g_d256_slots = 3;  // lsd_gemm_set_d256_slots(): gemm_d256 ring depth 2..4 (BN 128: at most 3)
-// Decode GEMM row blocking: when the column tiles x K splits leave the chip
-// under-filled (< g_rb_fill workgroups, e.g. the deferred-residual projections
-// with N = H), M > g_sk_rows rows run as ceil(M / g_sk_rows) row blocks
-// (grid z) that share each W tile through L2 -- more workgroups without more
-// split-K slab traffic (tools/microbench.py rows: H x H projection at M = 128
-// 14.1 -> 12.1 us; well-filled grids gain nothing, lm_head loses).
-static int g_sk_rows = 64;
-static int g_rb_fill = 192;
-// At most 128 rows (MT = 8) per row block: M up to 256 always runs as >= 2
-// row blocks.
-static int sk_rblocks(int M, int N, int S) {
-  const int need = (M + 127) / 128;
-  if (M <= g_sk_rows || (N / 64) * S >= g_rb_fill) return need;
-  const int rb = (M + g_sk_rows - 1) / g_sk_rows;
-  return rb > need ? rb : need;
-}
-// Row tiles (16 rows each) of one row block: MT is instantiated for
-// {1, 2, 3, 4, 6, 8}.  The split-K workspace is sized from this
-// (lsd_gemm_sk_rows = row blocks x rows per block), so the two never disagree.
-static int sk_mt(int M, int rb) {
-  const int mt = ((M + rb - 1) / rb + 15) / 16;
-  return mt == 5 || mt == 7 ? mt + 1 : mt;
-}
-
-// Column tile width: 64 * NW.  Wide tiles (NW = 2) read A half as often but
-// double the weight fragments per wave; measured slower at M = 128 on every
-// GPT-2 XL shape (tools/microbench.py rows), so only silu_mul (gate/up pairs)
-// uses them by default; lsd_gemm_set_nw2_rows() lowers the row threshold.
-static int g_nw2_rows = 1 << 30;
-static int sk_nw(int M, int epi) { return (epi == EPI_SILU_MUL || M > g_nw2_rows) ? 2 : 1; }
-
 template <int EPI, int NW>
-static hipError_t launch_sk_nw(const GemmParams& p, int* cnt, float* ws, hipStream_t st) {
-  const int RB = sk_rblocks(p.M, p.N, p.splits);
-  const int MT = sk_mt(p.M, RB);
-  dim3 grid((p.N + 64 * NW - 1) / (64 * NW), p.splits, RB), block(256);
-  switch (MT) {
-    case 1: LSD_LAUNCH(NW == 2 ? "sk<1,2>" : "sk<1,1>", (gemm_sk_kernel<1, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    case 2: LSD_LAUNCH(NW == 2 ? "sk<2,2>" : "sk<2,1>", (gemm_sk_kernel<2, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    case 3: LSD_LAUNCH(NW == 2 ? "sk<3,2>" : "sk<3,1>", (gemm_sk_kernel<3, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    case 4: LSD_LAUNCH(NW == 2 ? "sk<4,2>" : "sk<4,1>", (gemm_sk_kernel<4, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    case 6: LSD_LAUNCH(NW == 2 ? "sk<6,2>" : "sk<6,1>", (gemm_sk_kernel<6, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    case 8: LSD_LAUNCH(NW == 2 ? "sk<8,2>" : "sk<8,1>", (gemm_sk_kernel<8, NW, EPI>), grid, block, 0, st, p, cnt, ws); break;
-    default: return hipErrorInvalidValue;
+static hipError_t launch_sk(const GemmParams& p, const GemmPlan& pl, dim3 grid, dim3 block, int* cnt, float* ws,
+                            hipStream_t st) {
+  switch (pl.mt) {
+    case 1: LSD_LAUNCH((gemm_sk_kernel<1, NW, EPI>), grid, block, 0, st, p, cnt, ws);
+    case 2: LSD_LAUNCH((gemm_sk_kernel<2, NW, EPI>), grid, block, 0, st, p, cnt, ws);
+    case 3: LSD_LAUNCH((gemm_sk_kernel<3, NW, EPI>), grid, block, 0, st, p, cnt, ws);
+    case 4: LSD_LAUNCH((gemm_sk_kernel<4, NW, EPI>), grid, block, 0, st, p, cnt, ws);
+    case 6: LSD_LAUNCH((gemm_sk_kernel<6, NW, EPI>), grid, block, 0, st, p, cnt, ws);
+    case 8: LSD_LAUNCH((gemm_sk_kernel<8, NW, EPI>), grid, block, 0, st, p, cnt, ws);
   }
-  return hipGetLastError();
+  return hipErrorInvalidValue;
 }
 
 template <int EPI>
-static hipError_t launch_sk(const GemmParams& p, int* cnt, float* ws, hipStream_t st) {
-  if constexpr (EPI == EPI_SILU_MUL) {
-    return launch_sk_nw<EPI, 2>(p, cnt, ws, st);
-  } else {
-    return sk_nw(p.M, EPI) == 2 ? launch_sk_nw<EPI, 2>(p, cnt, ws, st) : launch_sk_nw<EPI, 1>(p, cnt, ws, st);
+static hipError_t launch_plan(const GemmParams& p, const GemmPlan& pl, int* cnt, float* ws, hipStream_t st) {
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(pl.block);
+  const int tm = pl.tiles_m, tn = pl.tiles_n;
+  switch (pl.kernel) {
+    case GK_SK:
+      if constexpr (EPI != EPI_SILU_MUL)  // silu_mul pairs gate / up columns: wide tiles only
+        if (pl.nw == 1) return launch_sk<EPI, 1>(p, pl, grid, block, cnt, ws, st);
+      return pl.nw == 2 ? launch_sk<EPI, 2>(p, pl, grid, block, cnt, ws, st) : hipErrorInvalidValue;
+    case GK_D256:
+      if (pl.tn == 64 && pl.slots == 2) LSD_LAUNCH((gemm_d256_kernel<EPI, 64, 2>), grid, block, 0, st, p, cnt, ws);
+      if (pl.tn == 64 && pl.slots == 3) LSD_LAUNCH((gemm_d256_kernel<EPI, 64, 3>), grid, block, 0, st, p, cnt, ws);
+      if (pl.tn == 64 && pl.slots == 4) LSD_LAUNCH((gemm_d256_kernel<EPI, 64, 4>), grid, block, 0, st, p, cnt, ws);
+      if (pl.tn == 128 && pl.slots == 2) LSD_LAUNCH((gemm_d256_kernel<EPI, 128, 2>), grid, block, 0, st, p, cnt, ws);
+      if (pl.tn == 128 && pl.slots == 3) LSD_LAUNCH((gemm_d256_kernel<EPI, 128, 3>), grid, block, 0, st, p, cnt, ws);
+      break;
+    case GK_BIG: LSD_LAUNCH((gemm_big_kernel<EPI>), grid, block, 0, st, p, tm, tn, pl.G);
+    case GK_P8:
+      if (pl.var == 0) LSD_LAUNCH((gemm_p8_kernel<EPI, 0>), grid, block, 0, st, p, tm, tn, pl.G);
+      if (pl.var == 4) LSD_LAUNCH((gemm_p8_kernel<EPI, 4>), grid, block, 0, st, p, tm, tn, pl.G);
+      break;
+    case GK_TILED: LSD_LAUNCH((gemm_tiled_kernel<EPI>), grid, block, 0, st, p, tm, tn);
+    case GK_RING:
+      if (pl.m96) LSD_LAUNCH((gemm_ring_kernel<EPI, 3, 64, 3>), grid, block, 0, st, p, tm, tn);
+      if (pl.tn == 32) LSD_LAUNCH((gemm_ring_kernel<EPI, 3, 32>), grid, block, 0, st, p, tm, tn);
+      if (pl.tn == 64) LSD_LAUNCH((gemm_ring_kernel<EPI, 3, 64>), grid, block, 0, st, p, tm, tn);
+      if (pl.tn == 128 && pl.slots == 4) LSD_LAUNCH((gemm_ring_kernel<EPI, 4, 128>), grid, block, 0, st, p, tm, tn);
+      if (pl.tn == 128 && pl.slots == 3) LSD_LAUNCH((gemm_ring_kernel<EPI, 3, 128>), grid, block, 0, st, p, tm, tn);
+      break;
+    case GK_RING8:
+      if (pl.var == 1) LSD_LAUNCH((gemm_ring8_kernel<EPI, 1, 3>), grid, block, 0, st, p, tm, tn, pl.rot, cnt, ws);
+      if (pl.var != 2) break;
+      if (pl.pack == 1) LSD_LAUNCH((gemm_ring8_kernel<EPI, 2, 3, 0, 1>), grid, block, 0, st, p, tm, tn, pl.rot, cnt, ws);
+      if (pl.pack == 2) LSD_LAUNCH((gemm_ring8_kernel<EPI, 2, 3, 0, 2>), grid, block, 0, st, p, tm, tn, pl.rot, cnt, ws);
+      if (pl.pack == 3) LSD_LAUNCH((gemm_ring8_kernel<EPI, 2, 3, 0, 3>), grid, block, 0, st, p, tm, tn, pl.rot, cnt, ws);
+      if (pl.stage == 2) LSD_LAUNCH((gemm_ring8_kernel<EPI, 2, 3, 0, 0, true>), grid, block, 0, st, p, tm, tn, pl.rot, cnt, ws);
+      if (pl.stage == 1) LSD_LAUNCH((gemm_ring8_kernel<EPI, 2, 3, 1>), grid, block, 0, st, p, tm, tn, pl.rot, cnt, ws);
+      LSD_LAUNCH((gemm_ring8_kernel<EPI, 2, 3>), grid, block, 0, st, p, tm, tn, pl.rot, cnt, ws);
   }
-}
-
-// Launch kinds (lsd_gemm `kind`): 0 split-K decode kernel, 1 tiled family
-// (ring / 128x128 / 256x256 by shape), 2 / 3 gemm_d256 with 64 / 128-column
-// tiles (M <= 1024 in 256-row blocks, K % 64 == 0; the caller picks it per GEMM).
-static int d256_bn(int kind, int M, int N, int K) {
-  if (kind < 2 || M < 1 || M > 1024 || K % 64 != 0) return 0;
-  return kind == 3 && N % 128 == 0 ? 128 : 64;
-}
-
-template <int EPI, int BN>
-static hipError_t launch_d256_bn(const GemmParams& p, int* cnt, float* ws, hipStream_t st) {
-  const dim3 grid(((p.N + BN - 1) / BN) * ((p.M + 255) / 256) * p.splits), block(512);
-  const int slots = BN == 128 ? min(g_d256_slots, 3) : g_d256_slots;
-  switch (slots) {
-    case 2: LSD_LAUNCH(BN == 128 ? "d256<128,2>" : "d256<64,2>", (gemm_d256_kernel<EPI, BN, 2>), grid, block, 0, st, p, cnt, ws); break;
-    case 4:
-      if constexpr (BN == 64) {
-        LSD_LAUNCH("d256<64,4>", (gemm_d256_kernel<EPI, BN, 4>), grid, block, 0, st, p, cnt, ws);
-        break;
-      }
-      [[fallthrough]];
-    default: LSD_LAUNCH(BN == 128 ? "d256<128,3>" : "d256<64,3>", (gemm_d256_kernel<EPI, BN, 3>), grid, block, 0, st, p, cnt, ws); break;
-  }
-  return hipGetLastError();
-}
-
-template <int EPI>
-static hipError_t launch_d256(const GemmParams& p, int kind, int* cnt, float* ws, hipStream_t st) {
-  const int bn = d256_bn(kind, p.M, p.N, p.K);
-  if (bn == 0) return hipErrorInvalidValue;
-  if (p.splits > 1 && EPI != EPI_SLAB && (cnt == nullptr || ws == nullptr)) return hipErrorInvalidValue;
-  return bn == 128 ? launch_d256_bn<EPI, 128>(p, cnt, ws, st) : launch_d256_bn<EPI, 64>(p, cnt, ws, st);
-}
-
-template <int EPI>
-static hipError_t launch_tiled(const GemmParams& p, int* cnt, float* ws, hipStream_t st) {
-  // 256x256 pipelined kernel once the problem fills the chip with 1-block/CU
-  // tiles; the 128x128 kernel (2 blocks/CU) for smaller M / N.
-  const int bm = (p.M + GBM - 1) / GBM, bn = (p.N + GBN - 1) / GBN;
-  if (p.M >= GBM && p.K % 64 == 0 && bm * bn * p.splits >= g_big_min_blocks) {
-    if (g_big_kind == 1)
-      LSD_LAUNCH("p8<0>", (gemm_p8_kernel<EPI, 0>), dim3(bm * bn * p.splits), dim3(512), 0, st, p, bm, bn,
-                         g_big_group);
-    else if (g_big_kind == 4)
-      LSD_LAUNCH("p8<4>", (gemm_p8_kernel<EPI, 4>), dim3(bm * bn * p.splits), dim3(512), 0, st, p, bm, bn,
-                         g_big_group);
-    else
-      LSD_LAUNCH("big", (gemm_big_kernel<EPI>), dim3(bm * bn * p.splits), dim3(512), 0, st, p, bm, bn,
-                         g_big_group);
-    return hipGetLastError();
-  }
-  const int tm = (p.M + TBM - 1) / TBM;
-  if (g_ring_tn == 64 || g_ring_tn == 32 || g_ring_tn == 0) {
-    // narrow ring tiles: twice the workgroups of the 128-column grid; 32-wide
-    // (2 blocks/CU) when 64-wide tiles leave the chip under-filled (auto, 0)
-    const int tn64 = (p.N + 63) / 64;
-    const bool narrow = g_ring_tn == 32 || (g_ring_tn == 0 && tm * tn64 * p.splits < g_ring_fill);
-    if (narrow && (p.N % 32) == 0) {
-      const int tn = (p.N + 31) / 32;
-      if (tm * tn * p.splits <= 2L * g_tiled3_max_blocks) {  // long: the tests' "no cap" is 1 << 30
-        LSD_LAUNCH("ring<3,32>", (gemm_ring_kernel<EPI, 3, 32>), dim3(tm * tn * p.splits), dim3(256), 0, st, p, tm, tn);
-        return hipGetLastError();
-      }
-    }
-    // 96-row tiles above 128 rows while 3 x the column tiles fit one round
-    // on the chip (GPT-2 XL QKV at 256 rows: 225 workgroups of 512 KB of
-    // operand traffic instead of 150 of 614 KB; the ring GEMMs are bound by
-    // L2 -> CU bytes per workgroup, profiles/r2_decode_gemm_limits.log).
-    // Alone 10-12 % faster (QKV 16.3 -> 14.7 us at 256 rows, MLP-up 17.1 ->
-    // 15.0 at 192), but beside the other microbatch lane the extra
-    // workgroups cost more than they save (bench: 384 sequences -1 to -1.4 %,
-    // 512 within +-0.5 %; profiles/r2_ring_m96.log) -- off by default.
-    if (p.splits == 1 && p.M > TBM && g_ring_m96 > 0) {
-      const int tm96 = (p.M + 95) / 96;
-      if (tm96 * tn64 <= g_ring_m96) {
-        LSD_LAUNCH("ring<3,64,m96>", (gemm_ring_kernel<EPI, 3, 64, 3>), dim3(tm96 * tn64), dim3(256), 0, st, p, tm96, tn64);
-        return hipGetLastError();
-      }
-    }
-    if (tm * tn64 * p.splits <= g_tiled3_max_blocks) {
-      const dim3 g8(tm * tn64 * p.splits), b8(512);
-      const int rot = (g_ring8_flags & 1) != 0;
-      const bool combine = p.splits > 1 && EPI != EPI_SLAB;
-      if (combine && (g_ring8 != 2 || cnt == nullptr || ws == nullptr)) return hipErrorInvalidValue;
-      if (g_ring8 == 1)
-        LSD_LAUNCH("ring8<1,3>", (gemm_ring8_kernel<EPI, 1, 3>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
-      else if (g_ring8 == 2 && g_ring8_pack == 1)
-        LSD_LAUNCH("ring8<2,3,pk1>", (gemm_ring8_kernel<EPI, 2, 3, 0, 1>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
-      else if (g_ring8 == 2 && g_ring8_pack == 2)
-        LSD_LAUNCH("ring8<2,3,pk2>", (gemm_ring8_kernel<EPI, 2, 3, 0, 2>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
-      else if (g_ring8 == 2 && g_ring8_pack == 3)
-        LSD_LAUNCH("ring8<2,3,pk3>", (gemm_ring8_kernel<EPI, 2, 3, 0, 3>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
-      else if (g_ring8 == 2 && (g_ring8_flags & 4))
-        LSD_LAUNCH("ring8<2,3,bl>", (gemm_ring8_kernel<EPI, 2, 3, 0, 0, true>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
-      else if (g_ring8 == 2 && (g_ring8_flags & 2))
-        LSD_LAUNCH("ring8<2,3,nt>", (gemm_ring8_kernel<EPI, 2, 3, 1>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
-      else if (g_ring8 == 2)
-        LSD_LAUNCH("ring8<2,3>", (gemm_ring8_kernel<EPI, 2, 3>), g8, b8, 0, st, p, tm, tn64, rot, cnt, ws);
-      else
-        LSD_LAUNCH("ring<3,64>", (gemm_ring_kernel<EPI, 3, 64>), dim3(tm * tn64 * p.splits), dim3(256), 0, st, p, tm, tn64);
-      return hipGetLastError();
-    }
-  }
-  const int tn = (p.N + TBN - 1) / TBN;
-  dim3 grid(tm * tn * p.splits), block(256);
-  // the cap counts 128x64 tiles whatever LSD_RING_TN says: a 128x128 ring
-  // grid gets half as many workgroups (vocab-wide lm_head grids stay on the
-  // 2-blocks/CU kernel; profiles/r1_ab_ring_n64.log)
-  const int cap128 = g_tiled3_max_blocks / 2;
-  if (tm * tn * p.splits <= cap128 && g_ring_slots == 4)
-    LSD_LAUNCH("ring<4,128>", (gemm_ring_kernel<EPI, 4, 128>), grid, block, 0, st, p, tm, tn);
-  else if (tm * tn * p.splits <= cap128)
-    LSD_LAUNCH("ring<3,128>", (gemm_ring_kernel<EPI, 3, 128>), grid, block, 0, st, p, tm, tn);
-  else
-    LSD_LAUNCH("tiled", (gemm_tiled_kernel<EPI>), grid, block, 0, st, p, tm, tn);
-  return hipGetLastError();
+  return hipErrorInvalidValue;  // selectors that name no instance: not a plan_gemm() result
 }
 
 }  // namespace lsd
 
 using namespace lsd;
 
+static GemmTuning g_tuning;
+
 extern "C" const char* lsd_gemm_last_launch() { return g_last_launch; }
-extern "C" void lsd_gemm_set_big_min(int v) { g_big_min_blocks = v; }
-extern "C" void lsd_gemm_set_big_group(int v) { g_big_group = v < 0 ? 0 : v; }
-extern "C" void lsd_gemm_set_big_kind(int v) { g_big_kind = (v == 1 || v == 4) ? v : 0; }
-extern "C" void lsd_gemm_set_tiled3_max(int v) { g_tiled3_max_blocks = v; }
-extern "C" void lsd_gemm_set_ring_slots(int v) { g_ring_slots = v == 4 ? 4 : 3; }
-extern "C" void lsd_gemm_set_ring_tn(int v) { g_ring_tn = (v == 64 || v == 32 || v == 0) ? v : 128; }
-extern "C" void lsd_gemm_set_ring_fill(int v) { g_ring_fill = v; }
-extern "C" void lsd_gemm_set_ring_m96(int v) { g_ring_m96 = v; }
-extern "C" void lsd_gemm_set_ring8(int v) { g_ring8 = (v == 1 || v == 2) ? v : 0; }
-extern "C" void lsd_gemm_set_ring8_flags(int v) { g_ring8_flags = v & 7; }
-extern "C" void lsd_gemm_set_ring8_pack(int v) { g_ring8_pack = v & 3; }
-extern "C" void lsd_gemm_set_d256_slots(int v) { g_d256_slots = v < 2 ? 2 : (v > 4 ? 4 : v); }
+extern "C" void lsd_gemm_set_big_min(int v) { g_tuning.big_min_blocks = v; }
+extern "C" void lsd_gemm_set_big_group(int v) { g_tuning.set_big_group(v); }
+extern "C" void lsd_gemm_set_big_kind(int v) { g_tuning.set_big_kind(v); }
+extern "C" void lsd_gemm_set_tiled3_max(int v) { g_tuning.tiled3_max_blocks = v; }
+extern "C" void lsd_gemm_set_ring_slots(int v) { g_tuning.set_ring_slots(v); }
+extern "C" void lsd_gemm_set_ring_tn(int v) { g_tuning.set_ring_tn(v); }
+extern "C" void lsd_gemm_set_ring_fill(int v) { g_tuning.ring_fill = v; }
+extern "C" void lsd_gemm_set_ring_m96(int v) { g_tuning.ring_m96 = v; }
+extern "C" void lsd_gemm_set_ring8(int v) { g_tuning.set_ring8(v); }
+extern "C" void lsd_gemm_set_ring8_flags(int v) { g_tuning.set_ring8_flags(v); }
+extern "C" void lsd_gemm_set_ring8_pack(int v) { g_tuning.set_ring8_pack(v); }
+extern "C" void lsd_gemm_set_d256_slots(int v) { g_tuning.set_d256_slots(v); }
+extern "C" void lsd_gemm_set_nw2_rows(int v) { g_tuning.nw2_rows = v; }
+extern "C" void lsd_gemm_set_sk_rows(int v) { g_tuning.set_sk_rows(v); }
 
-// columns per gemm_d256 tile of a launch of this kind (0: not a d256 launch):
-// the split workspace and ticket counters are sized from it (bindings.cpp)
-extern "C" int lsd_gemm_d256_bn(int kind, int M, int N, int K) { return d256_bn(kind, M, N, K); }
-// 128x64 tiles of a tiled (kind 1) launch when it runs on gemm_ring8_kernel
-// (mirrors launch_tiled), else 0: the split workspace / counters are sized from it
+// The launch of this shape under the tuning as it is now (one snapshot: a
+// setter call after this does not reach a plan already made).
+extern "C" void lsd_gemm_plan(int M, int N, int K, int splits, int epi, int kind, GemmPlan* out) {
+  const GemmTuning t = g_tuning;
+  *out = plan_gemm(M, N, K, splits, epi, kind, t);
+}
+
+// Queries for tests and tools, 0 where no such launch exists: columns per
+// gemm_d256 tile of a kind 2 / 3 launch; 128x64 tiles of a tiled (kind 1)
+// launch that runs on the all-compute gemm_ring8_kernel; row blocks and
+// 64-column tiles per workgroup of a split-K (kind 0) launch.
+static GemmPlan query(int M, int N, int K, int S, int epi, int kind) {
+  GemmPlan pl;
+  lsd_gemm_plan(M, N, K, S, epi, kind, &pl);
+  return pl;
+}
+extern "C" int lsd_gemm_d256_bn(int kind, int M, int N, int K) {
+  const GemmPlan pl = query(M, N, K, 1, EPI_BF16, kind);
+  return pl.valid && pl.kernel == GK_D256 ? pl.tn : 0;
+}
 extern "C" int lsd_gemm_ring8_tiles(int M, int N, int K, int S) {
-  if (g_ring8 != 2) return 0;
-  const int bm = (M + GBM - 1) / GBM, bn = (N + GBN - 1) / GBN;
-  if (M >= GBM && K % 64 == 0 && bm * bn * S >= g_big_min_blocks) return 0;
-  if (!(g_ring_tn == 64 || g_ring_tn == 32 || g_ring_tn == 0)) return 0;
-  const int tm = (M + TBM - 1) / TBM, tn64 = (N + 63) / 64;
-  const bool narrow = g_ring_tn == 32 || (g_ring_tn == 0 && tm * tn64 * S < g_ring_fill);
-  if (narrow && (N % 32) == 0 && tm * ((N + 31) / 32) * S <= 2L * g_tiled3_max_blocks) return 0;
-  if (S == 1 && M > TBM && g_ring_m96 > 0 && ((M + 95) / 96) * tn64 <= g_ring_m96) return 0;
-  return tm * tn64 * S <= g_tiled3_max_blocks ? tm * tn64 : 0;
+  const GemmPlan pl = query(M, N, K, S, EPI_BF16, 1);
+  return pl.valid && pl.kernel == GK_RING8 && pl.var == 2 ? pl.tiles_m * pl.tiles_n : 0;
 }
-extern "C" int lsd_gemm_sk_rblocks(int M, int N, int S) { return sk_rblocks(M, N, S); }
-extern "C" int lsd_gemm_sk_rows(int M, int N, int S) {  // rows per row block
-  return sk_mt(M, sk_rblocks(M, N, S)) * 16;
+extern "C" int lsd_gemm_sk_rblocks(int M, int N, int S) {
+  const GemmPlan pl = query(M, N, 32, S, EPI_BF16, 0);
+  return pl.valid ? (int)pl.grid[2] : 0;
 }
-extern "C" int lsd_gemm_sk_nw(int M, int epi) { return sk_nw(M, epi); }
-extern "C" void lsd_gemm_set_nw2_rows(int v) { g_nw2_rows = v; }
-extern "C" void lsd_gemm_set_sk_rows(int v) { g_sk_rows = v < 16 ? 16 : (v > 128 ? 128 : v); }
+extern "C" int lsd_gemm_sk_nw(int M, int epi) { return query(M, 128, 32, 1, epi, 0).nw; }
 
-// C ABI used by csrc/bindings.cpp; shapes are validated there.
-extern "C" hipError_t lsd_gemm(const GemmParams* p, int epi, int kind, int* cnt, float* ws,
-                               hipStream_t st) {
-#define LSD_DISPATCH(E)                                                                   \
-  case E:                                                                                 \
-    return kind >= 2 ? launch_d256<E>(*p, kind, cnt, ws, st)                              \
-                     : (kind ? launch_tiled<E>(*p, cnt, ws, st) : launch_sk<E>(*p, cnt, ws, st));
-  switch (epi) {
-    LSD_DISPATCH(EPI_BF16)
-    LSD_DISPATCH(EPI_GELU)
-    LSD_DISPATCH(EPI_SILU_MUL)
-    LSD_DISPATCH(EPI_F32)
-    LSD_DISPATCH(EPI_RESID)
-    LSD_DISPATCH(EPI_QKV)
-    LSD_DISPATCH(EPI_SLAB)
+// C ABI used by csrc/bindings.cpp, which validates shapes and pointers and
+// sizes cnt / ws from the same plan: launch it.
+extern "C" hipError_t lsd_gemm(const GemmParams* p, const GemmPlan* plan, int* cnt, float* ws, hipStream_t st) {
+  const GemmPlan& pl = *plan;
+  if (!pl.valid || pl.M != p->M || pl.N != p->N || pl.K != p->K || pl.splits != p->splits) return hipErrorInvalidValue;
+  if (pl.combine_tiles > 0 && (cnt == nullptr || ws == nullptr)) return hipErrorInvalidValue;
+  switch (pl.epi) {
+    case EPI_BF16: return launch_plan<EPI_BF16>(*p, pl, cnt, ws, st);
+    case EPI_GELU: return launch_plan<EPI_GELU>(*p, pl, cnt, ws, st);
+    case EPI_SILU_MUL: return launch_plan<EPI_SILU_MUL>(*p, pl, cnt, ws, st);
+    case EPI_F32: return launch_plan<EPI_F32>(*p, pl, cnt, ws, st);
+    case EPI_RESID: return launch_plan<EPI_RESID>(*p, pl, cnt, ws, st);
+    case EPI_QKV: return launch_plan<EPI_QKV>(*p, pl, cnt, ws, st);
+    case EPI_SLAB: return launch_plan<EPI_SLAB>(*p, pl, cnt, ws, st);
     default: return hipErrorInvalidValue;
   }
-#undef LSD_DISPATCH
 }
+

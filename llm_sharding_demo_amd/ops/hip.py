@@ -99,7 +99,7 @@ class LazyNorm:
         return 2 if self.rms else 1
 
 
-# gemv epilogue codes (csrc/kernels/gemm.hip Epi)
+# gemv epilogue codes (csrc/kernels/gemm_plan.h Epi)
 _EPI = {"none": 0, "gelu": 1, "silu_mul": 2}
 EPI_F32, EPI_RESID, EPI_QKV = 3, 4, 6
 # longest row the sampler loads once into registers (sample.hip: CH x NT x 4)

@@ -106,7 +106,7 @@ class Routing:
     d256_rb_max_m: int = 512
     d256_rb_max_n: int = 8192
     # the 256x256 pipelined kernel (gemm_p8) once a tiled launch has this
-    # many 256x256 tiles; the 128x128 kernels below (launch_tiled in gemm.hip)
+    # many 256x256 tiles; the 128x128 kernels below (plan_gemm() in csrc/kernels/gemm_plan.h)
     big_min_blocks: int = 160
     # -- norms / head ------------------------------------------------------
     # one wave per row from norm_wave_min rows (prefill 32 K x 1600 97.7 ->
@@ -151,8 +151,9 @@ class Routing:
                 or (M > self.tiled_min_m and N >= self.tiled_min_n))
 
     def d256_bn(self, M: int, N: int, K: int) -> int:
-        """Tile columns when this GEMM runs on gemm_d256_kernel, else 0
-        (mirrors d256_bn() in gemm.hip)."""
+        """Tile columns when this GEMM is routed to gemm_d256_kernel, else 0: the
+        routing policy that picks launch kind 2 / 3.  What a kind 2 / 3 launch
+        then runs is decided in one place, plan_gemm() in csrc/kernels/gemm_plan.h."""
         if not self.d256 or K % 64 or N > 32768 or not self.tiled(M, N):
             return 0
         if 256 < M <= self.d256_rb_max_m:  # several 256-row blocks (auto only)
@@ -177,7 +178,7 @@ class Routing:
         return max(1, min(round(target / tiles), K // 64 // 2 or 1, 16))
 
     def sk_splits(self, M: int, N: int, K: int, lanes: int = 1, nw: int = 1) -> int:
-        """nw: 64-column tiles per workgroup (2 for SiLU*up: sk_nw() in gemm.hip)."""
+        """nw: 64-column tiles per workgroup (2 for SiLU*up: GemmPlan::nw, csrc/kernels/gemm_plan.h)."""
         tiles = math.ceil(N / (64 * nw))  # >= the target: never row-blocked
         target = self.sk_target or max(128, 384 // max(1, lanes))
         return max(1, min(math.ceil(target / tiles), K // 32 // self.sk_min_steps or 1))
