@@ -84,6 +84,9 @@ hipError_t lsd_penalize(float* logits, long ld, int B, int V, const int* hist, i
                         long ldseg, hipStream_t st);
 hipError_t lsd_record_tokens(int* hist, int L, int nslots, const int* slots, const long long* step, int back,
                              const int* tokens, const int* active, int B, hipStream_t st);
+hipError_t lsd_logit_edits(float* logits, long ld, int B, int V, const int* cnt, const int* tok, const float* val,
+                           const int* until, int E, int nslots, const int* slots, const long long* step,
+                           float* segmax, long ldseg, hipStream_t st);
 hipError_t lsd_logprobs(const float* logits, long ld, int B, int V, const int* tokens, const int* nlp, const int* slots,
                         const long long* step, int back, const int* active, float* lp_tok, int* lp_top_id,
                         float* lp_top, int L, int nslots, int W, hipStream_t st);
@@ -741,6 +744,50 @@ void penalize(torch::Tensor logits, int64_t V, torch::Tensor hist, torch::Tensor
                          frequency.data_ptr<float>(), sm, ldseg, cur_stream()), "penalize");
 }
 
+// Per-request logit edits (logit_edit.hip): logit_bias, banned tokens and
+// min_new_tokens.  Row i adds, in place on its fp32 logits (and repairs
+// linear_f32's segment maxima, when given), the entries [0, cnt[slots[i]]) of
+// its KV slot's table row -- tok / val / until [slots, E] -- whose `until`
+// exceeds the row's sampler counter step[i] (absent = draw 0).
+void logit_edits(torch::Tensor logits, int64_t V, torch::Tensor cnt, torch::Tensor tok, torch::Tensor val,
+                 torch::Tensor until, torch::Tensor slots, c10::optional<torch::Tensor> step,
+                 c10::optional<torch::Tensor> segmax) {
+  need(logits, torch::kFloat32, "logits");
+  need(cnt, torch::kInt32, "cnt");
+  need(tok, torch::kInt32, "tok");
+  need(val, torch::kFloat32, "val");
+  need(until, torch::kInt32, "until");
+  need(slots, torch::kInt32, "slots");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= 1 && V <= logits.size(1), "logits [B, >=V]");
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(tok.dim() == 2 && tok.is_contiguous() && val.is_contiguous() && until.is_contiguous() &&
+                  cnt.is_contiguous() && val.sizes() == tok.sizes() && until.sizes() == tok.sizes() &&
+                  cnt.dim() == 1 && cnt.size(0) == tok.size(0) && tok.size(0) >= 1,
+              "logit_edits: the table is contiguous cnt [slots], tok / val / until [slots, E]");
+  TORCH_CHECK(tok.size(1) >= 1 && tok.size(1) <= 1024,
+              "logit_edits: a table of more than 1024 entries per slot is more than the kernel's 4 trips per thread");
+  TORCH_CHECK(slots.numel() == B && slots.is_contiguous(), "logit_edits: slots must be contiguous [B]");
+  const long long* sp = nullptr;
+  if (step.has_value()) {
+    need(*step, torch::kInt64, "step");
+    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
+    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
+  }
+  float* sm = nullptr;
+  long ldseg = 0;
+  if (segmax.has_value()) {
+    need(*segmax, torch::kFloat32, "segmax");
+    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && logits.size(1) % 8 == 0 &&
+                    logits.stride(0) % 8 == 0 && segmax->size(1) == logits.size(1) / 8,
+                "segmax must be fp32 [B, logits row length / 8] (row length % 8 == 0)");
+    sm = segmax->data_ptr<float>();
+    ldseg = segmax->stride(0);
+  }
+  check_hip(lsd_logit_edits(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V, cnt.data_ptr<int>(),
+                            tok.data_ptr<int>(), val.data_ptr<float>(), until.data_ptr<int>(), (int)tok.size(1),
+                            (int)tok.size(0), slots.data_ptr<int>(), sp, sm, ldseg, cur_stream()), "logit_edits");
+}
+
 // hist[slots[i], step[i] - back] = tokens[i] for active rows (all rows without
 // `active`); step absent = entry 0 (the prefill draw).  back = 1 after
 // sample_into, which has already advanced the counters.
@@ -890,6 +937,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("apply_rows", &apply_rows, py::arg("args"), py::arg("b"));
   m.def("penalize", &penalize, py::arg("logits"), py::arg("V"), py::arg("hist"), py::arg("slots"),
         py::arg("counts"), py::arg("presence"), py::arg("frequency"), py::arg("segmax") = py::none());
+  m.def("logit_edits", &logit_edits, py::arg("logits"), py::arg("V"), py::arg("cnt"), py::arg("tok"), py::arg("val"),
+        py::arg("until"), py::arg("slots"), py::arg("step") = py::none(), py::arg("segmax") = py::none());
   m.def("record_tokens", &record_tokens, py::arg("hist"), py::arg("slots"), py::arg("step"), py::arg("tokens"),
         py::arg("active") = py::none(), py::arg("back") = 0);
   m.def("logprobs", &logprobs, py::arg("logits"), py::arg("V"), py::arg("tokens"), py::arg("nlp"), py::arg("slots"),

@@ -14,9 +14,10 @@ from __future__ import annotations
 
 import dataclasses
 import math
+import operator
 import os
 from dataclasses import dataclass, field
-from typing import Optional, Sequence
+from typing import Mapping, Optional, Sequence
 
 
 # ---------------------------------------------------------------------------
@@ -174,6 +175,26 @@ def model_config_from_hf_json(path: str) -> ModelConfig:
 # ---------------------------------------------------------------------------
 
 MAX_LOGPROBS_CEILING = 20  # alternatives per token the logprob kernel's record can hold
+MAX_LOGIT_EDITS_CEILING = 1024  # entries per request the logit-edit kernel's 256 threads visit in 4 trips
+INT32_MAX = 2 ** 31 - 1
+
+
+def _fp32(v) -> float:
+    import struct
+
+    return struct.unpack("f", struct.pack("f", float(v)))[0]
+
+
+def _token_id(t) -> int:
+    """A token id given as an int or, as JSON object keys arrive, a decimal string."""
+    try:
+        if isinstance(t, str) and t.strip().lstrip("+-").isdecimal():
+            return int(t)
+        if not isinstance(t, (bool, str)):
+            return operator.index(t)
+    except (TypeError, ValueError):
+        pass
+    raise ValueError(f"token ids must be integers (or decimal strings), got {t!r}")
 
 
 @dataclass
@@ -207,7 +228,26 @@ class SamplingParams:
     bit-equal to that entry's; a -inf logit has logprob -inf; a vocabulary of
     fewer than n tokens pads with id -1 and -inf (trimmed from
     Request.logprobs).  Asking never changes a draw: the same seed gives the
-    same tokens with and without."""
+    same tokens with and without.
+
+    logit_bias / banned_token_ids / min_new_tokens edit the row's fp32 logits
+    before every draw: each entry is logit[t] <- logit[t] + v, one rounding per
+    addition, applied after the presence / frequency penalties and ahead of
+    temperature, top-k, top-p, min-p and the greedy argmax -- greedy requests
+    are edited too.  logit_bias maps token ids (ints, or decimal strings as
+    JSON gives them) to finite values in [-100, 100]; banned_token_ids can
+    never be drawn (v = -inf; duplicates collapse; a token both biased and
+    banned is banned); min_new_tokens = m keeps the model's EOS token from
+    being drawn in the first m draws (the prefill draw is draw 0; 0 <= m <=
+    max_new_tokens), whether or not stop_at_eos is set: the entry (eos, -inf)
+    holds while the draw's sampler counter is below m, every other entry for
+    good.  A request's entries -- the distinct tokens of logit_bias and
+    banned_token_ids, plus one with min_new_tokens > 0 -- number at most
+    EngineConfig.max_logit_edits; the ids must lie in the vocabulary and some
+    token must stay drawable.  All three default to off (None / None / 0), and
+    such a request runs nothing extra.  Logprobs are taken after the edits (a
+    banned token has logprob -inf), and asking for edits never changes
+    another request's draws."""
 
     temperature: float = 0.6
     top_k: int = 40
@@ -220,10 +260,62 @@ class SamplingParams:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     logprobs: Optional[int] = None
+    logit_bias: Optional[Mapping[int, float]] = None
+    banned_token_ids: Optional[Sequence[int]] = None
+    min_new_tokens: int = 0
 
-    def validate(self, max_logprobs: int = MAX_LOGPROBS_CEILING) -> None:
+    @property
+    def has_logit_edits(self) -> bool:
+        return bool(self.logit_bias) or bool(self.banned_token_ids) or self.min_new_tokens != 0
+
+    def logit_edits(self, eos: int) -> Optional[tuple]:
+        """The request's edit entries as (tokens, values, untils), sorted by
+        token (a token's permanent entry ahead of the min_new_tokens one), or
+        None without any: what the last stage's table holds for its KV slot.
+        Values are rounded to fp32 here; a ban is -inf, `until` INT32_MAX for
+        a permanent entry and min_new_tokens for the EOS one."""
+        if not self.has_logit_edits:
+            return None
+        ent = {}
+        for t, v in (self.logit_bias or {}).items():
+            t = _token_id(t)
+            if t in ent:
+                raise ValueError(f"logit_bias names token {t} twice")
+            ent[t] = _fp32(v)
+        for t in self.banned_token_ids or ():
+            ent[_token_id(t)] = -math.inf
+        rows = [(t, v, INT32_MAX) for t, v in ent.items()]
+        if self.min_new_tokens > 0:
+            rows.append((int(eos), -math.inf, int(self.min_new_tokens)))
+        rows.sort(key=lambda r: (r[0], -r[2]))
+        return tuple(zip(*rows)) if rows else None
+
+    def validate(self, max_logprobs: int = MAX_LOGPROBS_CEILING, max_logit_edits: int = 300) -> None:
         if self.max_new_tokens < 0:
             raise ValueError("max_new_tokens must be >= 0")
+        m = self.min_new_tokens
+        if isinstance(m, bool) or not isinstance(m, int) or not (0 <= m <= self.max_new_tokens):
+            raise ValueError("min_new_tokens must be an integer in [0, max_new_tokens]")
+        if self.logit_bias is not None or self.banned_token_ids is not None:
+            if self.logit_bias is not None and not isinstance(self.logit_bias, Mapping):
+                raise ValueError("logit_bias must map token ids to values")
+            if isinstance(self.banned_token_ids, (str, bytes, Mapping)):
+                raise ValueError("banned_token_ids must be a sequence of token ids")
+            for v in (self.logit_bias or {}).values():
+                if (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v)
+                        or not -100.0 <= v <= 100.0):
+                    raise ValueError("logit_bias values must be finite and in [-100, 100]")
+            try:
+                toks = set(map(_token_id, self.logit_bias or ())) | set(map(_token_id, self.banned_token_ids or ()))
+            except TypeError:
+                raise ValueError("banned_token_ids must be a sequence of token ids") from None
+            if len(toks) < len(self.logit_bias or ()):
+                raise ValueError("logit_bias names a token twice")
+            if any(t < 0 or t > INT32_MAX for t in toks):
+                raise ValueError("token ids must be >= 0")
+            if len(toks) + (m > 0) > max_logit_edits:
+                raise ValueError(f"logit_bias, banned_token_ids and min_new_tokens make {len(toks) + (m > 0)} "
+                                 f"entries; at most {max_logit_edits} (max_logit_edits)")
         if self.logprobs is not None:
             n = self.logprobs
             if isinstance(n, bool) or not isinstance(n, int) or not (0 <= n <= max_logprobs):
@@ -332,10 +424,17 @@ class EngineConfig:
     # sizes the last stage's logprob records, slots x max_seq x (4 + 8 W) bytes,
     # allocated when the first such request arrives.  At most 20.
     max_logprobs: int = 5
+    # Most logit-edit entries a request may carry (SamplingParams.logit_bias,
+    # banned_token_ids, min_new_tokens); sizes the last stage's edit table,
+    # slots x (4 + 12 E) bytes, allocated when the first such request arrives.
+    # At most 1024.
+    max_logit_edits: int = 300
 
     def __post_init__(self):
         if not (0 <= self.max_logprobs <= MAX_LOGPROBS_CEILING):
             raise ValueError(f"max_logprobs must be in [0, {MAX_LOGPROBS_CEILING}]")
+        if not (1 <= self.max_logit_edits <= MAX_LOGIT_EDITS_CEILING):
+            raise ValueError(f"max_logit_edits must be in [1, {MAX_LOGIT_EDITS_CEILING}]")
 
     @property
     def model(self) -> ModelConfig:
@@ -370,6 +469,7 @@ class EngineConfig:
             kv_fraction=float(_env("KV_FRACTION", "0.85")),
             metrics_every=int(_env("METRICS_EVERY", "16")),
             max_logprobs=int(_env("MAX_LOGPROBS", "5")),
+            max_logit_edits=int(_env("MAX_LOGIT_EDITS", "300")),
         )
         if cfg.split_points and cfg.num_stages == 1:
             cfg.num_stages = len(cfg.split_points) + 1

@@ -123,6 +123,12 @@ class ReferenceBackend(Backend):
         histories, in place on the fp32 logits, ahead of the sampler."""
         ref.penalize(logits, hist, slots, counts, presence, frequency, vocab)
 
+    def logit_edits(self, logits, table, slots, step, vocab: int) -> None:
+        """The rows' logit_bias / ban / min_new_tokens entries (table = the
+        last stage's per-slot cnt, tok, val, until), in place on the fp32
+        logits, after the penalties and ahead of the sampler; step None = draw 0."""
+        ref.logit_edits(logits, table, slots, step, vocab)
+
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         ref.record_tokens(hist, slots, step, tokens, active, back)
 

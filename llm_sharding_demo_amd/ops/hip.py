@@ -380,6 +380,12 @@ class HipBackend(Backend):
         self.C.penalize(logits, vocab, hist, slots, counts, presence, frequency,
                         getattr(logits, "_lsd_segmax", None))
 
+    def logit_edits(self, logits, table, slots, step, vocab: int) -> None:
+        # logit_edit.hip: one workgroup per row, ahead of the draw; rows whose
+        # slot has no entry return at once; the segment maxima are repaired too
+        self.C.logit_edits(logits, vocab, table[0], table[1], table[2], table[3], slots, step,
+                           getattr(logits, "_lsd_segmax", None))
+
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         self.C.record_tokens(hist, slots, step, tokens, active, back)
 

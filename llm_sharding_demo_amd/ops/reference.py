@@ -158,6 +158,51 @@ def penalize(logits: torch.Tensor, hist: torch.Tensor, slots: torch.Tensor, coun
     return logits if segmax is None else (logits, segmax)
 
 
+def logit_edits(logits: torch.Tensor, table, slots: torch.Tensor, step: Optional[torch.Tensor], vocab: int,
+                segmax: Optional[torch.Tensor] = None):
+    """Per-request logit edits (logit_bias, banned tokens, min_new_tokens),
+    after `penalize` and ahead of `sample`.
+
+    table = (cnt [slots] int, tok [slots, E] int, val [slots, E] fp32, until
+    [slots, E] int): row r reads entries [0, cnt[s]) of its KV slot s =
+    slots[r], sorted by token.  With c = step[r], the row's sampler counter
+    before the draw (step None: c = 0, the prefill draw), every entry with
+    c < until is active and does
+        logit[tok] <- logit[tok] + val
+    in fp32, one rounding per addition, the entries of one token in table
+    order (a ban is val = -inf; a permanent entry has until = INT32_MAX).
+    Rows whose slot has no entry are untouched, as is a token none of whose
+    entries is active; entries with a token outside [0, vocab) are ignored.
+
+    fp32 `logits` [B, >= vocab] are rewritten in place and returned.  With
+    `segmax` [B, width / 8] (linear_f32's 8-logit segment maxima, padding
+    columns included) the maximum of every segment holding an edited token is
+    recomputed from its 8 stored logits in place too, and (logits, segmax) is
+    returned.
+    """
+    assert logits.dtype == torch.float32, "logit_edits rewrites fp32 logits in place"
+    cnt, tok, val, until = table
+    E = tok.shape[1]
+    for r in range(logits.shape[0]):
+        s = int(slots[r])
+        if not 0 <= s < cnt.shape[0]:
+            continue
+        n = min(int(cnt[s]), E)
+        c = int(step[r]) if step is not None else 0
+        touched = []
+        for e in range(n):
+            t = int(tok[s, e])
+            if not (0 <= t < vocab and c < int(until[s, e])):
+                continue
+            logits[r, t] = logits[r, t] + val[s, e].float()  # fp32 + fp32: one rounding
+            touched.append(t // 8)
+        if segmax is not None and touched:
+            segs = torch.unique(torch.tensor(touched))
+            idx = segs[:, None] * 8 + torch.arange(8)
+            segmax[r, segs] = logits[r][idx].max(dim=1).values
+    return logits if segmax is None else (logits, segmax)
+
+
 def record_tokens(hist: torch.Tensor, slots: torch.Tensor, step: Optional[torch.Tensor], tokens: torch.Tensor,
                   active: Optional[torch.Tensor] = None, back: int = 0) -> None:
     """hist[slots[i], step[i] - back] = tokens[i] for active rows (all rows

@@ -43,8 +43,8 @@ import torch
 
 from ..models.stage import StageModel
 from ..runtime.batch import BatchMeta, MixedMeta, SamplingState
-from ..runtime.plan import (NO_FEATURES, ROW_FIELDS, GroupPlan, StepPlan, device_fields, pack_rows, packed_size,
-                            row_features)
+from ..runtime.plan import (NO_FEATURES, ROW_FIELDS, GroupPlan, StepPlan, device_fields, has_edits, pack_rows,
+                            packed_size, row_features)
 from ..utils.tracing import trace_range
 from ..utils import racecheck
 from .comm import Handle, SendHandle, Transport
@@ -201,6 +201,11 @@ class GroupState(racecheck.Shared):
         # penalty (penalize and record_tokens run around the sampler), one that
         # asked for logprobs (the logprob kernel runs after the sampler)
         self.cut = self.pen = self.lp = False
+        # a row with logit edits (plan.has_edits): the edit pass runs ahead of
+        # the sampler.  A flag beside the triple -- it adds no row vector, so the
+        # packed row state and apply_rows' record do not depend on it -- and the
+        # last part of the decode graphs' key
+        self.edit = False
         if w.last:
             for f in ROW_FIELDS:  # the sampler's row vectors, idle: temp, topk, greedy, seeds, sstep, ...
                 setattr(self, f.vec, torch.full((cap,), f.idle, dtype=getattr(torch, f.dtype), device=dev))
@@ -428,6 +433,14 @@ class StageWorker(racecheck.Shared):
         self.lp_rec: Optional[tuple] = None
         self.max_logprobs = 5
         self.logprob_launches = 0
+        # last stage: logit edits per KV slot (_edit_tab: allocated when the
+        # first request with logit_bias / banned tokens / min_new_tokens
+        # arrives) -- (cnt [slots] int32, tok [slots, E] int32, val [slots, E]
+        # fp32, until [slots, E] int32), E = max_logit_edits -- and the items
+        # whose sampler ran behind the edit pass
+        self.edit_tab: Optional[tuple] = None
+        self.max_logit_edits = 300
+        self.logit_edit_launches = 0
 
     # ------------------------------------------------------------------
     def configure(self, groups: int, cap: int) -> None:
@@ -710,6 +723,8 @@ class StageWorker(racecheck.Shared):
                     self.penalty_launches += 1
                 if gs.lp:
                     self.logprob_launches += 1
+                if gs.edit:
+                    self.logit_edit_launches += 1
                 rows.append(d)
             try:
                 with (self.t.issuing() if self.t is not None else contextlib.nullcontext()):
@@ -943,37 +958,45 @@ class StageWorker(racecheck.Shared):
             self.penalty_launches += 1
         if gs.lp:
             self.logprob_launches += 1
+        if gs.edit:
+            self.logit_edit_launches += 1
         if J:
             lf = logits[b:]
             if seg is not None:
                 lf._lsd_segmax = seg[b:]
             fc = [ch[i] for i in finals]
+            self._edit_finals(gs, fc, lf)
             ids = be.sample(lf, SamplingState.of(fc, dev), V)
             self._record_finals(fc, ids, lf)
             gs.tokret[b: b + J].copy_(ids)
         self.mixed_items += 1
 
     def _features(self, gp: GroupPlan, gs: GroupState) -> tuple:
-        """(cut, pen, lp) of the group once this item ran: the current ones, or
-        those of the item's new composition -- one pass over its rows, kept
-        with the plan item, so whichever path runs it reads the same triple."""
+        """(cut, pen, lp, edit) of the group once this item ran: the current
+        ones, or those of the item's new composition -- one pass over its rows,
+        kept with the plan item, so whichever path runs it reads the same four."""
         if gp.rows is None:
-            return gs.cut, gs.pen, gs.lp
+            return gs.cut, gs.pen, gs.lp, gs.edit
         if not self.last:
-            return NO_FEATURES
+            return NO_FEATURES + (False,)
         if gp.feats is None:
             gp.feats = row_features(gp.rows)
-        return gp.feats
+        if gp.edit is None:
+            gp.edit = has_edits(gp.rows)
+        return gp.feats + (gp.edit,)
 
     def _set_features(self, gs: GroupState, feats: tuple) -> None:
         """A composition change is being applied: the group's features from
-        now on, and what they need -- the token history, the logprob records --
-        allocated here, on the host side of the change (never inside a capture)."""
-        gs.cut, gs.pen, gs.lp = feats
+        now on, and what they need -- the token history, the logprob records,
+        the edit table -- allocated here, on the host side of the change (never
+        inside a capture)."""
+        gs.cut, gs.pen, gs.lp, gs.edit = feats
         if gs.pen:
             self._hist()
         if gs.lp:
             self._lp_rec()
+        if gs.edit:
+            self._edit_tab()
 
     def _apply_rows(self, gp: GroupPlan, gs: GroupState) -> None:
         """New composition: rows [0, n) from the plan, pad rows [n, b) idle on
@@ -1067,14 +1090,20 @@ class StageWorker(racecheck.Shared):
         """Decode rows of a group: draw into the token-return vector, advance
         the sampler counters and positions.  A composition with a penalised
         row runs lm_head, penalize, sample_into, record_tokens; any other the
-        sampler alone, as before.  A composition with a logprob row then runs
-        the logprob kernel over the logits the sampler drew from."""
+        sampler alone, as before.  A composition with an edited row runs the
+        edit pass right ahead of the sampler (after the penalties; the counters
+        it compares are the ones the draw uses).  A composition with a logprob
+        row then runs the logprob kernel over the logits the sampler drew from."""
         be, V = self.stage.backend, self.stage.cfg.vocab_size
         if not gs.pen:
+            if gs.edit:
+                be.logit_edits(logits, self.edit_tab, gs.slots[:b], gs.sstep[:b], V)
             be.sample_into(logits, gs.samp(b), V, gs.tokret[:b], meta)
         else:
             hist = self.pen_hist
             be.penalize(logits, hist, gs.slots[:b], gs.sstep[:b], gs.presence[:b], gs.frequency[:b], V)
+            if gs.edit:
+                be.logit_edits(logits, self.edit_tab, gs.slots[:b], gs.sstep[:b], V)
             be.sample_into(logits, gs.samp(b), V, gs.tokret[:b], meta)
             # the sampler has advanced the counters: the draw used counter - 1
             be.record_tokens(hist, gs.slots[:b], gs.sstep[:b], gs.tokret[:b], gs.active[:b], 1)
@@ -1101,6 +1130,76 @@ class StageWorker(racecheck.Shared):
             self.stage.backend.logprobs(logits, ids, nlp, slots, None, None, self._lp_rec(),
                                         self.stage.cfg.vocab_size, 0)
             self.logprob_launches += 1
+
+    def _edit_tab(self) -> tuple:
+        """Logit-edit table of the last stage: (cnt [KV slots, scratch and
+        compat included] int32, tok [.., E] int32, val [.., E] fp32, until
+        [.., E] int32), E = max_logit_edits.  Unlike the history and the
+        logprob records its stale contents ARE read: a group whose rows joined
+        before the table existed runs the edit pass once a row with edits joins
+        it, and reads its other rows' counts.  So the counts start at zero, and
+        visibly to every lane: this thread waits for the fill before anything
+        that reads the table can be enqueued, on this lane or another (_hist:
+        a fill merely enqueued here could land after another lane's reader).
+        Allocated once, outside any capture, and never reallocated: captured
+        graphs hold its addresses.  From then on every final chunk writes its
+        slot's count (_edit_finals)."""
+        if self.edit_tab is None:
+            E = self.max_logit_edits
+            slots = max(self.scratch_slot, self.compat_slot) + 1
+            dev = self.device
+            self.edit_tab = (torch.zeros(slots, dtype=torch.int32, device=dev),
+                             torch.zeros(slots, E, dtype=torch.int32, device=dev),
+                             torch.zeros(slots, E, dtype=torch.float32, device=dev),
+                             torch.zeros(slots, E, dtype=torch.int32, device=dev))
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()
+        return self.edit_tab
+
+    def _edit_finals(self, gs: GroupState, fc, logits: torch.Tensor) -> None:
+        """Ahead of the first draw (draw 0) of the final chunks `fc`: their
+        logit edits into their KV slots' table rows, and the edit pass over
+        `logits`, the rows they are drawn from.  Eager, on the item's lane,
+        outside any graph.  Nothing without a table and without edits; once
+        the table exists every final chunk writes its slot's count, zero
+        included -- a request that reuses a slot must not inherit its
+        predecessor's entries.  One host-to-device copy through the group's
+        pinned staging ring: [slots J | counts J | flat table index n | tokens
+        n | value bits n | untils n]."""
+        ed = has_edits(fc)
+        if not ed and self.edit_tab is None:
+            return
+        cnt, tok, val, until = self._edit_tab()
+        E, J = tok.shape[1], len(fc)
+        ent = [c.edits if c.nedits else None for c in fc]
+        if any(c.nedits and (e is None or len(e[0]) != c.nedits or c.nedits > E) for c, e in zip(fc, ent)):
+            raise ValueError(f"a final chunk's logit edits are missing or exceed max_logit_edits = {E}")
+        n = sum(c.nedits for c in fc)
+        arr = np.empty(2 * J + 4 * n, dtype=np.int32)
+        arr[:J] = [c.slot for c in fc]
+        arr[J: 2 * J] = [c.nedits for c in fc]
+        if n:
+            o = 2 * J
+            arr[o: o + n] = np.concatenate([c.slot * E + np.arange(c.nedits) for c in fc if c.nedits])
+            arr[o + n: o + 2 * n] = [t for e in ent if e for t in e[0]]
+            arr[o + 2 * n: o + 3 * n] = np.array([v for e in ent if e for v in e[1]], dtype=np.float32).view(np.int32)
+            arr[o + 3 * n: o + 4 * n] = [u for e in ent if e for u in e[2]]
+        if self.device.type == "cuda":
+            buf = torch.empty(arr.size, dtype=torch.int32, device=self.device)
+            self._stage_h2d(gs, arr, buf)
+        else:
+            buf = torch.from_numpy(arr)
+        slots = buf[:J]
+        cnt.index_copy_(0, slots.long(), buf[J: 2 * J])
+        if n:
+            o = 2 * J
+            at = buf[o: o + n].long()
+            tok.view(-1).index_copy_(0, at, buf[o + n: o + 2 * n])
+            val.view(-1).index_copy_(0, at, buf[o + 2 * n: o + 3 * n].view(torch.float32))
+            until.view(-1).index_copy_(0, at, buf[o + 3 * n: o + 4 * n])
+        if ed:
+            self.stage.backend.logit_edits(logits, self.edit_tab, slots, None, self.stage.cfg.vocab_size)
+            self.logit_edit_launches += 1
 
     _ROWS_PIN = 4  # packed row-state buffers per group: reused 4 composition changes later
 
@@ -1149,6 +1248,7 @@ class StageWorker(racecheck.Shared):
             be.decode = False
             logits = st.head(x, meta, rows=rows)
         fc = [ch[i] for i in finals]
+        self._edit_finals(gs, fc, logits)
         ids = be.sample(logits, SamplingState.of(fc, dev), st.cfg.vocab_size)
         self._record_finals(fc, ids, logits)
         return ids
@@ -1267,12 +1367,14 @@ class StageWorker(racecheck.Shared):
         slot[2] = True
 
     def _decode(self, gp: GroupPlan, gs: GroupState, inp: torch.Tensor, io: bool = False) -> torch.Tensor:
-        key = (gp.b, gp.ctxb, io, gs.cut, gs.pen, gs.lp)
+        key = (gp.b, gp.ctxb, io, gs.cut, gs.pen, gs.lp, gs.edit)
         lane = self.lane_of(gp.g)
         if gs.pen:
             self.penalty_launches += 1
         if gs.lp:
             self.logprob_launches += 1
+        if gs.edit:
+            self.logit_edit_launches += 1
 
         def body():
             if io and not self.first:  # the edge receive, inside the graph

@@ -24,6 +24,7 @@ batching), so a short request finishes while a long one keeps decoding.
 """
 from __future__ import annotations
 
+import itertools
 import logging
 import os
 import queue
@@ -349,6 +350,7 @@ class Engine(racecheck.Shared):
                         wire=torch.bfloat16 if self.cfg.wire_dtype == "bf16" else None)
         w.merge_prefill = w.MERGE_PREFILL and self.cfg.merge_prefill
         w.max_logprobs = self.cfg.max_logprobs
+        w.max_logit_edits = self.cfg.max_logit_edits
         return w
 
     @property
@@ -368,7 +370,9 @@ class Engine(racecheck.Shared):
     # requests
     # ------------------------------------------------------------------
     def _validate(self, prompt: List[int], sp: SamplingParams) -> None:
-        sp.validate(self.cfg.max_logprobs)
+        sp.validate(self.cfg.max_logprobs, self.cfg.max_logit_edits)
+        if sp.has_logit_edits:
+            self._validate_edits(sp)
         if sp.logprobs is not None and self.mode == "dist":
             # the records stay on the last stage until the request finishes and
             # are read from there directly; fetching them over the control
@@ -379,6 +383,19 @@ class Engine(racecheck.Shared):
         if len(prompt) + sp.max_new_tokens > self.max_seq:
             raise ValueError(f"prompt ({len(prompt)}) + max_new_tokens ({sp.max_new_tokens}) "
                              f"exceeds the context limit {self.max_seq}")
+
+    def _validate_edits(self, sp: SamplingParams) -> None:
+        """What SamplingParams.validate cannot know: the ids of logit_bias and
+        banned_token_ids lie in the vocabulary, and the bans (the EOS of
+        min_new_tokens among them) leave a token to draw."""
+        V, eos = self.mcfg.vocab_size, self.mcfg.eos_token_id
+        for t in itertools.chain(sp.logit_bias or (), sp.banned_token_ids or ()):
+            if not 0 <= int(t) < V:
+                raise ValueError(f"logit_bias / banned_token_ids: token id {t} outside the vocabulary [0, {V})")
+        toks, vals, _ = sp.logit_edits(eos)
+        banned = {t for t, v in zip(toks, vals) if v == float("-inf") and 0 <= t < V}
+        if len(banned) >= V:
+            raise ValueError("banned_token_ids and min_new_tokens leave no token to draw")
 
     def submit(self, prompt_ids: List[int], params: SamplingParams) -> Request:
         """Thread-safe: queue one request; the driver loop admits it at the

@@ -50,6 +50,10 @@ class Chunk:
     presence: float = 0.0   # presence / frequency penalties over the generated tokens
     frequency: float = 0.0
     logprobs: int = -1      # alternatives recorded with every draw's logprob (-1: no record)
+    nedits: int = 0         # logit-edit entries of the request (logit_bias, bans, min_new_tokens)
+    # the entries, SamplingParams.logit_edits' (tokens, values, untils) sorted by
+    # token: on the final chunk only, whose stage writes them to the slot's table
+    edits: Optional[tuple] = None
 
     @property
     def qlen(self) -> int:
@@ -76,6 +80,15 @@ class Row:
     presence: float = 0.0
     frequency: float = 0.0
     logprobs: int = -1
+    nedits: int = 0     # logit-edit entries in the slot's table: the group's edit gate (has_edits)
+
+
+def has_edits(xs) -> bool:
+    """Some Row / Chunk carries logit edits: the edit pass runs ahead of the
+    draw.  A flag of its own beside row_features' triple, which keys what the
+    packed row state and apply_rows' record hold -- the edit pass adds no row
+    vector."""
+    return any(map(operator.attrgetter("nedits"), xs))
 
 
 @dataclass
@@ -92,6 +105,8 @@ class GroupPlan:
     fwd_rows: int = 0
     # row_features(rows), once a last stage has computed it (not part of the plan: never sent)
     feats: Optional[tuple] = field(default=None, compare=False, repr=False)
+    # has_edits(rows), from the scheduler or once a last stage has computed it (never sent)
+    edit: Optional[bool] = field(default=None, compare=False, repr=False)
 
     @property
     def n_final(self) -> int:
@@ -325,19 +340,61 @@ def _pack_group(gp: GroupPlan, ids: bool):
                               count=sum(len(x.ids) for x in c))
         ch = _pack_cols(c, _CHUNK_INTS) + (np.array([x.seed for x in c], dtype=np.int64), tok)
     rows = _pack_cols(gp.rows, _ROW_INTS) if gp.rows is not None else None
-    return (gp.g, gp.ret, gp.n, gp.b, gp.ctxb, gp.kind, gp.fwd_rows, ch, rows)
+    out = (gp.g, gp.ret, gp.n, gp.b, gp.ctxb, gp.kind, gp.fwd_rows, ch, rows)
+    if has_edits(gp.chunks) or (gp.rows is not None and has_edits(gp.rows)):
+        out += (_pack_edits(gp),)  # a group without edits: the 9-tuple, as before
+    return out
 
 
-def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows) -> GroupPlan:
+def _pack_edits(gp: GroupPlan) -> tuple:
+    """The logit edits of a group, the tenth element of its wire tuple: (the
+    rows' nedits column or None, the chunks' -- (nedits column, offsets [n + 1]
+    into the concatenated entries of the chunks that carry theirs (the final
+    ones), tokens int32, values float32, untils int32) -- or None)."""
+    import numpy as np
+
+    rows = np.array([r.nedits for r in gp.rows], dtype=np.int32) if gp.rows is not None else None
+    ch = None
+    if gp.chunks:
+        ed = [c.edits or ((), (), ()) for c in gp.chunks]
+        off = np.zeros(len(ed) + 1, dtype=np.int64)
+        np.cumsum([len(e[0]) for e in ed], out=off[1:])
+        tok, val, until = (np.fromiter(itertools.chain.from_iterable(e[k] for e in ed), dtype=dt, count=int(off[-1]))
+                           for k, dt in enumerate((np.int32, np.float32, np.int32)))
+        ch = (np.array([c.nedits for c in gp.chunks], dtype=np.int32), off, tok, val, until)
+    return rows, ch
+
+
+def _unpack_edits(ed) -> tuple:
+    """Inverse of _pack_edits -> (rows' nedits list or None, chunks' nedits
+    list or None, chunks' edits list or None)."""
+    rows, ch = ed
+    if ch is None:
+        return (rows.tolist() if rows is not None else None), None, None
+    n, off, tok, val, until = ch
+    off, tok, val, until = off.tolist(), tok.tolist(), val.tolist(), until.tolist()
+    edits = [(tuple(tok[a:b]), tuple(val[a:b]), tuple(until[a:b])) if b > a else None
+             for a, b in zip(off, off[1:])]
+    return (rows.tolist() if rows is not None else None), n.tolist(), edits
+
+
+def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None) -> GroupPlan:
     """Inverse of _pack_group.  Chunks sent without their token ids carry
     range(len) in their place (their stage reads only the lengths)."""
     gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb, kind=kind, fwd_rows=fwd_rows)
+    more_r, more_c = {}, {}
+    if ed is not None:
+        rn, cn, ce = _unpack_edits(ed)
+        if rn is not None:
+            more_r = dict(nedits=rn)
+        if cn is not None:
+            more_c = dict(nedits=cn, edits=ce)
     if ch is not None:
         ints, floats, seeds, tok = ch
         gp.chunks = _unpack_cols(Chunk, _CHUNK_INTS, ints, floats, seed=seeds.tolist(),
-                                 tok=tok.tolist() if tok is not None else None)
+                                 tok=tok.tolist() if tok is not None else None, **more_c)
     if rows is not None:
-        gp.rows = _unpack_cols(Row, _ROW_INTS, *rows)
+        gp.rows = _unpack_cols(Row, _ROW_INTS, *rows, **more_r)
     return gp
 
 

@@ -530,6 +530,7 @@ class _Meta:
     seed: int
     values: tuple = ((), ())  # plan.sampler_values: the chunk / row sampler fields
     logprobs: int = -1  # alternatives asked with every token's logprob (-1: no records)
+    edits: Optional[tuple] = None  # SamplingParams.logit_edits: (tokens, values, untils) sorted by token
     rep: int = 0        # replica and KV slot, from the request's first prefill chunk
     slot: int = -1
     done: bool = False  # finished by this scheduler (plain flag: the readout loop's hot path)
@@ -562,6 +563,7 @@ class Scheduler(racecheck.Shared):
         self.step_log: List[tuple] = []                     # (step, had_prefill) of timed steps
         self.stats = {"steps": 0, "joins": 0, "leaves": 0, "max_rows": 0, "captures": 0, "deferred": 0}
         self._rng = engine._rng
+        self._edited = 0  # live requests with logit edits: _group looks at chunks and rows only then
 
     # -- admission ---------------------------------------------------------
     def submit(self, prompt_ids: List[int], params: SamplingParams) -> Request:
@@ -623,6 +625,9 @@ class Scheduler(racecheck.Shared):
             p = req.params
             seed = p.seed if p.seed is not None else rng.getrandbits(62)
             meta[i] = _Meta(req, seed, sampler_values(p, seed), -1 if p.logprobs is None else int(p.logprobs))
+            if p.has_logit_edits:
+                meta[i].edits = p.logit_edits(self.eng.mcfg.eos_token_id)
+                self._edited += 1
             lens.append(len(req.prompt_ids))
             wants.append(p.max_new_tokens)
             stops.append(bool(p.stop_at_eos))
@@ -669,6 +674,23 @@ class Scheduler(racecheck.Shared):
         if changed:
             gp.rows = [Row(sid, slot, pos, *h, sstep, src, *t)
                        for sid, slot, pos, sstep, src in rows for h, t in (meta[sid].values,)]
+        if self._edited:
+            # requests with logit edits: every chunk and row says how many
+            # entries, the final chunk brings them (the last stage writes them
+            # to the slot's table ahead of the prefill draw)
+            for c in gp.chunks:
+                ed = meta[c.seq].edits
+                if ed is not None:
+                    c.nedits = len(ed[0])
+                    if c.final:
+                        c.edits = ed
+            if changed:
+                for r in gp.rows:
+                    ed = meta[r.seq].edits
+                    if ed is not None:
+                        r.nedits = len(ed[0])
+        if changed:
+            gp.edit = bool(self._edited) and any(r.nedits for r in gp.rows)
         return gp
 
     # -- token readout -----------------------------------------------------------
@@ -751,6 +773,8 @@ class Scheduler(racecheck.Shared):
         for sid, tok, flags in events:
             if flags & EV_RELEASE:
                 m = self.meta.pop(sid, None)
+                if m is not None and m.edits is not None:
+                    self._edited -= 1
                 if m is not None and flags & EV_FINISH and not m.done:
                     m.done = True
                     self._finish(m, done.get(sid, []))
@@ -789,6 +813,7 @@ class Scheduler(racecheck.Shared):
                 m.done = True
                 m.req.finish(error=err)
         self.meta.clear()
+        self._edited = 0
         self.core.reset()
         self.readouts.clear()
         with self._plock:

@@ -5,7 +5,8 @@
 otherwise the string "Error: {code} - {text}"; network failures return
 "Request failed: {exc}".  The optional sampling fields of /generate
 (temperature, top_k, top_p, min_p, presence_penalty, frequency_penalty, logprobs,
-greedy, seed, stop_at_eos) are sent when given; with logprobs the returned dict
+logit_bias, banned_token_ids, min_new_tokens, greedy, seed, stop_at_eos) are sent
+when given; with logprobs the returned dict
 has a "logprobs" object beside "generated".
 """
 from __future__ import annotations
@@ -19,12 +20,14 @@ COORDINATOR_URL = os.environ.get("COORDINATOR_URL", "http://127.0.0.1:5000/gener
 def generate_text(prompt: str, max_new_tokens: int = 20, url: str = None,
                   timeout: float = 300.0, top_p: float = None, min_p: float = None,
                   presence_penalty: float = None, frequency_penalty: float = None,
-                  logprobs: int = None, **sampling) -> Union[dict, str]:
+                  logprobs: int = None, logit_bias: dict = None, banned_token_ids: list = None,
+                  min_new_tokens: int = None, **sampling) -> Union[dict, str]:
     import requests
 
     payload = {"prompt": prompt, "max_new_tokens": max_new_tokens}
     sampling.update(top_p=top_p, min_p=min_p, presence_penalty=presence_penalty,
-                    frequency_penalty=frequency_penalty, logprobs=logprobs)
+                    frequency_penalty=frequency_penalty, logprobs=logprobs, logit_bias=logit_bias,
+                    banned_token_ids=banned_token_ids, min_new_tokens=min_new_tokens)
     payload.update({k: v for k, v in sampling.items() if v is not None})
     try:
         r = requests.post(url or COORDINATOR_URL, json=payload, timeout=timeout)

@@ -15,7 +15,8 @@ Roles (env SHARD_ROLE, `server.py:21`):
   b            blocks[SPLIT_AT:] + ln_f + lm_head                 -> /forward_b
   all          one process answers every endpoint (debug)
 Additions: optional sampling fields on /generate (temperature, top_k, top_p,
-min_p, presence_penalty, frequency_penalty, logprobs, greedy, seed, stop_at_eos;
+min_p, presence_penalty, frequency_penalty, logprobs, logit_bias, banned_token_ids,
+min_new_tokens, greedy, seed, stop_at_eos;
 defaults = reference sampler; with logprobs the response gains a "logprobs" object
 beside "generated"), 422 on empty/over-long
 prompts (instead of the reference's 500, quirk Q9), GET /health, GET /metrics
@@ -29,7 +30,7 @@ from __future__ import annotations
 
 import logging
 import time
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 import torch
 from pydantic import BaseModel
@@ -65,6 +66,11 @@ class GenerateReq(BaseModel):
     frequency_penalty: float = 0.0  # off it again per occurrence so far (in [-2, 2])
     # alternatives returned with every generated token's logprob (None = no "logprobs" in the response)
     logprobs: Optional[int] = None
+    # logit edits ahead of every draw: {token id: value in [-100, 100]} added to the logits,
+    # tokens that can never be drawn, and draws (from the first) in which EOS cannot be drawn
+    logit_bias: Optional[Dict[str, float]] = None
+    banned_token_ids: Optional[List[int]] = None
+    min_new_tokens: int = 0
 
 
 def logprobs_json(lp) -> dict:
@@ -180,7 +186,8 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                             seed=req.seed, max_new_tokens=req.max_new_tokens,
                             stop_at_eos=req.stop_at_eos, top_p=req.top_p, min_p=req.min_p,
                             presence_penalty=req.presence_penalty, frequency_penalty=req.frequency_penalty,
-                            logprobs=req.logprobs)
+                            logprobs=req.logprobs, logit_bias=req.logit_bias,
+                            banned_token_ids=req.banned_token_ids, min_new_tokens=req.min_new_tokens)
         if req.max_new_tokens == 0 and req.logprobs is None:
             return {"generated": tok.decode(ids, skip_special_tokens=True)}
         if not ids:
@@ -190,7 +197,7 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
 
         lp = None
         try:
-            sp.validate(cfg.max_logprobs)
+            sp.validate(cfg.max_logprobs, cfg.max_logit_edits)
             if req.max_new_tokens == 0:
                 from ..runtime.scheduler import Logprobs
 
@@ -269,7 +276,9 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
     full-sequence recompute on every step, hidden states relayed through here.
     Kept for deployments where the shards are separate hosts without xGMI.
     This relay keeps the reference's sampler: presence_penalty and
-    frequency_penalty are ignored here.  records=True: -> (tokens, the logprob
+    frequency_penalty are ignored here; logit_bias, banned_token_ids and
+    min_new_tokens are applied on the host (ops/reference.py logit_edits; ids
+    outside the vocabulary are ignored).  records=True: -> (tokens, the logprob
     records of a request that asked for them or None), computed on the host
     from the logits this loop already holds (ops/reference.py logprobs)."""
     import requests
@@ -285,6 +294,11 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
         from ..runtime.scheduler import Logprobs
 
         lp = Logprobs(out, [], [])
+    table = None
+    if sp.has_logit_edits:
+        table = tuple(torch.tensor([col], dtype=dt) for col, dt in zip(
+            sp.logit_edits(cfg.model.eos_token_id), (torch.int32, torch.float32, torch.int32)))
+        table = (torch.tensor([table[0].shape[1]], dtype=torch.int32),) + table
     seq = list(ids)
     url_a = f"http://{cfg.shard_a_service}:{cfg.shard_port}/forward"
     url_b = f"http://{cfg.shard_b_service}:{cfg.shard_port}/forward_b"
@@ -295,6 +309,8 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
         r2 = requests.post(url_b, json={"hidden_states": hidden}, timeout=30)
         r2.raise_for_status()
         logits = torch.tensor(r2.json()["logits"], dtype=torch.float32)[0, -1:]
+        if table is not None:
+            ref.logit_edits(logits, table, torch.tensor([0]), torch.tensor([step]), vocab)
         u = counter_uniform(torch.tensor([seed]), torch.tensor([step]))
         nxt = int(ref.sample(logits, torch.tensor([sp.temperature]), torch.tensor([sp.top_k]),
                              torch.tensor([1 if sp.greedy else 0]), u, vocab,
