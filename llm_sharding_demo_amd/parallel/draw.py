@@ -1,0 +1,214 @@
+"""What happens to a row's logits between `lm_head` and the returned token.
+
+A `StageWorker` (parallel/pipeline.py) moves a step through its stage; its
+`DrawStage` decides what runs on the logits of the last stage: the penalty
+pass, the logit edits, the sampler, the token history and the logprob records,
+for the decode rows of a group (`rows`, captured into the decode graphs) and
+for the first draw of a finished prompt (`finals`, eager).  It owns the three
+per-KV-slot tables these passes read and write, and counts the items that ran
+each pass.  Every stage has one; off the last stage it stays empty.
+"""
+from __future__ import annotations
+
+from typing import Callable, Optional
+
+import numpy as np
+import torch
+
+from ..runtime.batch import SamplingState
+from ..runtime.plan import has_edits, row_features
+from ..utils import racecheck
+
+
+class DrawStage(racecheck.Shared):
+    def __init__(self, stage, slots: int, stage_h2d: Callable, gpu: Callable):
+        """`stage`: the StageModel (backend, device, vocabulary, max_seq --
+        read at each call: a test may wrap the backend after construction);
+        `slots`: KV slots, scratch and compat included; `stage_h2d(gs, host
+        int32 array, device tensor)`: the worker's pinned staging copy;
+        `gpu()`: the worker's shared hold on the capture gate."""
+        self.stage = stage
+        self.slots = slots
+        self._stage_h2d, self._gpu = stage_h2d, gpu
+        # per-KV-slot tables, each allocated when the first request that needs
+        # it arrives (_hist, _lp_rec, _edit_tab), beside the items whose
+        # sampler ran with that pass around it
+        self.pen_hist: Optional[torch.Tensor] = None  # generated tokens, by the draw's sampler counter
+        self.penalty_launches = 0
+        self.lp_rec: Optional[tuple] = None  # logprob records, indexed like the history, W = max_logprobs wide
+        self.max_logprobs = 5
+        self.logprob_launches = 0
+        self.edit_tab: Optional[tuple] = None  # logit_bias / banned tokens / min_new_tokens, E = max_logit_edits
+        self.max_logit_edits = 300
+        self.logit_edit_launches = 0
+
+    # ------------------------------------------------------------------
+    # tables
+    def _hist(self) -> torch.Tensor:
+        """Generated-token history, [KV slots (scratch and compat included),
+        max_seq] int32.  Entries at or past a row's sampler counter are never
+        read, so it needs no initial value and a reused slot no clearing."""
+        if self.pen_hist is None:
+            L, dev = self.stage.max_seq, self.stage.device
+            if L > 8192 and dev.type == "cuda":
+                raise ValueError(f"presence / frequency penalties: max_seq_len {L} exceeds the 8192-token "
+                                 "history the penalty kernel's LDS table holds")
+            # no fill: one enqueued on this lane could land after another lane's first record
+            self.pen_hist = torch.empty(self.slots, L, dtype=torch.int32, device=dev)
+        return self.pen_hist
+
+    def _lp_rec(self) -> tuple:
+        """Logprob records: (lp_tok [KV slots, max_seq] fp32, lp_top_id [.., W]
+        int32, lp_top [.., W] fp32), record j of a slot = the draw with sampler
+        counter j.  Records at or past a sequence's token count are never
+        fetched, so no initial value and no clearing."""
+        if self.lp_rec is None:
+            S, L, W, dev = self.slots, self.stage.max_seq, self.max_logprobs, self.stage.device
+            # no fill: one enqueued on this lane could land after another lane's first record
+            self.lp_rec = (torch.empty(S, L, dtype=torch.float32, device=dev),
+                           torch.empty(S, L, W, dtype=torch.int32, device=dev),
+                           torch.empty(S, L, W, dtype=torch.float32, device=dev))
+        return self.lp_rec
+
+    def _edit_tab(self) -> tuple:
+        """Logit-edit table: (cnt [KV slots, scratch and compat included]
+        int32, tok [.., E] int32, val [.., E] fp32, until [.., E] int32), E =
+        max_logit_edits.  Unlike the history and the logprob records its stale
+        contents ARE read: a group whose rows joined before the table existed
+        runs the edit pass once a row with edits joins it, and reads its other
+        rows' counts.  So the counts start at zero, and visibly to every lane:
+        this thread waits for the fill before anything that reads the table can
+        be enqueued, on this lane or another (_hist: a fill merely enqueued
+        here could land after another lane's reader).  Allocated once, outside
+        any capture, and never reallocated: captured graphs hold its addresses.
+        From then on every final chunk writes its slot's count (finals)."""
+        if self.edit_tab is None:
+            S, E, dev = self.slots, self.max_logit_edits, self.stage.device
+            self.edit_tab = (torch.zeros(S, dtype=torch.int32, device=dev),
+                             torch.zeros(S, E, dtype=torch.int32, device=dev),
+                             torch.zeros(S, E, dtype=torch.float32, device=dev),
+                             torch.zeros(S, E, dtype=torch.int32, device=dev))
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()
+        return self.edit_tab
+
+    def prepare(self, feats: tuple) -> None:
+        """A composition with the features (cut, pen, lp, edit) is being
+        applied: what they need -- the token history, the logprob records, the
+        edit table -- allocated here, on the host side of the change (never
+        inside a capture)."""
+        _, pen, lp, edit = feats
+        if pen:
+            self._hist()
+        if lp:
+            self._lp_rec()
+        if edit:
+            self._edit_tab()
+
+    def fetch_logprobs(self, slot: int, n: int) -> tuple:
+        """Host copies of records [0, n) of KV slot `slot`: (lp_tok [n],
+        lp_top_id [n, W], lp_top [n, W]).  For the coordinator thread, once it
+        has read the n-th token back: each record is written ahead of its
+        token's return in stream order.  Holds the capture gate shared (a
+        sibling stage thread may be capturing)."""
+        rec = self._lp_rec()
+        with self._gpu():
+            return tuple(t[slot, :n].cpu() for t in rec)
+
+    # ------------------------------------------------------------------
+    def count(self, gs) -> None:
+        """One decode item of group `gs` was issued -- eagerly, captured or as
+        a replayed graph: count the passes that ran around its sampler."""
+        if gs.pen:
+            self.penalty_launches += 1
+        if gs.lp:
+            self.logprob_launches += 1
+        if gs.edit:
+            self.logit_edit_launches += 1
+
+    def rows(self, gs, logits: torch.Tensor, b: int, meta) -> None:
+        """Decode rows of a group: draw into the token-return vector, advance
+        the sampler counters and positions.  A composition with a penalised
+        row runs penalize and record_tokens around the sampler.  One with an
+        edited row runs the edit pass right ahead of the sampler (after the
+        penalties; the counters it compares are the ones the draw uses).  One
+        with a logprob row then runs the logprob kernel over the logits the
+        sampler drew from.  Any other runs the sampler alone."""
+        be, V = self.stage.backend, self.stage.cfg.vocab_size
+        slots, step, out = gs.slots[:b], gs.sstep[:b], gs.tokret[:b]
+        if gs.pen:
+            be.penalize(logits, self.pen_hist, slots, step, gs.presence[:b], gs.frequency[:b], V)
+        if gs.edit:
+            be.logit_edits(logits, self.edit_tab, slots, step, V)
+        be.sample_into(logits, gs.samp(b), V, out, meta)
+        if gs.pen:
+            # the sampler has advanced the counters: the draw used counter - 1
+            be.record_tokens(self.pen_hist, slots, step, out, gs.active[:b], 1)
+        if gs.lp:
+            be.logprobs(logits, out, gs.nlp[:b], slots, step, gs.active[:b], self.lp_rec, V, 1)
+
+    def finals(self, gs, fc, logits: torch.Tensor) -> torch.Tensor:
+        """First generated token (draw 0) of the final chunks `fc`, drawn from
+        `logits`.  Eager, on the item's lane, outside any graph.  Ahead of the
+        draw their logit edits go into their KV slots' table rows and the edit
+        pass runs over `logits`: nothing without a table and without edits;
+        once the table exists every final chunk writes its slot's count, zero
+        included -- a request that reuses a slot must not inherit its
+        predecessor's entries.  Behind it the token goes into the history when
+        a chunk carries a penalty (its history is empty, so this draw needs no
+        penalty pass), and its logprob record is taken from `logits` when one
+        asked."""
+        be, V, dev = self.stage.backend, self.stage.cfg.vocab_size, self.stage.device
+        _, pen, lp = row_features(fc)
+        ed = has_edits(fc)
+        tab = self._edit_tab() if ed or self.edit_tab is not None else None
+        slots = nlp = None
+        if tab is not None or pen or lp:
+            slots, nlp = self._stage_finals(gs, fc, tab)
+        if ed:
+            be.logit_edits(logits, tab, slots, None, V)
+            self.logit_edit_launches += 1
+        ids = be.sample(logits, SamplingState.of(fc, dev), V)
+        if pen:
+            be.record_tokens(self._hist(), slots, None, ids, None, 0)
+            self.penalty_launches += 1
+        if lp:
+            be.logprobs(logits, ids, nlp, slots, None, None, self._lp_rec(), V, 0)
+            self.logprob_launches += 1
+        return ids
+
+    def _stage_finals(self, gs, fc, tab: Optional[tuple]) -> tuple:
+        """What the passes around the first draw of `fc` read, on the device
+        in ONE host-to-device copy through the group's pinned staging ring:
+        [slots J | logprob widths J | edit counts J], then with n edits among
+        them [flat table index n | tokens n | value bits n | untils n].  With
+        a table, its rows are written from the copy.  -> (slots, widths)."""
+        cols = [[c.slot for c in fc], [c.logprobs for c in fc], [c.nedits for c in fc]]
+        if tab is not None:
+            cnt, tok, val, until = tab
+            E = tok.shape[1]
+            if any(c.nedits and (c.edits is None or len(c.edits[0]) != c.nedits or c.nedits > E) for c in fc):
+                raise ValueError(f"a final chunk's logit edits are missing or exceed max_logit_edits = {E}")
+            ent = [c.edits for c in fc if c.nedits]
+            if ent:
+                cols += [np.concatenate([c.slot * E + np.arange(c.nedits) for c in fc if c.nedits]),
+                         [t for e in ent for t in e[0]],
+                         np.array([v for e in ent for v in e[1]], dtype=np.float32).view(np.int32),
+                         [u for e in ent for u in e[2]]]
+        arr = np.concatenate([np.asarray(c, dtype=np.int32) for c in cols])
+        dev = self.stage.device
+        if dev.type == "cuda":
+            buf = torch.empty(arr.size, dtype=torch.int32, device=dev)
+            self._stage_h2d(gs, arr, buf)
+        else:
+            buf = torch.from_numpy(arr)
+        slots, nlp, counts, *edits = buf.split([len(c) for c in cols])
+        if tab is not None:
+            cnt.index_copy_(0, slots.long(), counts)
+        if edits:
+            at, t, v, u = edits
+            at = at.long()
+            tok.view(-1).index_copy_(0, at, t)
+            val.view(-1).index_copy_(0, at, v.view(torch.float32))
+            until.view(-1).index_copy_(0, at, u)
+        return slots, nlp

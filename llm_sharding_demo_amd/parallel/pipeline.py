@@ -42,12 +42,13 @@ import numpy as np
 import torch
 
 from ..models.stage import StageModel
-from ..runtime.batch import BatchMeta, MixedMeta, SamplingState
+from ..runtime.batch import BatchMeta, MixedMeta
 from ..runtime.plan import (NO_FEATURES, ROW_FIELDS, GroupPlan, StepPlan, device_fields, has_edits, pack_rows,
                             packed_size, row_features)
 from ..utils.tracing import trace_range
 from ..utils import racecheck
 from .comm import Handle, SendHandle, Transport
+from .draw import DrawStage
 
 class _CaptureGate(racecheck.Shared):
     """Stage threads sharing one GPU (local mode) issue work concurrently, but
@@ -419,28 +420,9 @@ class StageWorker(racecheck.Shared):
         self.native_changes = 0  # composition-change items issued by exec_items
         self.mixed_items = 0     # decode + prefill items run as one forward (_mixed)
         self.io_items = 0  # decode items whose (graph) body carried its own transfers
-        # last stage: generated-token history per KV slot, int32 [slots,
-        # max_seq], indexed by the draw's sampler counter (_hist: allocated
-        # when the first penalised request arrives), and the items whose
-        # sampler ran with the penalty pass around it
-        self.pen_hist: Optional[torch.Tensor] = None
-        self.penalty_launches = 0
-        # last stage: logprob records per KV slot, indexed like the history
-        # (_lp_rec: allocated when the first logprob request arrives) --
-        # (lp_tok [slots, L] fp32, lp_top_id [slots, L, W] int32, lp_top
-        # [slots, L, W] fp32), W = max_logprobs -- and the items whose sampler
-        # was followed by the logprob kernel
-        self.lp_rec: Optional[tuple] = None
-        self.max_logprobs = 5
-        self.logprob_launches = 0
-        # last stage: logit edits per KV slot (_edit_tab: allocated when the
-        # first request with logit_bias / banned tokens / min_new_tokens
-        # arrives) -- (cnt [slots] int32, tok [slots, E] int32, val [slots, E]
-        # fp32, until [slots, E] int32), E = max_logit_edits -- and the items
-        # whose sampler ran behind the edit pass
-        self.edit_tab: Optional[tuple] = None
-        self.max_logit_edits = 300
-        self.logit_edit_launches = 0
+        # what runs on the last stage's logits, its per-KV-slot tables and
+        # launch counters (parallel/draw.py); allocates nothing until asked
+        self.draw = DrawStage(stage, max(scratch_slot, compat_slot) + 1, self._stage_h2d, self._gpu)
 
     # ------------------------------------------------------------------
     def configure(self, groups: int, cap: int) -> None:
@@ -496,6 +478,7 @@ class StageWorker(racecheck.Shared):
         # the hand-over from the constructing thread is ordered by the plan channel,
         # which the lockset checker (utils/racecheck.py) cannot see
         racecheck.handoff(self)
+        racecheck.handoff(self.draw)
         for gs in (getattr(self, "groups", None) or {}).values():
             racecheck.handoff(gs)
         if not self.lanes:
@@ -719,12 +702,7 @@ class StageWorker(racecheck.Shared):
                     d[18] = args.numel()
                     packed.append((slot, lane))
                     self.native_changes += 1
-                if gs.pen:
-                    self.penalty_launches += 1
-                if gs.lp:
-                    self.logprob_launches += 1
-                if gs.edit:
-                    self.logit_edit_launches += 1
+                self.draw.count(gs)
                 rows.append(d)
             try:
                 with (self.t.issuing() if self.t is not None else contextlib.nullcontext()):
@@ -930,7 +908,7 @@ class StageWorker(racecheck.Shared):
                 and gp.n <= gp.b)
 
     def _mixed(self, gp: GroupPlan, gs: GroupState) -> None:
-        st, be, dev = self.stage, self.stage.backend, self.device
+        st, dev = self.stage, self.device
         ch = gp.chunks
         b = gp.b
         pf, ids, _ = self._chunk_meta(gs, ch, tuple(c.qlen for c in ch))
@@ -947,28 +925,18 @@ class StageWorker(racecheck.Shared):
             rows = torch.cat([rows, pf.last_idx.index_select(0, fi) + b])
         logits = st.forward(mm, inp, head=True, head_rows=rows, variant=gp.g & 1)
         gs.ensure_tokret(self, b + J)
-        V = st.cfg.vocab_size
         seg = getattr(logits, "_lsd_segmax", None)
         ld = logits[:b]
         if seg is not None:
             ld._lsd_segmax = seg[:b]
         # decode rows: draw, advance their sampler counters and positions (as the graph does)
-        self._sample_rows(gs, ld, b, dec)
-        if gs.pen:
-            self.penalty_launches += 1
-        if gs.lp:
-            self.logprob_launches += 1
-        if gs.edit:
-            self.logit_edit_launches += 1
+        self.draw.rows(gs, ld, b, dec)
+        self.draw.count(gs)
         if J:
             lf = logits[b:]
             if seg is not None:
                 lf._lsd_segmax = seg[b:]
-            fc = [ch[i] for i in finals]
-            self._edit_finals(gs, fc, lf)
-            ids = be.sample(lf, SamplingState.of(fc, dev), V)
-            self._record_finals(fc, ids, lf)
-            gs.tokret[b: b + J].copy_(ids)
+            gs.tokret[b: b + J].copy_(self.draw.finals(gs, [ch[i] for i in finals], lf))
         self.mixed_items += 1
 
     def _features(self, gp: GroupPlan, gs: GroupState) -> tuple:
@@ -987,16 +955,10 @@ class StageWorker(racecheck.Shared):
 
     def _set_features(self, gs: GroupState, feats: tuple) -> None:
         """A composition change is being applied: the group's features from
-        now on, and what they need -- the token history, the logprob records,
-        the edit table -- allocated here, on the host side of the change (never
+        now on, and the tables they need, on the host side of the change (never
         inside a capture)."""
         gs.cut, gs.pen, gs.lp, gs.edit = feats
-        if gs.pen:
-            self._hist()
-        if gs.lp:
-            self._lp_rec()
-        if gs.edit:
-            self._edit_tab()
+        self.draw.prepare(feats)
 
     def _apply_rows(self, gp: GroupPlan, gs: GroupState) -> None:
         """New composition: rows [0, n) from the plan, pad rows [n, b) idle on
@@ -1046,160 +1008,8 @@ class StageWorker(racecheck.Shared):
             else:
                 vec[:b].copy_(part.view(vec.dtype))
 
-    def _lp_rec(self) -> tuple:
-        """Logprob records of the last stage: (lp_tok [KV slots, max_seq] fp32,
-        lp_top_id [.., W] int32, lp_top [.., W] fp32), record j of a slot = the
-        draw with sampler counter j.  Records at or past a sequence's token
-        count are never fetched, so no initial value and no clearing."""
-        if self.lp_rec is None:
-            L, W = self.stage.max_seq, self.max_logprobs
-            slots = max(self.scratch_slot, self.compat_slot) + 1
-            dev = self.device
-            # no fill: one enqueued on this lane could land after another lane's first record
-            self.lp_rec = (torch.empty(slots, L, dtype=torch.float32, device=dev),
-                           torch.empty(slots, L, W, dtype=torch.int32, device=dev),
-                           torch.empty(slots, L, W, dtype=torch.float32, device=dev))
-        return self.lp_rec
-
     def fetch_logprobs(self, slot: int, n: int) -> tuple:
-        """Host copies of records [0, n) of KV slot `slot`: (lp_tok [n],
-        lp_top_id [n, W], lp_top [n, W]).  For the coordinator thread, once it
-        has read the n-th token back: each record is written ahead of its
-        token's return in stream order.  Holds the capture gate shared (a
-        sibling stage thread may be capturing)."""
-        rec = self._lp_rec()
-        with self._gpu():
-            return tuple(t[slot, :n].cpu() for t in rec)
-
-    def _hist(self) -> torch.Tensor:
-        """Generated-token history of the last stage, [KV slots (scratch and
-        compat included), max_seq] int32.  Entries at or past a row's sampler
-        counter are never read, so it needs no initial value and a reused slot
-        no clearing."""
-        if self.pen_hist is None:
-            L = self.stage.max_seq
-            if L > 8192 and self.device.type == "cuda":
-                raise ValueError(f"presence / frequency penalties: max_seq_len {L} exceeds the 8192-token "
-                                 "history the penalty kernel's LDS table holds")
-            slots = max(self.scratch_slot, self.compat_slot) + 1
-            # no fill: one enqueued on this lane could land after another lane's first record
-            self.pen_hist = torch.empty(slots, L, dtype=torch.int32, device=self.device)
-        return self.pen_hist
-
-    def _sample_rows(self, gs: GroupState, logits: torch.Tensor, b: int, meta) -> None:
-        """Decode rows of a group: draw into the token-return vector, advance
-        the sampler counters and positions.  A composition with a penalised
-        row runs lm_head, penalize, sample_into, record_tokens; any other the
-        sampler alone, as before.  A composition with an edited row runs the
-        edit pass right ahead of the sampler (after the penalties; the counters
-        it compares are the ones the draw uses).  A composition with a logprob
-        row then runs the logprob kernel over the logits the sampler drew from."""
-        be, V = self.stage.backend, self.stage.cfg.vocab_size
-        if not gs.pen:
-            if gs.edit:
-                be.logit_edits(logits, self.edit_tab, gs.slots[:b], gs.sstep[:b], V)
-            be.sample_into(logits, gs.samp(b), V, gs.tokret[:b], meta)
-        else:
-            hist = self.pen_hist
-            be.penalize(logits, hist, gs.slots[:b], gs.sstep[:b], gs.presence[:b], gs.frequency[:b], V)
-            if gs.edit:
-                be.logit_edits(logits, self.edit_tab, gs.slots[:b], gs.sstep[:b], V)
-            be.sample_into(logits, gs.samp(b), V, gs.tokret[:b], meta)
-            # the sampler has advanced the counters: the draw used counter - 1
-            be.record_tokens(hist, gs.slots[:b], gs.sstep[:b], gs.tokret[:b], gs.active[:b], 1)
-        if gs.lp:
-            be.logprobs(logits, gs.tokret[:b], gs.nlp[:b], gs.slots[:b], gs.sstep[:b], gs.active[:b],
-                        self.lp_rec, V, 1)
-
-    def _record_finals(self, fc, ids: torch.Tensor, logits: torch.Tensor) -> None:
-        """First generated token (draw 0) of the final chunks `fc` into the
-        history, when one of them carries a penalty (its history is empty, so
-        the prefill draw itself needs no penalty pass), and its logprob record
-        from `logits`, the rows `ids` were drawn from, when one of them asked.
-        Eager, outside any graph."""
-        _, pen, lp = row_features(fc)
-        if not (pen or lp):
-            return
-        slots = _h2d([c.slot for c in fc], torch.int32, self.device)
-        slots = slots.to(self.device, non_blocking=True)
-        if pen:
-            self.stage.backend.record_tokens(self._hist(), slots, None, ids, None, 0)
-            self.penalty_launches += 1
-        if lp:
-            nlp = _h2d([c.logprobs for c in fc], torch.int32, self.device).to(self.device, non_blocking=True)
-            self.stage.backend.logprobs(logits, ids, nlp, slots, None, None, self._lp_rec(),
-                                        self.stage.cfg.vocab_size, 0)
-            self.logprob_launches += 1
-
-    def _edit_tab(self) -> tuple:
-        """Logit-edit table of the last stage: (cnt [KV slots, scratch and
-        compat included] int32, tok [.., E] int32, val [.., E] fp32, until
-        [.., E] int32), E = max_logit_edits.  Unlike the history and the
-        logprob records its stale contents ARE read: a group whose rows joined
-        before the table existed runs the edit pass once a row with edits joins
-        it, and reads its other rows' counts.  So the counts start at zero, and
-        visibly to every lane: this thread waits for the fill before anything
-        that reads the table can be enqueued, on this lane or another (_hist:
-        a fill merely enqueued here could land after another lane's reader).
-        Allocated once, outside any capture, and never reallocated: captured
-        graphs hold its addresses.  From then on every final chunk writes its
-        slot's count (_edit_finals)."""
-        if self.edit_tab is None:
-            E = self.max_logit_edits
-            slots = max(self.scratch_slot, self.compat_slot) + 1
-            dev = self.device
-            self.edit_tab = (torch.zeros(slots, dtype=torch.int32, device=dev),
-                             torch.zeros(slots, E, dtype=torch.int32, device=dev),
-                             torch.zeros(slots, E, dtype=torch.float32, device=dev),
-                             torch.zeros(slots, E, dtype=torch.int32, device=dev))
-            if dev.type == "cuda":
-                torch.cuda.current_stream(dev).synchronize()
-        return self.edit_tab
-
-    def _edit_finals(self, gs: GroupState, fc, logits: torch.Tensor) -> None:
-        """Ahead of the first draw (draw 0) of the final chunks `fc`: their
-        logit edits into their KV slots' table rows, and the edit pass over
-        `logits`, the rows they are drawn from.  Eager, on the item's lane,
-        outside any graph.  Nothing without a table and without edits; once
-        the table exists every final chunk writes its slot's count, zero
-        included -- a request that reuses a slot must not inherit its
-        predecessor's entries.  One host-to-device copy through the group's
-        pinned staging ring: [slots J | counts J | flat table index n | tokens
-        n | value bits n | untils n]."""
-        ed = has_edits(fc)
-        if not ed and self.edit_tab is None:
-            return
-        cnt, tok, val, until = self._edit_tab()
-        E, J = tok.shape[1], len(fc)
-        ent = [c.edits if c.nedits else None for c in fc]
-        if any(c.nedits and (e is None or len(e[0]) != c.nedits or c.nedits > E) for c, e in zip(fc, ent)):
-            raise ValueError(f"a final chunk's logit edits are missing or exceed max_logit_edits = {E}")
-        n = sum(c.nedits for c in fc)
-        arr = np.empty(2 * J + 4 * n, dtype=np.int32)
-        arr[:J] = [c.slot for c in fc]
-        arr[J: 2 * J] = [c.nedits for c in fc]
-        if n:
-            o = 2 * J
-            arr[o: o + n] = np.concatenate([c.slot * E + np.arange(c.nedits) for c in fc if c.nedits])
-            arr[o + n: o + 2 * n] = [t for e in ent if e for t in e[0]]
-            arr[o + 2 * n: o + 3 * n] = np.array([v for e in ent if e for v in e[1]], dtype=np.float32).view(np.int32)
-            arr[o + 3 * n: o + 4 * n] = [u for e in ent if e for u in e[2]]
-        if self.device.type == "cuda":
-            buf = torch.empty(arr.size, dtype=torch.int32, device=self.device)
-            self._stage_h2d(gs, arr, buf)
-        else:
-            buf = torch.from_numpy(arr)
-        slots = buf[:J]
-        cnt.index_copy_(0, slots.long(), buf[J: 2 * J])
-        if n:
-            o = 2 * J
-            at = buf[o: o + n].long()
-            tok.view(-1).index_copy_(0, at, buf[o + n: o + 2 * n])
-            val.view(-1).index_copy_(0, at, buf[o + 2 * n: o + 3 * n].view(torch.float32))
-            until.view(-1).index_copy_(0, at, buf[o + 3 * n: o + 4 * n])
-        if ed:
-            self.stage.backend.logit_edits(logits, self.edit_tab, slots, None, self.stage.cfg.vocab_size)
-            self.logit_edit_launches += 1
+        return self.draw.fetch_logprobs(slot, n)
 
     _ROWS_PIN = 4  # packed row-state buffers per group: reused 4 composition changes later
 
@@ -1247,11 +1057,7 @@ class StageWorker(racecheck.Shared):
             rows = meta.last_idx.index_select(0, torch.tensor(finals, dtype=torch.long, device=dev))
             be.decode = False
             logits = st.head(x, meta, rows=rows)
-        fc = [ch[i] for i in finals]
-        self._edit_finals(gs, fc, logits)
-        ids = be.sample(logits, SamplingState.of(fc, dev), st.cfg.vocab_size)
-        self._record_finals(fc, ids, logits)
-        return ids
+        return self.draw.finals(gs, [ch[i] for i in finals], logits)
 
     # Prefill chunks as hipGraphs (the non-steady items):
     # a chunk item whose shape (per-sequence query counts, split variant, input
@@ -1369,12 +1175,7 @@ class StageWorker(racecheck.Shared):
     def _decode(self, gp: GroupPlan, gs: GroupState, inp: torch.Tensor, io: bool = False) -> torch.Tensor:
         key = (gp.b, gp.ctxb, io, gs.cut, gs.pen, gs.lp, gs.edit)
         lane = self.lane_of(gp.g)
-        if gs.pen:
-            self.penalty_launches += 1
-        if gs.lp:
-            self.logprob_launches += 1
-        if gs.edit:
-            self.logit_edit_launches += 1
+        self.draw.count(gs)
 
         def body():
             if io and not self.first:  # the edge receive, inside the graph
@@ -1387,7 +1188,7 @@ class StageWorker(racecheck.Shared):
                     self._send(out, self.r + 1, "fwd", lane, capture=True)
                 return out
             # the sampler kernel also advances this stage's positions (no add kernel)
-            self._sample_rows(gs, out, gp.b, meta)
+            self.draw.rows(gs, out, gp.b, meta)
             if io:
                 self._send(gs.tokret[: gp.b], 0, "ret", lane, capture=True)
             return gs.tokret[: gp.b]

@@ -349,8 +349,8 @@ class Engine(racecheck.Shared):
                         compat_slot=self.kv_slots + 1,
                         wire=torch.bfloat16 if self.cfg.wire_dtype == "bf16" else None)
         w.merge_prefill = w.MERGE_PREFILL and self.cfg.merge_prefill
-        w.max_logprobs = self.cfg.max_logprobs
-        w.max_logit_edits = self.cfg.max_logit_edits
+        w.draw.max_logprobs = self.cfg.max_logprobs
+        w.draw.max_logit_edits = self.cfg.max_logit_edits
         return w
 
     @property

@@ -275,10 +275,10 @@ def test_engine_default_traffic_launches_nothing(runs):
     e, plain = runs
     fresh = _eng(e.P)
     assert fresh.generate_ids([PROMPT] + OTHER_PROMPTS, [PLAIN] + OTHERS)[0] == plain
-    assert all(w.logit_edit_launches == 0 and w.edit_tab is None for w in fresh.workers)
+    assert all(w.draw.logit_edit_launches == 0 and w.draw.edit_tab is None for w in fresh.workers)
     zero = SamplingParams(greedy=True, max_new_tokens=N, logit_bias={}, banned_token_ids=[], min_new_tokens=0)
     assert fresh.generate_ids([PROMPT], [zero])[0] == plain
-    assert all(w.logit_edit_launches == 0 and w.edit_tab is None for w in fresh.workers)
+    assert all(w.draw.logit_edit_launches == 0 and w.draw.edit_tab is None for w in fresh.workers)
 
 
 def test_engine_ban_is_live_and_neighbours_unchanged(runs):
@@ -286,7 +286,7 @@ def test_engine_ban_is_live_and_neighbours_unchanged(runs):
     ban = SamplingParams(greedy=True, max_new_tokens=N, banned_token_ids=[plain[0], plain[0]])
     alone = e.generate_ids([PROMPT], [ban])[0]
     assert len(alone) == N and plain[0] not in alone and alone[0] != plain[0]
-    assert e.workers[-1].logit_edit_launches > 0 and all(w.logit_edit_launches == 0 for w in e.workers[:-1])
+    assert e.workers[-1].draw.logit_edit_launches > 0 and all(w.draw.logit_edit_launches == 0 for w in e.workers[:-1])
     without = e.generate_ids(OTHER_PROMPTS, OTHERS)
     outs = e.generate_ids([OTHER_PROMPTS[0], PROMPT] + OTHER_PROMPTS[1:], [OTHERS[0], ban] + OTHERS[1:])
     assert outs[1] == alone

@@ -291,13 +291,13 @@ def test_engine_edited_requests_in_a_changing_batch(monkeypatch):
     without = e.generate_ids(PROMPTS[:2] + PROMPTS[3:5], OTHERS)
     default = [OTHERS[0], OTHERS[1], PLAIN_G, OTHERS[2], OTHERS[3], PLAIN_S]
     assert e.generate_ids(PROMPTS, default)[5] == plain_s  # precondition: comparable across compositions
-    assert sum(w.logit_edit_launches for w in e.workers) == 0 and e.workers[0].edit_tab is None  # default traffic
+    assert sum(w.draw.logit_edit_launches for w in e.workers) == 0 and e.workers[0].draw.edit_tab is None  # default traffic
     ed_g = dataclasses.replace(PLAIN_G, banned_token_ids=[plain[0]])
     ed_s = dataclasses.replace(PLAIN_S, banned_token_ids=[plain_s[1], plain_s[2]],
                                logit_bias={plain_s[0]: -5.0, 7: 1.0}, min_new_tokens=3)
     alone_g = e.generate_ids([PROMPTS[2]], [ed_g])[0]
     alone_s = e.generate_ids([PROMPTS[5]], [ed_s])[0]
-    assert sum(w.logit_edit_launches for w in e.workers) > 0
+    assert sum(w.draw.logit_edit_launches for w in e.workers) > 0
     assert len(alone_g) == N and len(alone_s) == N
     assert plain[0] not in alone_g and alone_g[0] != plain[0]  # the ban is live
     assert plain_s[1] not in alone_s and plain_s[2] not in alone_s and alone_s != plain_s
@@ -352,5 +352,5 @@ def test_engine_edits_with_penalties_and_logprobs_match_the_reference():
     out = want[0].output
     assert len(out) == 6 and eos not in out[:5] and out[5] == eos
     assert not set(want[2].output) & set(range(100, 350)) and all(t % 4 != 1 for t in want[3].output)
-    assert sum(w.logit_edit_launches for w in e.workers) > 0 and sum(w.penalty_launches for w in e.workers) > 0
+    assert sum(w.draw.logit_edit_launches for w in e.workers) > 0 and sum(w.draw.penalty_launches for w in e.workers) > 0
     assert sum(w.native_steps for w in e.workers) > 0

@@ -231,7 +231,7 @@ def test_engine_same_records_at_every_stage_count(runs, P):
     for sp, r in zip(ASK, reqs):
         got = e.generate_requests([PROMPT], [sp])[0]
         assert got.output == r.output and got.logprobs == r.logprobs
-    assert e.workers[-1].logprob_launches > 0 and all(w.logprob_launches == 0 for w in e.workers[:-1])
+    assert e.workers[-1].draw.logprob_launches > 0 and all(w.draw.logprob_launches == 0 for w in e.workers[:-1])
 
 
 OTHERS = [SamplingParams(temperature=0.7, top_k=5, seed=3, max_new_tokens=4),
@@ -320,7 +320,7 @@ def test_engine_record_length_with_stop_at_eos(runs):
 def test_engine_default_traffic_launches_nothing():
     e = _eng()
     e.generate_ids([PROMPT, [4, 5]], [_off(GREEDY), _off(SEEDED)])
-    assert all(w.logprob_launches == 0 and w.lp_rec is None for w in e.workers)
+    assert all(w.draw.logprob_launches == 0 and w.draw.lp_rec is None for w in e.workers)
     with pytest.raises(ValueError):
         e.generate_ids([PROMPT], [SamplingParams(logprobs=6)])  # above max_logprobs = 5
     e20 = _eng(max_logprobs=20)

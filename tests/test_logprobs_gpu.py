@@ -287,13 +287,13 @@ def test_engine_changing_batch(monkeypatch):
     e = _engine()
     plain = e.generate_ids(PROMPTS, _params(False))
     assert e.generate_ids(PROMPTS, _params(False)) == plain
-    assert sum(w.logprob_launches for w in e.workers) == 0 and e.workers[0].lp_rec is None  # all-default traffic
+    assert sum(w.draw.logprob_launches for w in e.workers) == 0 and e.workers[0].draw.lp_rec is None  # all-default traffic
     native0 = sum(w.native_steps for w in e.workers)
     assert native0 > 0
     sps = _params(True)
     first = _records(e.generate_requests(PROMPTS, sps))
     assert [t for t, _ in first] == plain
-    assert sum(w.logprob_launches for w in e.workers) > 0
+    assert sum(w.draw.logprob_launches for w in e.workers) > 0
     for (toks, lp), sp in zip(first, sps):
         if sp.logprobs is None:
             assert lp is None
@@ -315,7 +315,7 @@ def test_engine_changing_batch(monkeypatch):
     try:
         for _ in range(3):
             assert _records(two.generate_requests(PROMPTS, sps)) == first
-        assert two.workers[1].logprob_launches > 0 and two.workers[0].logprob_launches == 0
+        assert two.workers[1].draw.logprob_launches > 0 and two.workers[0].draw.logprob_launches == 0
         assert all(w.native_steps > 0 for w in two.workers)
     finally:
         two.shutdown()

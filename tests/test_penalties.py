@@ -179,14 +179,14 @@ def test_engine_explicit_zeros_are_the_plain_request(runs):
     e, plain, _ = runs
     z = SamplingParams(greedy=True, max_new_tokens=24, presence_penalty=0.0, frequency_penalty=0.0)
     assert e.generate_ids([PROMPT], [z])[0] == plain
-    assert all(w.penalty_launches == 0 for w in _eng().workers)
+    assert all(w.draw.penalty_launches == 0 for w in _eng().workers)
     seeded = SamplingParams(temperature=1.0, top_k=40, seed=99, max_new_tokens=8)
     zs = SamplingParams(temperature=1.0, top_k=40, seed=99, max_new_tokens=8, presence_penalty=0.0,
                         frequency_penalty=0.0)
     e2 = _eng()
     assert e2.generate_ids([PROMPT], [zs]) == e2.generate_ids([PROMPT], [seeded])
-    assert all(w.penalty_launches == 0 for w in e2.workers)
-    assert sum(w.penalty_launches for w in e.workers) > 0  # the module's engine ran penalised requests
+    assert all(w.draw.penalty_launches == 0 for w in e2.workers)
+    assert sum(w.draw.penalty_launches for w in e.workers) > 0  # the module's engine ran penalised requests
 
 
 def test_engine_mixed_steps_match_separate_forwards():

@@ -240,10 +240,10 @@ def test_engine_penalised_requests_in_a_changing_batch(monkeypatch):
     default = [OTHERS[0], OTHERS[1], SamplingParams(greedy=True, max_new_tokens=N), OTHERS[2], OTHERS[3],
                SamplingParams(temperature=1.0, top_k=40, seed=5, max_new_tokens=N)]
     assert e.generate_ids(PROMPTS, default)[5] == plain_s  # precondition: comparable across compositions
-    assert sum(w.penalty_launches for w in e.workers) == 0  # all-default traffic so far
+    assert sum(w.draw.penalty_launches for w in e.workers) == 0  # all-default traffic so far
     alone_g = e.generate_ids([PROMPTS[2]], [PEN_G])[0]
     alone_s = e.generate_ids([PROMPTS[5]], [PEN_S])[0]
-    assert sum(w.penalty_launches for w in e.workers) > 0
+    assert sum(w.draw.penalty_launches for w in e.workers) > 0
     assert len(alone_g) == N and len(alone_s) == N
     assert len(set(plain)) < N           # precondition: plain greedy repeats a token
     assert alone_g != plain and alone_s != plain_s  # the penalties are live
