@@ -87,6 +87,11 @@ hipError_t lsd_record_tokens(int* hist, int L, int nslots, const int* slots, con
 hipError_t lsd_logit_edits(float* logits, long ld, int B, int V, const int* cnt, const int* tok, const float* val,
                            const int* until, int E, int nslots, const int* slots, const long long* step,
                            float* segmax, long ldseg, hipStream_t st);
+hipError_t lsd_repeat_penalty(float* logits, long ld, int B, int V, const int* plen, const float* rpen, const int* ngram,
+                              const int* tok, int L, int nslots, const int* slots, const long long* step,
+                              float* segmax, long ldseg, hipStream_t st);
+hipError_t lsd_record_context(int* tok, int L, int nslots, const int* plen, const int* slots, const long long* step,
+                              int back, const int* tokens, const int* active, int B, hipStream_t st);
 hipError_t lsd_logprobs(const float* logits, long ld, int B, int V, const int* tokens, const int* nlp, const int* slots,
                         const long long* step, int back, const int* active, float* lp_tok, int* lp_top_id,
                         float* lp_top, int L, int nslots, int W, hipStream_t st);
@@ -788,6 +793,82 @@ void logit_edits(torch::Tensor logits, int64_t V, torch::Tensor cnt, torch::Tens
                             (int)tok.size(0), slots.data_ptr<int>(), sp, sm, ldseg, cur_stream()), "logit_edits");
 }
 
+// HF-style repetition_penalty and no_repeat_ngram_size (repeat.hip).  Row i
+// reads the context of its KV slot s = slots[i] -- tok[s, 0 .. min(plen[s] +
+// step[i], L)), the prompt and then the generated tokens (step absent = draw 0)
+// -- and rewrites, in place on its fp32 logits (repairing linear_f32's segment
+// maxima, when given): every distinct context token by rpen[s], then -inf to
+// every token that would complete an ngram[s]-gram already in the context.
+void repetition(torch::Tensor logits, int64_t V, torch::Tensor plen, torch::Tensor rpen, torch::Tensor ngram,
+                torch::Tensor tok, torch::Tensor slots, c10::optional<torch::Tensor> step,
+                c10::optional<torch::Tensor> segmax) {
+  need(logits, torch::kFloat32, "logits");
+  need(plen, torch::kInt32, "plen");
+  need(rpen, torch::kFloat32, "rpen");
+  need(ngram, torch::kInt32, "ngram");
+  need(tok, torch::kInt32, "tok");
+  need(slots, torch::kInt32, "slots");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= 1 && V <= logits.size(1), "logits [B, >=V]");
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(tok.dim() == 2 && tok.is_contiguous() && plen.is_contiguous() && rpen.is_contiguous() &&
+                  ngram.is_contiguous() && plen.dim() == 1 && rpen.dim() == 1 && ngram.dim() == 1 &&
+                  plen.size(0) == tok.size(0) && rpen.size(0) == tok.size(0) && ngram.size(0) == tok.size(0) &&
+                  tok.size(0) >= 1 && tok.size(1) >= 1,
+              "repetition: the table is contiguous plen / rpen / ngram [slots], tok [slots, max_seq]");
+  TORCH_CHECK(slots.numel() == B && slots.is_contiguous(), "repetition: slots must be contiguous [B]");
+  const long long* sp = nullptr;
+  if (step.has_value()) {
+    need(*step, torch::kInt64, "step");
+    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
+    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
+  }
+  float* sm = nullptr;
+  long ldseg = 0;
+  if (segmax.has_value()) {
+    need(*segmax, torch::kFloat32, "segmax");
+    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && logits.size(1) % 8 == 0 &&
+                    logits.stride(0) % 8 == 0 && segmax->size(1) == logits.size(1) / 8,
+                "segmax must be fp32 [B, logits row length / 8] (row length % 8 == 0)");
+    sm = segmax->data_ptr<float>();
+    ldseg = segmax->stride(0);
+  }
+  check_hip(lsd_repeat_penalty(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V, plen.data_ptr<int>(),
+                               rpen.data_ptr<float>(), ngram.data_ptr<int>(), tok.data_ptr<int>(), (int)tok.size(1),
+                               (int)tok.size(0), slots.data_ptr<int>(), sp, sm, ldseg, cur_stream()), "repetition");
+}
+
+// tok[slots[i], plen[slots[i]] + step[i] - back] = tokens[i] for active rows
+// (all rows without `active`); step absent = the prefill draw, right behind
+// the prompt.  back = 1 after sample_into, which has already advanced the
+// counters.
+void record_context(torch::Tensor tok, torch::Tensor plen, torch::Tensor slots, c10::optional<torch::Tensor> step,
+                    torch::Tensor tokens, c10::optional<torch::Tensor> active, int64_t back) {
+  need(tok, torch::kInt32, "tok");
+  need(plen, torch::kInt32, "plen");
+  need(slots, torch::kInt32, "slots");
+  need(tokens, torch::kInt32, "tokens");
+  TORCH_CHECK(tok.dim() == 2 && tok.is_contiguous() && plen.dim() == 1 && plen.is_contiguous() &&
+                  plen.size(0) == tok.size(0),
+              "record_context: tok must be contiguous int32 [slots, max_seq], plen [slots]");
+  const int64_t B = tokens.numel();
+  TORCH_CHECK(slots.numel() == B && slots.is_contiguous() && tokens.is_contiguous(), "record_context: [B] vectors");
+  const long long* sp = nullptr;
+  if (step.has_value()) {
+    need(*step, torch::kInt64, "step");
+    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
+    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
+  }
+  const int* act = nullptr;
+  if (active.has_value()) {
+    need(*active, torch::kInt32, "active");
+    TORCH_CHECK(active->numel() == B && active->is_contiguous(), "active must be contiguous int32 [B]");
+    act = active->data_ptr<int>();
+  }
+  check_hip(lsd_record_context(tok.data_ptr<int>(), (int)tok.size(1), (int)tok.size(0), plen.data_ptr<int>(),
+                               slots.data_ptr<int>(), sp, (int)back, tokens.data_ptr<int>(), act, (int)B,
+                               cur_stream()), "record_context");
+}
+
 // hist[slots[i], step[i] - back] = tokens[i] for active rows (all rows without
 // `active`); step absent = entry 0 (the prefill draw).  back = 1 after
 // sample_into, which has already advanced the counters.
@@ -939,6 +1020,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("counts"), py::arg("presence"), py::arg("frequency"), py::arg("segmax") = py::none());
   m.def("logit_edits", &logit_edits, py::arg("logits"), py::arg("V"), py::arg("cnt"), py::arg("tok"), py::arg("val"),
         py::arg("until"), py::arg("slots"), py::arg("step") = py::none(), py::arg("segmax") = py::none());
+  m.def("repetition", &repetition, py::arg("logits"), py::arg("V"), py::arg("plen"), py::arg("rpen"), py::arg("ngram"),
+        py::arg("tok"), py::arg("slots"), py::arg("step") = py::none(), py::arg("segmax") = py::none());
+  m.def("record_context", &record_context, py::arg("tok"), py::arg("plen"), py::arg("slots"), py::arg("step"),
+        py::arg("tokens"), py::arg("active") = py::none(), py::arg("back") = 0);
   m.def("record_tokens", &record_tokens, py::arg("hist"), py::arg("slots"), py::arg("step"), py::arg("tokens"),
         py::arg("active") = py::none(), py::arg("back") = 0);
   m.def("logprobs", &logprobs, py::arg("logits"), py::arg("V"), py::arg("tokens"), py::arg("nlp"), py::arg("slots"),

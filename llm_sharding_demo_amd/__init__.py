@@ -42,14 +42,18 @@ class LLM:
         self.tokenizer = load_tokenizer(cfg.model_id, mc.arch, cfg.weights, mc.eos_token_id)
 
     def generate_text(self, prompt: str, max_new_tokens: int = 20, top_p: float = 1.0, min_p: float = 0.0,
-                      presence_penalty: float = 0.0, frequency_penalty: float = 0.0, **sampling) -> dict:
+                      presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                      repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, **sampling) -> dict:
         """Same return contract as the reference /generate: prompt + continuation.
         top_p / min_p, the presence / frequency penalties (over the generated
-        tokens) and the other SamplingParams fields are per call.  With
+        tokens), repetition_penalty / no_repeat_ngram_size (over prompt +
+        generated tokens) and the other SamplingParams fields are per call.  With
         logprobs=n the dict also has "logprobs", as the /generate response."""
         ids = self.tokenizer.encode(prompt)
         sp = SamplingParams(max_new_tokens=max_new_tokens, top_p=top_p, min_p=min_p,
-                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, **sampling)
+                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                            **sampling)
         if max_new_tokens == 0:
             return {"generated": self.tokenizer.decode(ids, skip_special_tokens=True)}
         if sp.logprobs is not None:

@@ -66,6 +66,10 @@ def main(argv=None) -> int:
                    help="subtracted once from the logit of every token generated so far ([-2, 2])")
     g.add_argument("--frequency-penalty", type=float, default=0.0,
                    help="subtracted per earlier occurrence of a generated token ([-2, 2])")
+    g.add_argument("--repetition-penalty", type=float, default=1.0,
+                   help="logits of tokens in the prompt or generated so far: / r if positive, * r if negative ((0, 10])")
+    g.add_argument("--no-repeat-ngram-size", type=int, default=0, metavar="G",
+                   help="never complete a G-gram that is already in the prompt or the output ([0, 32])")
     g.add_argument("--logprobs", type=int, default=None, metavar="N",
                    help="also print every generated token's logprob and its N most likely alternatives")
     g.add_argument("--seed", type=int)
@@ -84,7 +88,9 @@ def main(argv=None) -> int:
         out = llm.generate_text(args.prompt, args.max_new_tokens, greedy=args.greedy,
                                 temperature=args.temperature, top_k=args.top_k, seed=args.seed,
                                 top_p=args.top_p, min_p=args.min_p, presence_penalty=args.presence_penalty,
-                                frequency_penalty=args.frequency_penalty, logprobs=args.logprobs)
+                                frequency_penalty=args.frequency_penalty, logprobs=args.logprobs,
+                                repetition_penalty=args.repetition_penalty,
+                                no_repeat_ngram_size=args.no_repeat_ngram_size)
         print(out)
         llm.engine.shutdown()
         return 0

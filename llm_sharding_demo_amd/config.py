@@ -247,7 +247,25 @@ class SamplingParams:
     token must stay drawable.  All three default to off (None / None / 0), and
     such a request runs nothing extra.  Logprobs are taken after the edits (a
     banned token has logprob -inf), and asking for edits never changes
-    another request's draws."""
+    another request's draws.
+
+    repetition_penalty / no_repeat_ngram_size are the two HF generate() rules
+    that read the prompt: before each draw the request's context is its prompt
+    followed by the tokens it has generated so far.  repetition_penalty = r
+    rewrites the logit of every distinct context token once, logit * r when it
+    is negative and logit / r otherwise (one fp32 rounding; r is used as
+    rounded to fp32; r > 1 discourages repeats, r < 1 encourages them);
+    no_repeat_ngram_size = G then sets to -inf every token that would complete
+    a G-gram already in the context (G = 1: every context token).  Both run on
+    the raw logits ahead of the presence / frequency penalties, the logit
+    edits, temperature, top-k, top-p, min-p and the greedy argmax -- greedy
+    requests get them too -- and logprobs are taken after them.
+    repetition_penalty is finite and in (0, 10], no_repeat_ngram_size an
+    integer in [0, 32]; with an n-gram ban the engine wants prompt +
+    max_new_tokens + banned tokens below the vocabulary size, so that some
+    token always stays drawable.  The defaults (1.0 / 0) are off: such a
+    request runs nothing extra and its prompt never reaches the last stage.
+    Asking never changes another request's draws."""
 
     temperature: float = 0.6
     top_k: int = 40
@@ -263,6 +281,18 @@ class SamplingParams:
     logit_bias: Optional[Mapping[int, float]] = None
     banned_token_ids: Optional[Sequence[int]] = None
     min_new_tokens: int = 0
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+
+    @property
+    def has_context(self) -> bool:
+        """repetition_penalty (as the fp32 the kernel multiplies by) or
+        no_repeat_ngram_size is on: the last stage keeps the request's prompt."""
+        return self.context_knobs() != (1.0, 0)
+
+    def context_knobs(self) -> tuple:
+        """(repetition_penalty rounded to fp32, no_repeat_ngram_size)."""
+        return _fp32(self.repetition_penalty), int(self.no_repeat_ngram_size)
 
     @property
     def has_logit_edits(self) -> bool:
@@ -296,6 +326,13 @@ class SamplingParams:
         m = self.min_new_tokens
         if isinstance(m, bool) or not isinstance(m, int) or not (0 <= m <= self.max_new_tokens):
             raise ValueError("min_new_tokens must be an integer in [0, max_new_tokens]")
+        r, G = self.repetition_penalty, self.no_repeat_ngram_size
+        if isinstance(r, bool) or not isinstance(r, (int, float)) or not math.isfinite(r) or not 0.0 < r <= 10.0:
+            raise ValueError("repetition_penalty must be finite and in (0, 10]")
+        if _fp32(r) == 0.0:
+            raise ValueError("repetition_penalty must be finite and in (0, 10] as a float32")
+        if isinstance(G, bool) or not isinstance(G, int) or not 0 <= G <= 32:
+            raise ValueError("no_repeat_ngram_size must be an integer in [0, 32]")
         if self.logit_bias is not None or self.banned_token_ids is not None:
             if self.logit_bias is not None and not isinstance(self.logit_bias, Mapping):
                 raise ValueError("logit_bias must map token ids to values")

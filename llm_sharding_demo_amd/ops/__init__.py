@@ -129,6 +129,16 @@ class ReferenceBackend(Backend):
         logits, after the penalties and ahead of the sampler; step None = draw 0."""
         ref.logit_edits(logits, table, slots, step, vocab)
 
+    def repetition(self, logits, table, slots, step, vocab: int) -> None:
+        """HF-style repetition_penalty and no_repeat_ngram_size over the rows'
+        prompt + generated tokens (table = the last stage's per-slot plen,
+        rpen, ngram, tok), in place on the fp32 logits, ahead of the penalties,
+        the logit edits and the sampler; step None = draw 0."""
+        ref.repetition(logits, table, slots, step, vocab)
+
+    def record_context(self, table, slots, step, tokens, active=None, back: int = 0) -> None:
+        ref.record_context(table, slots, step, tokens, active, back)
+
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         ref.record_tokens(hist, slots, step, tokens, active, back)
 

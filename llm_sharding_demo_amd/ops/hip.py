@@ -386,6 +386,15 @@ class HipBackend(Backend):
         self.C.logit_edits(logits, vocab, table[0], table[1], table[2], table[3], slots, step,
                            getattr(logits, "_lsd_segmax", None))
 
+    def repetition(self, logits, table, slots, step, vocab: int) -> None:
+        # repeat.hip: one workgroup per row, ahead of the penalty pass; rows whose
+        # slot has both knobs off return at once; the segment maxima are repaired too
+        self.C.repetition(logits, vocab, table[0], table[1], table[2], table[3], slots, step,
+                          getattr(logits, "_lsd_segmax", None))
+
+    def record_context(self, table, slots, step, tokens, active=None, back: int = 0) -> None:
+        self.C.record_context(table[3], table[0], slots, step, tokens, active, back)
+
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         self.C.record_tokens(hist, slots, step, tokens, active, back)
 

@@ -203,6 +203,86 @@ def logit_edits(logits: torch.Tensor, table, slots: torch.Tensor, step: Optional
     return logits if segmax is None else (logits, segmax)
 
 
+def repetition(logits: torch.Tensor, table, slots: torch.Tensor, step: Optional[torch.Tensor], vocab: int,
+               segmax: Optional[torch.Tensor] = None):
+    """HF-style repetition_penalty and no_repeat_ngram_size over prompt +
+    generated tokens, ahead of `penalize`, `logit_edits` and `sample`.
+
+    table = (plen [slots] int, rpen [slots] fp32, ngram [slots] int, tok
+    [slots, L] int): the context of the sequence on KV slot s is x =
+    tok[s, 0 .. n), its prompt followed by its generated tokens, with n =
+    min(plen[s] + c, L) and c = step[r], the row's sampler counter before the
+    draw (step None: c = 0, the prefill draw).  With r = rpen[s], G = ngram[s]:
+
+      1. r != 1: every distinct token t of x in [0, vocab) is rewritten once,
+         logit[t] <- logit[t] * r if logit[t] < 0 else logit[t] / r, in fp32
+         with one rounding (IEEE division; -0.0 and -inf stay what they are);
+      2. G > 0 and n >= G - 1: with tail = x[n - G + 1 .. n), every i in
+         [0, n - G] with x[i .. i + G - 1) == tail (raw ids) bans the token
+         that followed, logit[x[i + G - 1]] <- -inf when it is in [0, vocab);
+         G = 1 bans every context token.  Bans come after the penalty.
+
+    Rows whose slot has r == 1 and G == 0 are untouched.  fp32 `logits`
+    [B, >= vocab] are rewritten in place and returned.  With `segmax`
+    [B, width / 8] (linear_f32's 8-logit segment maxima, padding columns
+    included) the maximum of every segment holding a rewritten token is
+    recomputed from its 8 stored logits in place too, and (logits, segmax) is
+    returned.
+    """
+    assert logits.dtype == torch.float32, "repetition rewrites fp32 logits in place"
+    plen, rpen, ngram, tok = table
+    L = tok.shape[1]
+    for r in range(logits.shape[0]):
+        s = int(slots[r])
+        if not 0 <= s < plen.shape[0]:
+            continue
+        rp, G = rpen[s].float(), min(int(ngram[s]), 32)  # 32: the largest n-gram (SamplingParams.validate)
+        if float(rp) == 1.0 and G <= 0:
+            continue
+        c = int(step[r]) if step is not None else 0
+        n = max(0, min(int(plen[s]) + c, L))
+        x = tok[s, :n].long()
+        touched = []
+        if float(rp) != 1.0:
+            toks = torch.unique(x[(x >= 0) & (x < vocab)])
+            if toks.numel():
+                l = logits[r, toks]
+                logits[r, toks] = torch.where(l < 0, l * rp, l / rp)  # fp32 op fp32: one rounding
+                touched.append(toks)
+        if G > 0 and n >= G:
+            win = x.unfold(0, G, 1)  # [n - G + 1, G]: x[i .. i + G)
+            hit = (win[:, :G - 1] == x[n - G + 1:]).all(dim=1)
+            ban = torch.unique(win[hit, G - 1])
+            ban = ban[(ban >= 0) & (ban < vocab)]
+            if ban.numel():
+                logits[r, ban] = float("-inf")
+                touched.append(ban)
+        if segmax is not None and touched:
+            segs = torch.unique(torch.cat(touched) // 8)
+            idx = segs[:, None] * 8 + torch.arange(8)
+            segmax[r, segs] = logits[r][idx].max(dim=1).values
+    return logits if segmax is None else (logits, segmax)
+
+
+def record_context(table, slots: torch.Tensor, step: Optional[torch.Tensor], tokens: torch.Tensor,
+                   active: Optional[torch.Tensor] = None, back: int = 0) -> None:
+    """tok[slots[i], plen[slots[i]] + step[i] - back] = tokens[i] for active
+    rows (all rows when `active` is None), table as in `repetition`; step
+    None = the prefill draw, right behind the prompt.  back = 1 when the
+    sampler counters were already advanced past the draw.  Positions outside
+    [0, L) and slots outside the table are dropped."""
+    plen, _, _, tok = table
+    for i in range(tokens.shape[0]):
+        if active is not None and int(active[i]) == 0:
+            continue
+        s = int(slots[i])
+        if not 0 <= s < tok.shape[0]:
+            continue
+        j = int(plen[s]) + (int(step[i]) - back if step is not None else 0)
+        if 0 <= j < tok.shape[1]:
+            tok[s, j] = int(tokens[i])
+
+
 def record_tokens(hist: torch.Tensor, slots: torch.Tensor, step: Optional[torch.Tensor], tokens: torch.Tensor,
                   active: Optional[torch.Tensor] = None, back: int = 0) -> None:
     """hist[slots[i], step[i] - back] = tokens[i] for active rows (all rows

@@ -555,8 +555,10 @@ class GlooPlanChannel:
 
             enc = self._enc.get(dst)
             if enc is None:
-                # token ids only to a replica's first stage
-                enc = self._enc[dst] = PlanEncoder(ids=self.P is None or dst % self.P == 0)
+                # token ids only to a replica's first stage -- and to its last one
+                # those of groups whose chunks ask for a context (plan.has_context)
+                enc = self._enc[dst] = PlanEncoder(ids=self.P is None or dst % self.P == 0,
+                                                   ctx_ids=self.P is not None and dst % self.P == self.P - 1)
             rec, payload = enc.encode(obj)
             hdr = torch.from_numpy(rec)
             works = [self._isend(hdr, dst, self.tag), hdr]
@@ -666,8 +668,10 @@ class ShmPlanChannel:
             raise TransportError(f"shared-memory plan ring unavailable: {err or errs}")
         from ..runtime.plan import PlanDecoder, PlanEncoder
 
-        # replica 0's stage 0 is rank 0 itself: its followers never read token ids
-        self._enc = {rep: PlanEncoder(ids=rep > 0) for rep in self.rings}
+        # replica 0's stage 0 is rank 0 itself: its followers never read token ids,
+        # but for a replica's last stage, which reads those of groups whose chunks
+        # ask for a context (plan.has_context)
+        self._enc = {rep: PlanEncoder(ids=rep > 0, ctx_ids=True) for rep in self.rings}
         self._dec = PlanDecoder()
         self.fallback = GlooPlanChannel(transport.plan_pg, tag=1, plans=False)
         self.bytes_sent = 0

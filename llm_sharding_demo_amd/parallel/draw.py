@@ -1,12 +1,14 @@
 """What happens to a row's logits between `lm_head` and the returned token.
 
 A `StageWorker` (parallel/pipeline.py) moves a step through its stage; its
-`DrawStage` decides what runs on the logits of the last stage: the penalty
-pass, the logit edits, the sampler, the token history and the logprob records,
-for the decode rows of a group (`rows`, captured into the decode graphs) and
-for the first draw of a finished prompt (`finals`, eager).  It owns the three
-per-KV-slot tables these passes read and write, and counts the items that ran
-each pass.  Every stage has one; off the last stage it stays empty.
+`DrawStage` decides what runs on the logits of the last stage: the repetition
+pass, the penalty pass, the logit edits, the sampler, the token history, the
+context and the logprob records, for the decode rows of a group (`rows`,
+captured into the decode graphs) and for the first draw of a finished prompt
+(`finals`, eager); `chunks` copies the prompts that the repetition pass reads
+into its table as they are prefilled.  It owns the four per-KV-slot tables
+these passes read and write, and counts the items that ran each pass.  Every
+stage has one; off the last stage it stays empty.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import numpy as np
 import torch
 
 from ..runtime.batch import SamplingState
-from ..runtime.plan import has_edits, row_features
+from ..runtime.plan import has_context, has_edits, row_features
 from ..utils import racecheck
 
 
@@ -41,6 +43,8 @@ class DrawStage(racecheck.Shared):
         self.edit_tab: Optional[tuple] = None  # logit_bias / banned tokens / min_new_tokens, E = max_logit_edits
         self.max_logit_edits = 300
         self.logit_edit_launches = 0
+        self.ctx_tab: Optional[tuple] = None  # repetition_penalty / no_repeat_ngram_size and prompt + generated tokens
+        self.repetition_launches = 0
 
     # ------------------------------------------------------------------
     # tables
@@ -92,12 +96,38 @@ class DrawStage(racecheck.Shared):
                 torch.cuda.current_stream(dev).synchronize()
         return self.edit_tab
 
+    def _ctx_tab(self) -> tuple:
+        """Context table: (plen [KV slots, scratch and compat included] int32,
+        rpen [..] fp32, ngram [..] int32, tok [.., max_seq] int32): a slot's
+        prompt length, repetition_penalty, no_repeat_ngram_size, and its
+        prompt followed by its generated tokens.  Like the edit table's counts
+        its stale parameters ARE read -- by the other rows of a group with a
+        flagged row, and by every pad row on the scratch slot -- so they start
+        at "off" (0, 1.0, 0), visibly to every lane: this thread waits for the
+        fill (_edit_tab).  Allocated once, outside any capture, and never
+        reallocated: captured graphs hold its addresses.  From then on every
+        first chunk of a prompt writes its slot's parameters (chunks)."""
+        if self.ctx_tab is None:
+            S, L, dev = self.slots, self.stage.max_seq, self.stage.device
+            if L > 8192 and dev.type == "cuda":
+                raise ValueError(f"repetition_penalty / no_repeat_ngram_size: max_seq_len {L} exceeds the "
+                                 "8192-token context the repetition kernel's LDS key set holds")
+            self.ctx_tab = (torch.zeros(S, dtype=torch.int32, device=dev),
+                            torch.ones(S, dtype=torch.float32, device=dev),
+                            torch.zeros(S, dtype=torch.int32, device=dev),
+                            torch.zeros(S, L, dtype=torch.int32, device=dev))
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()
+        return self.ctx_tab
+
     def prepare(self, feats: tuple) -> None:
-        """A composition with the features (cut, pen, lp, edit) is being
+        """A composition with the features (cut, pen, lp, edit[, ctx]) is being
         applied: what they need -- the token history, the logprob records, the
-        edit table -- allocated here, on the host side of the change (never
-        inside a capture)."""
-        _, pen, lp, edit = feats
+        edit table, the context table -- allocated here, on the host side of
+        the change (never inside a capture)."""
+        _, pen, lp, edit, *more = feats
+        if more and more[0]:
+            self._ctx_tab()
         if pen:
             self._hist()
         if lp:
@@ -125,6 +155,51 @@ class DrawStage(racecheck.Shared):
             self.logprob_launches += 1
         if gs.edit:
             self.logit_edit_launches += 1
+        if gs.ctx:
+            self.repetition_launches += 1
+
+    def chunks(self, gs, chunks) -> None:
+        """Prefill chunks are about to run on the last stage (every prefill
+        item, eager or replayed; never inside a capture).  Nothing while no
+        context table exists and no chunk asks for one.  Once it exists every
+        chunk that opens a prompt writes its slot's (plen, rpen, ngram), the
+        defaults included -- a request that reuses a slot must not inherit its
+        predecessor's -- and every chunk that asks writes its token ids to
+        tok[slot, start : start + qlen].  ONE host-to-device copy through the
+        group's pinned staging ring: [slots H | plen H | rpen bits H | ngram H]
+        of the H opening chunks, then [flat table index T | ids T]."""
+        flagged = [c for c in chunks if c.ctx and c.qlen]
+        if self.ctx_tab is None and not flagged:
+            return
+        plen, rpen, ngram, tok = self._ctx_tab()
+        heads = [c for c in chunks if c.start == 0]
+        if not heads and not flagged:
+            return
+        L = tok.shape[1]
+        for c in flagged:
+            if isinstance(c.ids, range) or c.start + c.qlen > L or not 0 <= c.slot < self.slots:
+                raise ValueError("a prefill chunk with repetition_penalty / no_repeat_ngram_size reached the last "
+                                 f"stage without its token ids, or past max_seq_len = {L}")
+        cols = [[c.slot for c in heads], [c.plen for c in heads],
+                np.array([c.rpen for c in heads], dtype=np.float32).view(np.int32), [c.ngram for c in heads]]
+        if flagged:
+            cols += [np.concatenate([c.slot * L + c.start + np.arange(c.qlen) for c in flagged]),
+                     [t for c in flagged for t in c.ids]]
+        arr = np.concatenate([np.asarray(c, dtype=np.int32) for c in cols])
+        dev = self.stage.device
+        if dev.type == "cuda":
+            buf = torch.empty(arr.size, dtype=torch.int32, device=dev)
+            self._stage_h2d(gs, arr, buf)
+        else:
+            buf = torch.from_numpy(arr)
+        slots, pl, rp, ng, *ids = buf.split([len(c) for c in cols])
+        if heads:
+            at = slots.long()
+            plen.index_copy_(0, at, pl)
+            rpen.index_copy_(0, at, rp.view(torch.float32))
+            ngram.index_copy_(0, at, ng)
+        if ids:
+            tok.view(-1).index_copy_(0, ids[0].long(), ids[1])
 
     def rows(self, gs, logits: torch.Tensor, b: int, meta) -> None:
         """Decode rows of a group: draw into the token-return vector, advance
@@ -133,9 +208,13 @@ class DrawStage(racecheck.Shared):
         edited row runs the edit pass right ahead of the sampler (after the
         penalties; the counters it compares are the ones the draw uses).  One
         with a logprob row then runs the logprob kernel over the logits the
-        sampler drew from.  Any other runs the sampler alone."""
+        sampler drew from.  One with a repetition penalty or an n-gram ban runs
+        the repetition pass first of all, and record_context behind the draw.
+        Any other runs the sampler alone."""
         be, V = self.stage.backend, self.stage.cfg.vocab_size
         slots, step, out = gs.slots[:b], gs.sstep[:b], gs.tokret[:b]
+        if gs.ctx:
+            be.repetition(logits, self.ctx_tab, slots, step, V)
         if gs.pen:
             be.penalize(logits, self.pen_hist, slots, step, gs.presence[:b], gs.frequency[:b], V)
         if gs.edit:
@@ -144,6 +223,8 @@ class DrawStage(racecheck.Shared):
         if gs.pen:
             # the sampler has advanced the counters: the draw used counter - 1
             be.record_tokens(self.pen_hist, slots, step, out, gs.active[:b], 1)
+        if gs.ctx:
+            be.record_context(self.ctx_tab, slots, step, out, gs.active[:b], 1)
         if gs.lp:
             be.logprobs(logits, out, gs.nlp[:b], slots, step, gs.active[:b], self.lp_rec, V, 1)
 
@@ -157,14 +238,19 @@ class DrawStage(racecheck.Shared):
         predecessor's entries.  Behind it the token goes into the history when
         a chunk carries a penalty (its history is empty, so this draw needs no
         penalty pass), and its logprob record is taken from `logits` when one
-        asked."""
+        asked.  A chunk with a repetition penalty or an n-gram ban runs the
+        repetition pass first of all -- over its prompt, which `chunks` has
+        put into the context table -- and the token goes in behind the prompt."""
         be, V, dev = self.stage.backend, self.stage.cfg.vocab_size, self.stage.device
         _, pen, lp = row_features(fc)
-        ed = has_edits(fc)
+        ed, cx = has_edits(fc), has_context(fc)
         tab = self._edit_tab() if ed or self.edit_tab is not None else None
         slots = nlp = None
-        if tab is not None or pen or lp:
+        if tab is not None or pen or lp or cx:
             slots, nlp = self._stage_finals(gs, fc, tab)
+        if cx:
+            be.repetition(logits, self._ctx_tab(), slots, None, V)
+            self.repetition_launches += 1
         if ed:
             be.logit_edits(logits, tab, slots, None, V)
             self.logit_edit_launches += 1
@@ -172,6 +258,8 @@ class DrawStage(racecheck.Shared):
         if pen:
             be.record_tokens(self._hist(), slots, None, ids, None, 0)
             self.penalty_launches += 1
+        if cx:
+            be.record_context(self.ctx_tab, slots, None, ids, None, 0)
         if lp:
             be.logprobs(logits, ids, nlp, slots, None, None, self._lp_rec(), V, 0)
             self.logprob_launches += 1

@@ -43,8 +43,8 @@ import torch
 
 from ..models.stage import StageModel
 from ..runtime.batch import BatchMeta, MixedMeta
-from ..runtime.plan import (NO_FEATURES, ROW_FIELDS, GroupPlan, StepPlan, device_fields, has_edits, pack_rows,
-                            packed_size, row_features)
+from ..runtime.plan import (NO_FEATURES, ROW_FIELDS, GroupPlan, StepPlan, device_fields, has_context, has_edits,
+                            pack_rows, packed_size, row_features)
 from ..utils.tracing import trace_range
 from ..utils import racecheck
 from .comm import Handle, SendHandle, Transport
@@ -207,6 +207,11 @@ class GroupState(racecheck.Shared):
         # packed row state and apply_rows' record do not depend on it -- and the
         # last part of the decode graphs' key
         self.edit = False
+        # a row with a repetition penalty or an n-gram ban (plan.has_context):
+        # the repetition pass runs ahead of the penalties and record_context
+        # behind the draw.  A flag like `edit` -- a per-slot table, no row
+        # vector -- and the fifth feature in the decode graphs' key
+        self.ctx = False
         if w.last:
             for f in ROW_FIELDS:  # the sampler's row vectors, idle: temp, topk, greedy, seeds, sstep, ...
                 setattr(self, f.vec, torch.full((cap,), f.idle, dtype=getattr(torch, f.dtype), device=dev))
@@ -911,6 +916,7 @@ class StageWorker(racecheck.Shared):
         st, dev = self.stage, self.device
         ch = gp.chunks
         b = gp.b
+        self.draw.chunks(gs, ch)
         pf, ids, _ = self._chunk_meta(gs, ch, tuple(c.qlen for c in ch))
         dec = gs.meta(b, gp.ctxb)
         mm = MixedMeta(token_slots=torch.cat([dec.token_slots, pf.token_slots]),
@@ -940,24 +946,27 @@ class StageWorker(racecheck.Shared):
         self.mixed_items += 1
 
     def _features(self, gp: GroupPlan, gs: GroupState) -> tuple:
-        """(cut, pen, lp, edit) of the group once this item ran: the current
+        """(cut, pen, lp, edit, ctx) of the group once this item ran: the current
         ones, or those of the item's new composition -- one pass over its rows,
-        kept with the plan item, so whichever path runs it reads the same four."""
+        kept with the plan item, so whichever path runs it reads the same five."""
         if gp.rows is None:
-            return gs.cut, gs.pen, gs.lp, gs.edit
+            return gs.cut, gs.pen, gs.lp, gs.edit, gs.ctx
         if not self.last:
-            return NO_FEATURES + (False,)
+            return NO_FEATURES + (False, False)
         if gp.feats is None:
             gp.feats = row_features(gp.rows)
         if gp.edit is None:
             gp.edit = has_edits(gp.rows)
-        return gp.feats + (gp.edit,)
+        if gp.ctx is None:
+            gp.ctx = has_context(gp.rows)
+        return gp.feats + (gp.edit, gp.ctx)
 
     def _set_features(self, gs: GroupState, feats: tuple) -> None:
         """A composition change is being applied: the group's features from
         now on, and the tables they need, on the host side of the change (never
         inside a capture)."""
-        gs.cut, gs.pen, gs.lp, gs.edit = feats
+        gs.cut, gs.pen, gs.lp, gs.edit, *more = feats  # a 4-tuple: no context
+        gs.ctx = bool(more and more[0])
         self.draw.prepare(feats)
 
     def _apply_rows(self, gp: GroupPlan, gs: GroupState) -> None:
@@ -1037,6 +1046,11 @@ class StageWorker(racecheck.Shared):
         ch = gp.chunks
         finals = [i for i, c in enumerate(ch) if c.final]
         v = gp.g & 1  # alternating-split variant of this group
+        if self.last:
+            # prompts of requests with a repetition penalty or an n-gram ban go
+            # into their slots' context: ahead of the forward or the replay,
+            # never inside a capture (_prefill_graph captures the forward alone)
+            self.draw.chunks(gs, ch)
         x, meta = self._prefill_graph(gp, gs, inp, v) if self._prefill_graphs() else (None, None)
         if x is None:
             meta, ids, _ = self._chunk_meta(gs, ch, tuple(c.qlen for c in ch))
@@ -1173,7 +1187,7 @@ class StageWorker(racecheck.Shared):
         slot[2] = True
 
     def _decode(self, gp: GroupPlan, gs: GroupState, inp: torch.Tensor, io: bool = False) -> torch.Tensor:
-        key = (gp.b, gp.ctxb, io, gs.cut, gs.pen, gs.lp, gs.edit)
+        key = (gp.b, gp.ctxb, io, gs.cut, gs.pen, gs.lp, gs.edit, gs.ctx)
         lane = self.lane_of(gp.g)
         self.draw.count(gs)
 

@@ -383,6 +383,15 @@ class Engine(racecheck.Shared):
         if len(prompt) + sp.max_new_tokens > self.max_seq:
             raise ValueError(f"prompt ({len(prompt)}) + max_new_tokens ({sp.max_new_tokens}) "
                              f"exceeds the context limit {self.max_seq}")
+        if sp.no_repeat_ngram_size > 0:
+            # an n-gram ban can take every context token out (G = 1 does): with
+            # the request's own bans that must leave a token to draw
+            ed = sp.logit_edits(self.mcfg.eos_token_id)
+            banned = sum(v == float("-inf") for v in ed[1]) if ed else 0
+            if len(prompt) + sp.max_new_tokens + banned >= self.mcfg.vocab_size:
+                raise ValueError(f"no_repeat_ngram_size: prompt ({len(prompt)}) + max_new_tokens "
+                                 f"({sp.max_new_tokens}) + banned tokens ({banned}) must stay below the "
+                                 f"vocabulary size {self.mcfg.vocab_size}")
 
     def _validate_edits(self, sp: SamplingParams) -> None:
         """What SamplingParams.validate cannot know: the ids of logit_bias and

@@ -54,10 +54,20 @@ class Chunk:
     # the entries, SamplingParams.logit_edits' (tokens, values, untils) sorted by
     # token: on the final chunk only, whose stage writes them to the slot's table
     edits: Optional[tuple] = None
+    # repetition_penalty / no_repeat_ngram_size and the prompt's length: the two
+    # knobs that read the prompt.  On every chunk of such a request, whose ids
+    # the last stage copies into the slot's context (has_context)
+    rpen: float = 1.0
+    ngram: int = 0
+    plen: int = 0
 
     @property
     def qlen(self) -> int:
         return len(self.ids)
+
+    @property
+    def ctx(self) -> bool:
+        return self.rpen != 1.0 or self.ngram != 0
 
 
 @dataclass
@@ -81,6 +91,7 @@ class Row:
     frequency: float = 0.0
     logprobs: int = -1
     nedits: int = 0     # logit-edit entries in the slot's table: the group's edit gate (has_edits)
+    ctx: int = 0        # repetition_penalty / no_repeat_ngram_size asked: the group's context gate (has_context)
 
 
 def has_edits(xs) -> bool:
@@ -89,6 +100,14 @@ def has_edits(xs) -> bool:
     packed row state and apply_rows' record hold -- the edit pass adds no row
     vector."""
     return any(map(operator.attrgetter("nedits"), xs))
+
+
+def has_context(xs) -> bool:
+    """Some Row / Chunk asks for repetition_penalty or no_repeat_ngram_size:
+    the repetition pass runs ahead of the penalties and the slot's context is
+    kept (a chunk's prompt ids, a row's draws).  A flag of its own like
+    has_edits: the pass reads a per-slot table and adds no row vector."""
+    return any(map(operator.attrgetter("ctx"), xs))
 
 
 @dataclass
@@ -107,6 +126,8 @@ class GroupPlan:
     feats: Optional[tuple] = field(default=None, compare=False, repr=False)
     # has_edits(rows), from the scheduler or once a last stage has computed it (never sent)
     edit: Optional[bool] = field(default=None, compare=False, repr=False)
+    # has_context(rows), likewise (never sent)
+    ctx: Optional[bool] = field(default=None, compare=False, repr=False)
 
     @property
     def n_final(self) -> int:
@@ -328,22 +349,46 @@ def _unpack_cols(cls, ints_names: tuple, ints, floats, **more) -> list:
                                              for nm, d in _DEFAULTS[cls]))))
 
 
-def _pack_group(gp: GroupPlan, ids: bool):
+def _pack_group(gp: GroupPlan, ids: bool, ctx_ids: bool = False):
+    """ctx_ids: the destination runs a last stage, which copies the prompt ids
+    of chunks that ask for a context into its table -- a group with such a
+    chunk travels with its ids."""
     import numpy as np
 
     ch = None
+    cx = has_context(gp.chunks)
     if gp.chunks:
         c = gp.chunks
         tok = None
-        if ids:
+        if ids or (ctx_ids and cx):
             tok = np.fromiter(itertools.chain.from_iterable(x.ids for x in c), dtype=np.int32,
                               count=sum(len(x.ids) for x in c))
         ch = _pack_cols(c, _CHUNK_INTS) + (np.array([x.seed for x in c], dtype=np.int64), tok)
     rows = _pack_cols(gp.rows, _ROW_INTS) if gp.rows is not None else None
     out = (gp.g, gp.ret, gp.n, gp.b, gp.ctxb, gp.kind, gp.fwd_rows, ch, rows)
+    cx = cx or (gp.rows is not None and has_context(gp.rows))
     if has_edits(gp.chunks) or (gp.rows is not None and has_edits(gp.rows)):
         out += (_pack_edits(gp),)  # a group without edits: the 9-tuple, as before
+    elif cx:
+        out += (None,)
+    if cx:
+        out += (_pack_context(gp),)  # one more element: 11, the edits' place held by None without any
     return out
+
+
+def _pack_context(gp: GroupPlan) -> tuple:
+    """The context knobs of a group, the last element of its wire tuple: (the
+    rows' ctx column or None, the chunks' (rpen float64, ngram int32, plen
+    int32) columns or None)."""
+    import numpy as np
+
+    rows = np.array([r.ctx for r in gp.rows], dtype=np.int32) if gp.rows is not None else None
+    ch = None
+    if gp.chunks:
+        ch = (np.array([c.rpen for c in gp.chunks], dtype=np.float64),
+              np.array([c.ngram for c in gp.chunks], dtype=np.int32),
+              np.array([c.plen for c in gp.chunks], dtype=np.int32))
+    return rows, ch
 
 
 def _pack_edits(gp: GroupPlan) -> tuple:
@@ -378,7 +423,7 @@ def _unpack_edits(ed) -> tuple:
     return (rows.tolist() if rows is not None else None), n.tolist(), edits
 
 
-def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None) -> GroupPlan:
+def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None) -> GroupPlan:
     """Inverse of _pack_group.  Chunks sent without their token ids carry
     range(len) in their place (their stage reads only the lengths)."""
     gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb, kind=kind, fwd_rows=fwd_rows)
@@ -389,6 +434,12 @@ def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None) -> Grou
             more_r = dict(nedits=rn)
         if cn is not None:
             more_c = dict(nedits=cn, edits=ce)
+    if cx is not None:
+        rc, cc = cx
+        if rc is not None:
+            more_r["ctx"] = rc.tolist()
+        if cc is not None:
+            more_c.update(zip(("rpen", "ngram", "plen"), (col.tolist() for col in cc)))
     if ch is not None:
         ints, floats, seeds, tok = ch
         gp.chunks = _unpack_cols(Chunk, _CHUNK_INTS, ints, floats, seed=seeds.tolist(),
@@ -401,30 +452,33 @@ def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None) -> Grou
 class _PlanPickler(pickle.Pickler):
     """Pickles every GroupPlan through _pack_group (ids: with token ids)."""
 
-    def __init__(self, file, ids: bool):
+    def __init__(self, file, ids: bool, ctx_ids: bool = False):
         super().__init__(file, protocol=pickle.HIGHEST_PROTOCOL)
-        self.ids = ids
+        self.ids, self.ctx_ids = ids, ctx_ids
 
     def reducer_override(self, obj):
         if type(obj) is GroupPlan:
-            return _unpack_group, _pack_group(obj, self.ids)
+            return _unpack_group, _pack_group(obj, self.ids, self.ctx_ids)
         return NotImplemented
 
 
-def _plan_dumps(plan: StepPlan, ids: bool) -> bytes:
+def _plan_dumps(plan: StepPlan, ids: bool, ctx_ids: bool = False) -> bytes:
     buf = io.BytesIO()
-    _PlanPickler(buf, ids).dump(plan)
+    _PlanPickler(buf, ids, ctx_ids).dump(plan)
     return buf.getvalue()
 
 
 class PlanEncoder:
     """Per-destination encoder (remembers what it sent last for REPEAT).
     ids=False: the destination stages never read prefill token ids (every
-    stage but a replica's first), so the chunks travel without them."""
+    stage but a replica's first), so the chunks travel without them --
+    except, with ctx_ids=True (a last stage is among the destinations), those
+    of a group with a chunk that asks for repetition_penalty or
+    no_repeat_ngram_size: the last stage keeps that prompt."""
 
-    def __init__(self, ids: bool = True):
+    def __init__(self, ids: bool = True, ctx_ids: bool = False):
         self._prev = None  # (step, replica, flags, groups) of the last plan sent
-        self.ids = ids
+        self.ids, self.ctx_ids = ids, ctx_ids
 
     def encode(self, plan: StepPlan):
         """-> (int32 numpy record, pickle payload bytes or None)."""
@@ -434,7 +488,7 @@ class PlanEncoder:
         flags = (_F_TIMING if plan.timing else 0) | (_F_END if plan.end else 0) | (_F_STOP if plan.stop else 0)
         groups = _steady_groups(plan)
         if groups is None:
-            payload = _plan_dumps(plan, self.ids)
+            payload = _plan_dumps(plan, self.ids, self.ctx_ids)
             rec[0], rec[1] = MAGIC_PICKLE, len(payload)
             self._prev = None
             return rec, payload

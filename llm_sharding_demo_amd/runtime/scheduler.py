@@ -531,6 +531,7 @@ class _Meta:
     values: tuple = ((), ())  # plan.sampler_values: the chunk / row sampler fields
     logprobs: int = -1  # alternatives asked with every token's logprob (-1: no records)
     edits: Optional[tuple] = None  # SamplingParams.logit_edits: (tokens, values, untils) sorted by token
+    context: Optional[tuple] = None  # SamplingParams.context_knobs: (repetition_penalty as fp32, no_repeat_ngram_size)
     rep: int = 0        # replica and KV slot, from the request's first prefill chunk
     slot: int = -1
     done: bool = False  # finished by this scheduler (plain flag: the readout loop's hot path)
@@ -564,6 +565,7 @@ class Scheduler(racecheck.Shared):
         self.stats = {"steps": 0, "joins": 0, "leaves": 0, "max_rows": 0, "captures": 0, "deferred": 0}
         self._rng = engine._rng
         self._edited = 0  # live requests with logit edits: _group looks at chunks and rows only then
+        self._contexts = 0  # live requests with repetition_penalty / no_repeat_ngram_size, likewise
 
     # -- admission ---------------------------------------------------------
     def submit(self, prompt_ids: List[int], params: SamplingParams) -> Request:
@@ -628,6 +630,9 @@ class Scheduler(racecheck.Shared):
             if p.has_logit_edits:
                 meta[i].edits = p.logit_edits(self.eng.mcfg.eos_token_id)
                 self._edited += 1
+            if p.has_context:
+                meta[i].context = p.context_knobs()
+                self._contexts += 1
             lens.append(len(req.prompt_ids))
             wants.append(p.max_new_tokens)
             stops.append(bool(p.stop_at_eos))
@@ -689,8 +694,21 @@ class Scheduler(racecheck.Shared):
                     ed = meta[r.seq].edits
                     if ed is not None:
                         r.nedits = len(ed[0])
+        if self._contexts:
+            # requests with a repetition penalty or an n-gram ban: every chunk
+            # brings the knobs and the prompt's length (the last stage copies
+            # its ids into the slot's context), every row the gate
+            for c in gp.chunks:
+                m = meta[c.seq]
+                if m.context is not None:
+                    (c.rpen, c.ngram), c.plen = m.context, len(m.req.prompt_ids)
+            if changed:
+                for r in gp.rows:
+                    if meta[r.seq].context is not None:
+                        r.ctx = 1
         if changed:
             gp.edit = bool(self._edited) and any(r.nedits for r in gp.rows)
+            gp.ctx = bool(self._contexts) and any(r.ctx for r in gp.rows)
         return gp
 
     # -- token readout -----------------------------------------------------------
@@ -775,6 +793,8 @@ class Scheduler(racecheck.Shared):
                 m = self.meta.pop(sid, None)
                 if m is not None and m.edits is not None:
                     self._edited -= 1
+                if m is not None and m.context is not None:
+                    self._contexts -= 1
                 if m is not None and flags & EV_FINISH and not m.done:
                     m.done = True
                     self._finish(m, done.get(sid, []))
@@ -813,7 +833,7 @@ class Scheduler(racecheck.Shared):
                 m.done = True
                 m.req.finish(error=err)
         self.meta.clear()
-        self._edited = 0
+        self._edited = self._contexts = 0
         self.core.reset()
         self.readouts.clear()
         with self._plock:

@@ -16,7 +16,7 @@ Roles (env SHARD_ROLE, `server.py:21`):
   all          one process answers every endpoint (debug)
 Additions: optional sampling fields on /generate (temperature, top_k, top_p,
 min_p, presence_penalty, frequency_penalty, logprobs, logit_bias, banned_token_ids,
-min_new_tokens, greedy, seed, stop_at_eos;
+min_new_tokens, repetition_penalty, no_repeat_ngram_size, greedy, seed, stop_at_eos;
 defaults = reference sampler; with logprobs the response gains a "logprobs" object
 beside "generated"), 422 on empty/over-long
 prompts (instead of the reference's 500, quirk Q9), GET /health, GET /metrics
@@ -71,6 +71,10 @@ class GenerateReq(BaseModel):
     logit_bias: Optional[Dict[str, float]] = None
     banned_token_ids: Optional[List[int]] = None
     min_new_tokens: int = 0
+    # the two rules over prompt + output: logits of tokens already there / r (* r when negative),
+    # r in (0, 10]; and no G-gram (G in [0, 32]) that is already there is completed again
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
 
 
 def logprobs_json(lp) -> dict:
@@ -187,7 +191,9 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                             stop_at_eos=req.stop_at_eos, top_p=req.top_p, min_p=req.min_p,
                             presence_penalty=req.presence_penalty, frequency_penalty=req.frequency_penalty,
                             logprobs=req.logprobs, logit_bias=req.logit_bias,
-                            banned_token_ids=req.banned_token_ids, min_new_tokens=req.min_new_tokens)
+                            banned_token_ids=req.banned_token_ids, min_new_tokens=req.min_new_tokens,
+                            repetition_penalty=req.repetition_penalty,
+                            no_repeat_ngram_size=req.no_repeat_ngram_size)
         if req.max_new_tokens == 0 and req.logprobs is None:
             return {"generated": tok.decode(ids, skip_special_tokens=True)}
         if not ids:
@@ -276,7 +282,8 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
     full-sequence recompute on every step, hidden states relayed through here.
     Kept for deployments where the shards are separate hosts without xGMI.
     This relay keeps the reference's sampler: presence_penalty and
-    frequency_penalty are ignored here; logit_bias, banned_token_ids and
+    frequency_penalty, repetition_penalty and no_repeat_ngram_size are ignored
+    here; logit_bias, banned_token_ids and
     min_new_tokens are applied on the host (ops/reference.py logit_edits; ids
     outside the vocabulary are ignored).  records=True: -> (tokens, the logprob
     records of a request that asked for them or None), computed on the host
