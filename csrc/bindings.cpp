@@ -87,6 +87,8 @@ hipError_t lsd_record_tokens(int* hist, int L, int nslots, const int* slots, con
 hipError_t lsd_logit_edits(float* logits, long ld, int B, int V, const int* cnt, const int* tok, const float* val,
                            const int* until, int E, int nslots, const int* slots, const long long* step,
                            float* segmax, long ldseg, hipStream_t st);
+hipError_t lsd_allow_mask(float* logits, long ld, int B, int V, const int* on, const int* bits, int W, int nslots,
+                          const int* slots, float* segmax, long ldseg, hipStream_t st);
 hipError_t lsd_repeat_penalty(float* logits, long ld, int B, int V, const int* plen, const float* rpen, const int* ngram,
                               const int* tok, int L, int nslots, const int* slots, const long long* step,
                               float* segmax, long ldseg, hipStream_t st);
@@ -793,6 +795,38 @@ void logit_edits(torch::Tensor logits, int64_t V, torch::Tensor cnt, torch::Tens
                             (int)tok.size(0), slots.data_ptr<int>(), sp, sm, ldseg, cur_stream()), "logit_edits");
 }
 
+// Per-request allowed_token_ids (allow_mask.hip).  Row i whose KV slot s =
+// slots[i] has on[s] != 0 gets, in place on its fp32 logits (repairing
+// linear_f32's segment maxima, when given), -inf at every token of [0, V) whose
+// bit -- bit t & 31 of bits[s, t >> 5] -- is clear.  What the arguments must
+// satisfy beyond their types and layouts is lsd_allow_mask's to refuse.
+void allow_mask(torch::Tensor logits, int64_t V, torch::Tensor on, torch::Tensor bits, torch::Tensor slots,
+                c10::optional<torch::Tensor> segmax) {
+  need(logits, torch::kFloat32, "logits");
+  need(on, torch::kInt32, "on");
+  need(bits, torch::kInt32, "bits");
+  need(slots, torch::kInt32, "slots");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits [B, width]");
+  const int64_t B = logits.size(0), ld = logits.size(1);
+  TORCH_CHECK(B <= 1 || logits.stride(0) == ld, "allow_mask: the rows of logits must be dense");
+  TORCH_CHECK(V >= 0 && V <= INT32_MAX && bits.dim() == 2 && bits.is_contiguous() && on.is_contiguous() &&
+                  on.dim() == 1 && on.size(0) == bits.size(0),
+              "allow_mask: the table is contiguous on [slots], bits [slots, W]");
+  TORCH_CHECK(slots.numel() == B && slots.is_contiguous(), "allow_mask: slots must be contiguous [B]");
+  float* sm = nullptr;
+  long ldseg = 0;
+  if (segmax.has_value()) {
+    need(*segmax, torch::kFloat32, "segmax");
+    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && segmax->size(1) * 8 >= ld,
+                "segmax must be fp32 [B, >= logits row length / 8]");
+    sm = segmax->data_ptr<float>();
+    ldseg = B <= 1 ? segmax->size(1) : segmax->stride(0);
+  }
+  check_hip(lsd_allow_mask(logits.data_ptr<float>(), ld, (int)B, (int)V, on.data_ptr<int>(), bits.data_ptr<int>(),
+                           (int)bits.size(1), (int)on.size(0), slots.data_ptr<int>(), sm, ldseg, cur_stream()),
+            "allow_mask");
+}
+
 // HF-style repetition_penalty and no_repeat_ngram_size (repeat.hip).  Row i
 // reads the context of its KV slot s = slots[i] -- tok[s, 0 .. min(plen[s] +
 // step[i], L)), the prompt and then the generated tokens (step absent = draw 0)
@@ -1020,6 +1054,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("counts"), py::arg("presence"), py::arg("frequency"), py::arg("segmax") = py::none());
   m.def("logit_edits", &logit_edits, py::arg("logits"), py::arg("V"), py::arg("cnt"), py::arg("tok"), py::arg("val"),
         py::arg("until"), py::arg("slots"), py::arg("step") = py::none(), py::arg("segmax") = py::none());
+  m.def("allow_mask", &allow_mask, py::arg("logits"), py::arg("V"), py::arg("on"), py::arg("bits"), py::arg("slots"),
+        py::arg("segmax") = py::none());
   m.def("repetition", &repetition, py::arg("logits"), py::arg("V"), py::arg("plen"), py::arg("rpen"), py::arg("ngram"),
         py::arg("tok"), py::arg("slots"), py::arg("step") = py::none(), py::arg("segmax") = py::none());
   m.def("record_context", &record_context, py::arg("tok"), py::arg("plen"), py::arg("slots"), py::arg("step"),

@@ -197,6 +197,16 @@ def _token_id(t) -> int:
     raise ValueError(f"token ids must be integers (or decimal strings), got {t!r}")
 
 
+def _strict_id(t) -> int:
+    """A token id given as an integer (no bool, no string, no float)."""
+    try:
+        if not isinstance(t, (bool, str, bytes, float)):
+            return operator.index(t)
+    except TypeError:
+        pass
+    raise ValueError(f"token ids must be integers, got {t!r}")
+
+
 @dataclass
 class SamplingParams:
     """Per-request sampling.  Defaults reproduce `server.py:187-205`.
@@ -265,7 +275,25 @@ class SamplingParams:
     max_new_tokens + banned tokens below the vocabulary size, so that some
     token always stays drawable.  The defaults (1.0 / 0) are off: such a
     request runs nothing extra and its prompt never reaches the last stage.
-    Asking never changes another request's draws."""
+    Asking never changes another request's draws.
+
+    allowed_token_ids: None (off; nothing runs, travels or is allocated for
+    the request) or a non-empty list of token ids of the vocabulary: before
+    every draw, the prefill draw (draw 0) included, every token of the
+    vocabulary that is not in the list has its fp32 logit set to -inf.  The
+    mask is the last edit of the logits: after the repetition pass, the
+    presence / frequency penalties and the logit edits, ahead of temperature,
+    top-k, top-p, min-p and the greedy argmax -- greedy requests are masked
+    too.  Duplicates collapse.  top_k may exceed the number of allowed tokens:
+    a -inf candidate has probability 0 and is never drawn.  Logprobs are taken
+    after the mask: a disallowed token has logprob -inf, the log-sum-exp runs
+    over what is left, and alternatives past the allowed set come back as
+    -inf.  Some allowed token must stay drawable after the request's own bans
+    (banned_token_ids, and the EOS of min_new_tokens > 0); with an n-gram ban
+    the engine wants prompt + max_new_tokens below the number of allowed
+    tokens that are not banned.  The list travels as a bitmask over the
+    vocabulary, so its length costs nothing.  Asking never changes another
+    request's draws."""
 
     temperature: float = 0.6
     top_k: int = 40
@@ -283,6 +311,28 @@ class SamplingParams:
     min_new_tokens: int = 0
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
+    allowed_token_ids: Optional[Sequence[int]] = None
+
+    def allowed_set(self) -> Optional[frozenset]:
+        """The distinct allowed token ids, or None without a list."""
+        if self.allowed_token_ids is None:
+            return None
+        return frozenset(_strict_id(t) for t in self.allowed_token_ids)
+
+    def allowed_mask(self, words: int):
+        """The allowed list as the packed words of the last stage's mask
+        table: int32 numpy [words], bit t & 31 of word t >> 5 set for every
+        allowed t (ids at or past 32 * words are an error), or None."""
+        if self.allowed_token_ids is None:
+            return None
+        import numpy as np
+
+        t = np.array(sorted(self.allowed_set()), dtype=np.int64)
+        if t.size and (t[0] < 0 or t[-1] >= 32 * words):
+            raise ValueError(f"allowed_token_ids must lie in [0, {32 * words})")
+        w = np.zeros(words, dtype=np.uint32)
+        np.bitwise_or.at(w, t >> 5, np.uint32(1) << (t & 31).astype(np.uint32))
+        return w.view(np.int32)
 
     @property
     def has_context(self) -> bool:
@@ -333,6 +383,15 @@ class SamplingParams:
             raise ValueError("repetition_penalty must be finite and in (0, 10] as a float32")
         if isinstance(G, bool) or not isinstance(G, int) or not 0 <= G <= 32:
             raise ValueError("no_repeat_ngram_size must be an integer in [0, 32]")
+        if self.allowed_token_ids is not None:
+            a = self.allowed_token_ids
+            if isinstance(a, (str, bytes, Mapping)) or not hasattr(a, "__iter__"):
+                raise ValueError("allowed_token_ids must be a sequence of token ids")
+            ids = self.allowed_set()
+            if not ids:
+                raise ValueError("allowed_token_ids must not be empty (None turns the mask off)")
+            if any(t < 0 or t > INT32_MAX for t in ids):
+                raise ValueError("allowed_token_ids must be >= 0")
         if self.logit_bias is not None or self.banned_token_ids is not None:
             if self.logit_bias is not None and not isinstance(self.logit_bias, Mapping):
                 raise ValueError("logit_bias must map token ids to values")

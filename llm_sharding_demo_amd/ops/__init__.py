@@ -139,6 +139,12 @@ class ReferenceBackend(Backend):
     def record_context(self, table, slots, step, tokens, active=None, back: int = 0) -> None:
         ref.record_context(table, slots, step, tokens, active, back)
 
+    def allow_mask(self, logits, table, slots, vocab: int) -> None:
+        """The rows' allowed_token_ids (table = the last stage's per-slot on,
+        bits): -inf at every token of [0, vocab) whose bit is clear, in place
+        on the fp32 logits, after the edits and ahead of the sampler."""
+        ref.allow_mask(logits, table, slots, vocab)
+
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         ref.record_tokens(hist, slots, step, tokens, active, back)
 

@@ -395,6 +395,11 @@ class HipBackend(Backend):
     def record_context(self, table, slots, step, tokens, active=None, back: int = 0) -> None:
         self.C.record_context(table[3], table[0], slots, step, tokens, active, back)
 
+    def allow_mask(self, logits, table, slots, vocab: int) -> None:
+        # allow_mask.hip: one workgroup per row, ahead of the draw; rows whose
+        # slot gave no allowed list return at once; the segment maxima are repaired too
+        self.C.allow_mask(logits, vocab, table[0], table[1], slots, getattr(logits, "_lsd_segmax", None))
+
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         self.C.record_tokens(hist, slots, step, tokens, active, back)
 

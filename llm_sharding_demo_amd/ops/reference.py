@@ -203,6 +203,45 @@ def logit_edits(logits: torch.Tensor, table, slots: torch.Tensor, step: Optional
     return logits if segmax is None else (logits, segmax)
 
 
+def allow_mask(logits: torch.Tensor, table, slots: torch.Tensor, vocab: int,
+               segmax: Optional[torch.Tensor] = None):
+    """Per-request allowed_token_ids: a vocabulary bitmask, after `repetition`,
+    `penalize` and `logit_edits` and ahead of `sample` and `logprobs`.
+
+    table = (on [slots] int32, bits [slots, W] int32), W >= ceil(width / 32)
+    for logits of `width` columns: token t is allowed when bit t & 31 of word
+    t >> 5 is set.  Row r reads its KV slot s = slots[r]: a slot outside
+    [0, slots) or with on[s] == 0 leaves the row untouched, whatever its bits
+    hold; otherwise every t in [0, vocab) with a clear bit gets
+        logit[t] <- -inf
+    a pure select: every other logit keeps its bits.  Columns at or past
+    `vocab` are never written, whatever their bits.
+
+    fp32 `logits` [B, >= vocab] are rewritten in place and returned.  With
+    `segmax` [B, width / 8] (linear_f32's 8-logit segment maxima, padding
+    columns included) every segment that holds a cleared t < vocab is
+    recomputed as the maximum of its 8 stored logits, in place too -- every
+    other segment is left as it is -- and (logits, segmax) is returned.
+    """
+    assert logits.dtype == torch.float32, "allow_mask rewrites fp32 logits in place"
+    on, bits = table
+    width, dev = logits.shape[1], logits.device
+    assert bits.shape[1] * 32 >= width and vocab <= width
+    t = torch.arange(vocab, device=dev)
+    for r in range(logits.shape[0]):
+        s = int(slots[r])
+        if not 0 <= s < on.shape[0] or int(on[s]) == 0:
+            continue
+        clear = ((bits[s].to(dev)[t >> 5] >> (t & 31)) & 1) == 0
+        logits[r, :vocab] = torch.where(clear, torch.full_like(logits[r, :vocab], -math.inf), logits[r, :vocab])
+        if segmax is not None:
+            segs = torch.unique(t[clear] >> 3)
+            if segs.numel():
+                idx = segs[:, None] * 8 + torch.arange(8, device=dev)
+                segmax[r, segs] = logits[r][idx].max(dim=1).values
+    return logits if segmax is None else (logits, segmax)
+
+
 def repetition(logits: torch.Tensor, table, slots: torch.Tensor, step: Optional[torch.Tensor], vocab: int,
                segmax: Optional[torch.Tensor] = None):
     """HF-style repetition_penalty and no_repeat_ngram_size over prompt +

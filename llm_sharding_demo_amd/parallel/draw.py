@@ -2,11 +2,11 @@
 
 A `StageWorker` (parallel/pipeline.py) moves a step through its stage; its
 `DrawStage` decides what runs on the logits of the last stage: the repetition
-pass, the penalty pass, the logit edits, the sampler, the token history, the
-context and the logprob records, for the decode rows of a group (`rows`,
+pass, the penalty pass, the logit edits, the allowed-token mask, the sampler,
+the token history, the context and the logprob records, for the decode rows of a group (`rows`,
 captured into the decode graphs) and for the first draw of a finished prompt
 (`finals`, eager); `chunks` copies the prompts that the repetition pass reads
-into its table as they are prefilled.  It owns the four per-KV-slot tables
+into its table as they are prefilled.  It owns the five per-KV-slot tables
 these passes read and write, and counts the items that ran each pass.  Every
 stage has one; off the last stage it stays empty.
 """
@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from ..runtime.batch import SamplingState
-from ..runtime.plan import has_context, has_edits, row_features
+from ..runtime.plan import has_allow, has_context, has_edits, row_features
 from ..utils import racecheck
 
 
@@ -45,6 +45,8 @@ class DrawStage(racecheck.Shared):
         self.logit_edit_launches = 0
         self.ctx_tab: Optional[tuple] = None  # repetition_penalty / no_repeat_ngram_size and prompt + generated tokens
         self.repetition_launches = 0
+        self.allow_tab: Optional[tuple] = None  # allowed_token_ids: a flag and a bitmask over the logits' columns
+        self.allow_launches = 0
 
     # ------------------------------------------------------------------
     # tables
@@ -120,14 +122,37 @@ class DrawStage(racecheck.Shared):
                 torch.cuda.current_stream(dev).synchronize()
         return self.ctx_tab
 
+    def _allow_tab(self) -> tuple:
+        """Allowed-token table: (on [KV slots, scratch and compat included]
+        int32, bits [.., W] int32), W = one bit per column of the padded
+        vocabulary: token t of a slot is allowed when bit t & 31 of word t >> 5
+        is set, and the mask pass touches only rows whose slot has on != 0.
+        Like the edit table's counts its stale flags ARE read -- by the other
+        rows of a group with an asking row, and by every pad row on the
+        scratch slot -- so they start at zero, visibly to every lane: this
+        thread waits for the fill (_edit_tab).  Allocated once, outside any
+        capture, and never reallocated: captured graphs hold its addresses.
+        From then on every final chunk writes its slot's flag (finals)."""
+        if self.allow_tab is None:
+            S, dev = self.slots, self.stage.device
+            W = (self.stage.cfg.vocab_padded + 31) // 32
+            self.allow_tab = (torch.zeros(S, dtype=torch.int32, device=dev),
+                              torch.zeros(S, W, dtype=torch.int32, device=dev))
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()
+        return self.allow_tab
+
     def prepare(self, feats: tuple) -> None:
-        """A composition with the features (cut, pen, lp, edit[, ctx]) is being
-        applied: what they need -- the token history, the logprob records, the
-        edit table, the context table -- allocated here, on the host side of
-        the change (never inside a capture)."""
+        """A composition with the features (cut, pen, lp, edit[, ctx[, allow]])
+        is being applied: what they need -- the token history, the logprob
+        records, the edit table, the context table, the allowed-token table --
+        allocated here, on the host side of the change (never inside a
+        capture)."""
         _, pen, lp, edit, *more = feats
         if more and more[0]:
             self._ctx_tab()
+        if more[1:] and more[1]:
+            self._allow_tab()
         if pen:
             self._hist()
         if lp:
@@ -157,6 +182,8 @@ class DrawStage(racecheck.Shared):
             self.logit_edit_launches += 1
         if gs.ctx:
             self.repetition_launches += 1
+        if gs.allow:
+            self.allow_launches += 1
 
     def chunks(self, gs, chunks) -> None:
         """Prefill chunks are about to run on the last stage (every prefill
@@ -210,6 +237,8 @@ class DrawStage(racecheck.Shared):
         with a logprob row then runs the logprob kernel over the logits the
         sampler drew from.  One with a repetition penalty or an n-gram ban runs
         the repetition pass first of all, and record_context behind the draw.
+        One with a row that gave allowed_token_ids runs the mask pass last of
+        the edits: the sampler and the logprob kernel see the masked logits.
         Any other runs the sampler alone."""
         be, V = self.stage.backend, self.stage.cfg.vocab_size
         slots, step, out = gs.slots[:b], gs.sstep[:b], gs.tokret[:b]
@@ -219,6 +248,8 @@ class DrawStage(racecheck.Shared):
             be.penalize(logits, self.pen_hist, slots, step, gs.presence[:b], gs.frequency[:b], V)
         if gs.edit:
             be.logit_edits(logits, self.edit_tab, slots, step, V)
+        if gs.allow:
+            be.allow_mask(logits, self.allow_tab, slots, V)
         be.sample_into(logits, gs.samp(b), V, out, meta)
         if gs.pen:
             # the sampler has advanced the counters: the draw used counter - 1
@@ -240,20 +271,28 @@ class DrawStage(racecheck.Shared):
         penalty pass), and its logprob record is taken from `logits` when one
         asked.  A chunk with a repetition penalty or an n-gram ban runs the
         repetition pass first of all -- over its prompt, which `chunks` has
-        put into the context table -- and the token goes in behind the prompt."""
+        put into the context table -- and the token goes in behind the prompt.
+        The allowed-token table goes like the edit table: nothing without a
+        table and without an asking chunk; once it exists every final chunk
+        writes its slot's flag, zero included, an asking one its mask words too,
+        and the mask pass runs last ahead of the draw."""
         be, V, dev = self.stage.backend, self.stage.cfg.vocab_size, self.stage.device
         _, pen, lp = row_features(fc)
-        ed, cx = has_edits(fc), has_context(fc)
+        ed, cx, al = has_edits(fc), has_context(fc), has_allow(fc)
         tab = self._edit_tab() if ed or self.edit_tab is not None else None
+        atab = self._allow_tab() if al or self.allow_tab is not None else None
         slots = nlp = None
-        if tab is not None or pen or lp or cx:
-            slots, nlp = self._stage_finals(gs, fc, tab)
+        if tab is not None or atab is not None or pen or lp or cx:
+            slots, nlp = self._stage_finals(gs, fc, tab, atab)
         if cx:
             be.repetition(logits, self._ctx_tab(), slots, None, V)
             self.repetition_launches += 1
         if ed:
             be.logit_edits(logits, tab, slots, None, V)
             self.logit_edit_launches += 1
+        if al:
+            be.allow_mask(logits, atab, slots, V)
+            self.allow_launches += 1
         ids = be.sample(logits, SamplingState.of(fc, dev), V)
         if pen:
             be.record_tokens(self._hist(), slots, None, ids, None, 0)
@@ -265,12 +304,15 @@ class DrawStage(racecheck.Shared):
             self.logprob_launches += 1
         return ids
 
-    def _stage_finals(self, gs, fc, tab: Optional[tuple]) -> tuple:
+    def _stage_finals(self, gs, fc, tab: Optional[tuple], atab: Optional[tuple] = None) -> tuple:
         """What the passes around the first draw of `fc` read, on the device
         in ONE host-to-device copy through the group's pinned staging ring:
         [slots J | logprob widths J | edit counts J], then with n edits among
         them [flat table index n | tokens n | value bits n | untils n].  With
-        a table, its rows are written from the copy.  -> (slots, widths)."""
+        a table, its rows are written from the copy.  With an allowed-token
+        table `atab` then [allow flags J], and with k asking chunks among them
+        [their slots k | their mask words k W]; its flags and rows are written
+        from the copy too.  -> (slots, widths)."""
         cols = [[c.slot for c in fc], [c.logprobs for c in fc], [c.nedits for c in fc]]
         if tab is not None:
             cnt, tok, val, until = tab
@@ -283,6 +325,16 @@ class DrawStage(racecheck.Shared):
                          [t for e in ent for t in e[0]],
                          np.array([v for e in ent for v in e[1]], dtype=np.float32).view(np.int32),
                          [u for e in ent for u in e[2]]]
+        ask = []
+        if atab is not None:
+            on, bits = atab
+            W = bits.shape[1]
+            ask = [c for c in fc if c.allow]
+            if any(c.mask is None or len(c.mask) != 4 * W or not 0 <= c.slot < self.slots for c in ask):
+                raise ValueError(f"a final chunk's allowed-token mask is missing or not {W} words long")
+            cols += [[1 if c.allow else 0 for c in fc]]
+            if ask:
+                cols += [[c.slot for c in ask], np.frombuffer(b"".join(c.mask for c in ask), dtype=np.int32)]
         arr = np.concatenate([np.asarray(c, dtype=np.int32) for c in cols])
         dev = self.stage.device
         if dev.type == "cuda":
@@ -290,9 +342,14 @@ class DrawStage(racecheck.Shared):
             self._stage_h2d(gs, arr, buf)
         else:
             buf = torch.from_numpy(arr)
-        slots, nlp, counts, *edits = buf.split([len(c) for c in cols])
+        slots, nlp, counts, *more = buf.split([len(c) for c in cols])
+        edits, more = (more[:4], more[4:]) if tab is not None and ent else ((), more)
         if tab is not None:
             cnt.index_copy_(0, slots.long(), counts)
+        if atab is not None:
+            on.index_copy_(0, slots.long(), more[0])
+            if ask:
+                bits.index_copy_(0, more[1].long(), more[2].view(len(ask), W))
         if edits:
             at, t, v, u = edits
             at = at.long()

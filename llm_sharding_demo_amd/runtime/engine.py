@@ -373,6 +373,7 @@ class Engine(racecheck.Shared):
         sp.validate(self.cfg.max_logprobs, self.cfg.max_logit_edits)
         if sp.has_logit_edits:
             self._validate_edits(sp)
+        left = self._validate_allowed(sp) if sp.allowed_token_ids is not None else None
         if sp.logprobs is not None and self.mode == "dist":
             # the records stay on the last stage until the request finishes and
             # are read from there directly; fetching them over the control
@@ -388,7 +389,13 @@ class Engine(racecheck.Shared):
             # the request's own bans that must leave a token to draw
             ed = sp.logit_edits(self.mcfg.eos_token_id)
             banned = sum(v == float("-inf") for v in ed[1]) if ed else 0
-            if len(prompt) + sp.max_new_tokens + banned >= self.mcfg.vocab_size:
+            if left is not None:
+                # with an allowed list only its tokens that are not banned can be drawn
+                if len(prompt) + sp.max_new_tokens >= left:
+                    raise ValueError(f"no_repeat_ngram_size: prompt ({len(prompt)}) + max_new_tokens "
+                                     f"({sp.max_new_tokens}) must stay below the {left} allowed tokens that "
+                                     "are not banned")
+            elif len(prompt) + sp.max_new_tokens + banned >= self.mcfg.vocab_size:
                 raise ValueError(f"no_repeat_ngram_size: prompt ({len(prompt)}) + max_new_tokens "
                                  f"({sp.max_new_tokens}) + banned tokens ({banned}) must stay below the "
                                  f"vocabulary size {self.mcfg.vocab_size}")
@@ -405,6 +412,29 @@ class Engine(racecheck.Shared):
         banned = {t for t, v in zip(toks, vals) if v == float("-inf") and 0 <= t < V}
         if len(banned) >= V:
             raise ValueError("banned_token_ids and min_new_tokens leave no token to draw")
+
+    def _validate_allowed(self, sp: SamplingParams) -> int:
+        """What SamplingParams.validate cannot know of allowed_token_ids: the
+        ids lie in the vocabulary, and the request's own bans (the EOS of
+        min_new_tokens among them) leave one of them to draw.  -> the allowed
+        tokens that are not banned."""
+        V = self.mcfg.vocab_size
+        allowed = sp.allowed_set()
+        for t in allowed:
+            if not 0 <= t < V:
+                raise ValueError(f"allowed_token_ids: token id {t} outside the vocabulary [0, {V})")
+        ed = sp.logit_edits(self.mcfg.eos_token_id)
+        banned = {t for t, v in zip(ed[0], ed[1]) if v == float("-inf")} if ed else set()
+        left = len(allowed - banned)
+        if left == 0:
+            raise ValueError("allowed_token_ids: banned_token_ids and min_new_tokens leave no allowed token to draw")
+        return left
+
+    @property
+    def mask_words(self) -> int:
+        """int32 words of a request's allowed-token mask: one bit per column of
+        the widest logits a last stage draws from (the padded vocabulary)."""
+        return (self.mcfg.vocab_padded + 31) // 32
 
     def submit(self, prompt_ids: List[int], params: SamplingParams) -> Request:
         """Thread-safe: queue one request; the driver loop admits it at the

@@ -60,6 +60,12 @@ class Chunk:
     rpen: float = 1.0
     ngram: int = 0
     plen: int = 0
+    # allowed_token_ids: 1 on every chunk of an asking request (has_allow); the
+    # packed mask (the bytes of SamplingParams.allowed_mask's int32 words, one bit
+    # per logits column) on the final chunk only, whose stage writes it to the
+    # slot's table
+    allow: int = 0
+    mask: Optional[bytes] = None
 
     @property
     def qlen(self) -> int:
@@ -92,6 +98,7 @@ class Row:
     logprobs: int = -1
     nedits: int = 0     # logit-edit entries in the slot's table: the group's edit gate (has_edits)
     ctx: int = 0        # repetition_penalty / no_repeat_ngram_size asked: the group's context gate (has_context)
+    allow: int = 0      # allowed_token_ids asked: the group's mask gate (has_allow)
 
 
 def has_edits(xs) -> bool:
@@ -108,6 +115,13 @@ def has_context(xs) -> bool:
     kept (a chunk's prompt ids, a row's draws).  A flag of its own like
     has_edits: the pass reads a per-slot table and adds no row vector."""
     return any(map(operator.attrgetter("ctx"), xs))
+
+
+def has_allow(xs) -> bool:
+    """Some Row / Chunk asks for allowed_token_ids: the mask pass runs right
+    ahead of the draw.  A flag of its own like has_edits: the pass reads a
+    per-slot table and adds no row vector."""
+    return any(map(operator.attrgetter("allow"), xs))
 
 
 @dataclass
@@ -128,6 +142,8 @@ class GroupPlan:
     edit: Optional[bool] = field(default=None, compare=False, repr=False)
     # has_context(rows), likewise (never sent)
     ctx: Optional[bool] = field(default=None, compare=False, repr=False)
+    # has_allow(rows), likewise (never sent)
+    allow: Optional[bool] = field(default=None, compare=False, repr=False)
 
     @property
     def n_final(self) -> int:
@@ -373,7 +389,28 @@ def _pack_group(gp: GroupPlan, ids: bool, ctx_ids: bool = False):
         out += (None,)
     if cx:
         out += (_pack_context(gp),)  # one more element: 11, the edits' place held by None without any
+    if has_allow(gp.chunks) or (gp.rows is not None and has_allow(gp.rows)):
+        # one more: 12, the edits' and the context's places held by None without any
+        out += (None,) * (11 - len(out)) + (_pack_allow(gp),)
     return out
+
+
+def _pack_allow(gp: GroupPlan) -> tuple:
+    """The allowed-token masks of a group, the last element of its wire tuple:
+    (the rows' allow column or None, the chunks' -- (allow column, which chunks
+    carry their mask (the final asking ones), those k chunks' packed words
+    [k W] int32 in chunk order) -- or None).  Packed words: the size does not depend
+    on how many tokens a list names."""
+    import numpy as np
+
+    rows = np.array([r.allow for r in gp.rows], dtype=np.int8) if gp.rows is not None else None
+    ch = None
+    if gp.chunks:
+        masks = [c.mask for c in gp.chunks if c.mask is not None]
+        ch = (np.array([c.allow for c in gp.chunks], dtype=np.int8),
+              np.array([len(c.mask) if c.mask is not None else -1 for c in gp.chunks], dtype=np.int32),
+              np.frombuffer(b"".join(masks), dtype=np.int32) if masks else None)
+    return rows, ch
 
 
 def _pack_context(gp: GroupPlan) -> tuple:
@@ -423,7 +460,7 @@ def _unpack_edits(ed) -> tuple:
     return (rows.tolist() if rows is not None else None), n.tolist(), edits
 
 
-def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None) -> GroupPlan:
+def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None, al=None) -> GroupPlan:
     """Inverse of _pack_group.  Chunks sent without their token ids carry
     range(len) in their place (their stage reads only the lengths)."""
     gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb, kind=kind, fwd_rows=fwd_rows)
@@ -440,6 +477,17 @@ def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None
             more_r["ctx"] = rc.tolist()
         if cc is not None:
             more_c.update(zip(("rpen", "ngram", "plen"), (col.tolist() for col in cc)))
+    if al is not None:
+        ra, ca = al
+        if ra is not None:
+            more_r["allow"] = ra.tolist()
+        if ca is not None:
+            flag, lens, words = ca
+            buf, at, masks = (words.tobytes() if words is not None else b""), 0, []
+            for n in lens.tolist():
+                masks.append(buf[at: at + n] if n >= 0 else None)
+                at += max(n, 0)
+            more_c.update(allow=flag.tolist(), mask=masks)
     if ch is not None:
         ints, floats, seeds, tok = ch
         gp.chunks = _unpack_cols(Chunk, _CHUNK_INTS, ints, floats, seed=seeds.tolist(),

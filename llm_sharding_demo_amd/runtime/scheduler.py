@@ -532,6 +532,7 @@ class _Meta:
     logprobs: int = -1  # alternatives asked with every token's logprob (-1: no records)
     edits: Optional[tuple] = None  # SamplingParams.logit_edits: (tokens, values, untils) sorted by token
     context: Optional[tuple] = None  # SamplingParams.context_knobs: (repetition_penalty as fp32, no_repeat_ngram_size)
+    mask: Optional[bytes] = None  # the bytes of SamplingParams.allowed_mask: the allowed list as packed int32 words
     rep: int = 0        # replica and KV slot, from the request's first prefill chunk
     slot: int = -1
     done: bool = False  # finished by this scheduler (plain flag: the readout loop's hot path)
@@ -566,6 +567,7 @@ class Scheduler(racecheck.Shared):
         self._rng = engine._rng
         self._edited = 0  # live requests with logit edits: _group looks at chunks and rows only then
         self._contexts = 0  # live requests with repetition_penalty / no_repeat_ngram_size, likewise
+        self._allowing = 0  # live requests with allowed_token_ids, likewise
 
     # -- admission ---------------------------------------------------------
     def submit(self, prompt_ids: List[int], params: SamplingParams) -> Request:
@@ -633,6 +635,9 @@ class Scheduler(racecheck.Shared):
             if p.has_context:
                 meta[i].context = p.context_knobs()
                 self._contexts += 1
+            if p.allowed_token_ids is not None:
+                meta[i].mask = p.allowed_mask(self.eng.mask_words).tobytes()
+                self._allowing += 1
             lens.append(len(req.prompt_ids))
             wants.append(p.max_new_tokens)
             stops.append(bool(p.stop_at_eos))
@@ -706,9 +711,24 @@ class Scheduler(racecheck.Shared):
                 for r in gp.rows:
                     if meta[r.seq].context is not None:
                         r.ctx = 1
+        if self._allowing:
+            # requests with allowed_token_ids: every chunk and row carries the
+            # gate, the final chunk the packed mask (the last stage writes it to
+            # the slot's table ahead of the prefill draw)
+            for c in gp.chunks:
+                mk = meta[c.seq].mask
+                if mk is not None:
+                    c.allow = 1
+                    if c.final:
+                        c.mask = mk
+            if changed:
+                for r in gp.rows:
+                    if meta[r.seq].mask is not None:
+                        r.allow = 1
         if changed:
             gp.edit = bool(self._edited) and any(r.nedits for r in gp.rows)
             gp.ctx = bool(self._contexts) and any(r.ctx for r in gp.rows)
+            gp.allow = bool(self._allowing) and any(r.allow for r in gp.rows)
         return gp
 
     # -- token readout -----------------------------------------------------------
@@ -795,6 +815,8 @@ class Scheduler(racecheck.Shared):
                     self._edited -= 1
                 if m is not None and m.context is not None:
                     self._contexts -= 1
+                if m is not None and m.mask is not None:
+                    self._allowing -= 1
                 if m is not None and flags & EV_FINISH and not m.done:
                     m.done = True
                     self._finish(m, done.get(sid, []))
@@ -833,7 +855,7 @@ class Scheduler(racecheck.Shared):
                 m.done = True
                 m.req.finish(error=err)
         self.meta.clear()
-        self._edited = self._contexts = 0
+        self._edited = self._contexts = self._allowing = 0
         self.core.reset()
         self.readouts.clear()
         with self._plock:

@@ -6,7 +6,7 @@ otherwise the string "Error: {code} - {text}"; network failures return
 "Request failed: {exc}".  The optional sampling fields of /generate
 (temperature, top_k, top_p, min_p, presence_penalty, frequency_penalty, logprobs,
 logit_bias, banned_token_ids, min_new_tokens, repetition_penalty,
-no_repeat_ngram_size, greedy, seed, stop_at_eos) are sent
+no_repeat_ngram_size, allowed_token_ids, greedy, seed, stop_at_eos) are sent
 when given; with logprobs the returned dict
 has a "logprobs" object beside "generated".
 """
@@ -23,14 +23,15 @@ def generate_text(prompt: str, max_new_tokens: int = 20, url: str = None,
                   presence_penalty: float = None, frequency_penalty: float = None,
                   logprobs: int = None, logit_bias: dict = None, banned_token_ids: list = None,
                   min_new_tokens: int = None, repetition_penalty: float = None,
-                  no_repeat_ngram_size: int = None, **sampling) -> Union[dict, str]:
+                  no_repeat_ngram_size: int = None, allowed_token_ids: list = None, **sampling) -> Union[dict, str]:
     import requests
 
     payload = {"prompt": prompt, "max_new_tokens": max_new_tokens}
     sampling.update(top_p=top_p, min_p=min_p, presence_penalty=presence_penalty,
                     frequency_penalty=frequency_penalty, logprobs=logprobs, logit_bias=logit_bias,
                     banned_token_ids=banned_token_ids, min_new_tokens=min_new_tokens,
-                    repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
+                    repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                    allowed_token_ids=allowed_token_ids)
     payload.update({k: v for k, v in sampling.items() if v is not None})
     try:
         r = requests.post(url or COORDINATOR_URL, json=payload, timeout=timeout)

@@ -16,7 +16,8 @@ Roles (env SHARD_ROLE, `server.py:21`):
   all          one process answers every endpoint (debug)
 Additions: optional sampling fields on /generate (temperature, top_k, top_p,
 min_p, presence_penalty, frequency_penalty, logprobs, logit_bias, banned_token_ids,
-min_new_tokens, repetition_penalty, no_repeat_ngram_size, greedy, seed, stop_at_eos;
+min_new_tokens, repetition_penalty, no_repeat_ngram_size, allowed_token_ids, greedy, seed,
+stop_at_eos;
 defaults = reference sampler; with logprobs the response gains a "logprobs" object
 beside "generated"), 422 on empty/over-long
 prompts (instead of the reference's 500, quirk Q9), GET /health, GET /metrics
@@ -75,6 +76,8 @@ class GenerateReq(BaseModel):
     # r in (0, 10]; and no G-gram (G in [0, 32]) that is already there is completed again
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
+    # the only tokens that may be drawn (None = the whole vocabulary): every other logit is -inf
+    allowed_token_ids: Optional[List[int]] = None
 
 
 def logprobs_json(lp) -> dict:
@@ -193,7 +196,8 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                             logprobs=req.logprobs, logit_bias=req.logit_bias,
                             banned_token_ids=req.banned_token_ids, min_new_tokens=req.min_new_tokens,
                             repetition_penalty=req.repetition_penalty,
-                            no_repeat_ngram_size=req.no_repeat_ngram_size)
+                            no_repeat_ngram_size=req.no_repeat_ngram_size,
+                            allowed_token_ids=req.allowed_token_ids)
         if req.max_new_tokens == 0 and req.logprobs is None:
             return {"generated": tok.decode(ids, skip_special_tokens=True)}
         if not ids:
@@ -285,7 +289,8 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
     frequency_penalty, repetition_penalty and no_repeat_ngram_size are ignored
     here; logit_bias, banned_token_ids and
     min_new_tokens are applied on the host (ops/reference.py logit_edits; ids
-    outside the vocabulary are ignored).  records=True: -> (tokens, the logprob
+    outside the vocabulary are ignored), allowed_token_ids behind them
+    (ops/reference.py allow_mask).  records=True: -> (tokens, the logprob
     records of a request that asked for them or None), computed on the host
     from the logits this loop already holds (ops/reference.py logprobs)."""
     import requests
@@ -306,6 +311,10 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
         table = tuple(torch.tensor([col], dtype=dt) for col, dt in zip(
             sp.logit_edits(cfg.model.eos_token_id), (torch.int32, torch.float32, torch.int32)))
         table = (torch.tensor([table[0].shape[1]], dtype=torch.int32),) + table
+    allow = None
+    if sp.allowed_token_ids is not None:
+        allow = (torch.ones(1, dtype=torch.int32),
+                 torch.from_numpy(sp.allowed_mask((cfg.model.vocab_padded + 31) // 32))[None])
     seq = list(ids)
     url_a = f"http://{cfg.shard_a_service}:{cfg.shard_port}/forward"
     url_b = f"http://{cfg.shard_b_service}:{cfg.shard_port}/forward_b"
@@ -318,6 +327,8 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
         logits = torch.tensor(r2.json()["logits"], dtype=torch.float32)[0, -1:]
         if table is not None:
             ref.logit_edits(logits, table, torch.tensor([0]), torch.tensor([step]), vocab)
+        if allow is not None:
+            ref.allow_mask(logits, allow, torch.tensor([0]), min(vocab, logits.shape[1]))
         u = counter_uniform(torch.tensor([seed]), torch.tensor([step]))
         nxt = int(ref.sample(logits, torch.tensor([sp.temperature]), torch.tensor([sp.top_k]),
                              torch.tensor([1 if sp.greedy else 0]), u, vocab,
