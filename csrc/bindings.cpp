@@ -89,6 +89,9 @@ hipError_t lsd_logit_edits(float* logits, long ld, int B, int V, const int* cnt,
                            float* segmax, long ldseg, hipStream_t st);
 hipError_t lsd_allow_mask(float* logits, long ld, int B, int V, const int* on, const int* bits, int W, int nslots,
                           const int* slots, float* segmax, long ldseg, hipStream_t st);
+hipError_t lsd_bad_words(float* logits, long ld, int B, int V, const int* cnt, const int* end, int N, const int* btok,
+                         int T, const int* plen, const int* ctok, int L, int nslots, const int* slots,
+                         const long long* step, float* segmax, long ldseg, hipStream_t st);
 hipError_t lsd_repeat_penalty(float* logits, long ld, int B, int V, const int* plen, const float* rpen, const int* ngram,
                               const int* tok, int L, int nslots, const int* slots, const long long* step,
                               float* segmax, long ldseg, hipStream_t st);
@@ -871,6 +874,56 @@ void repetition(torch::Tensor logits, int64_t V, torch::Tensor plen, torch::Tens
                                (int)tok.size(0), slots.data_ptr<int>(), sp, sm, ldseg, cur_stream()), "repetition");
 }
 
+// Per-request bad_words (bad_words.hip).  Row i whose KV slot s = slots[i] has
+// cnt[s] > 0 reads the context of the slot -- ctok[s, 0 .. min(plen[s] +
+// step[i], L)), the prompt and then the generated tokens (step absent = draw 0)
+// -- and gets, in place on its fp32 logits (repairing linear_f32's segment
+// maxima, when given), -inf at the last token of every sequence e < cnt[s] --
+// btok[s, end[s, e - 1] .. end[s, e]) -- whose other tokens the context ends
+// with.  What the arguments must satisfy beyond their types and layouts is
+// lsd_bad_words' to refuse.
+void bad_words(torch::Tensor logits, int64_t V, torch::Tensor cnt, torch::Tensor end, torch::Tensor btok,
+               torch::Tensor plen, torch::Tensor ctok, torch::Tensor slots, c10::optional<torch::Tensor> step,
+               c10::optional<torch::Tensor> segmax) {
+  need(logits, torch::kFloat32, "logits");
+  need(cnt, torch::kInt32, "cnt");
+  need(end, torch::kInt32, "end");
+  need(btok, torch::kInt32, "tok");
+  need(plen, torch::kInt32, "plen");
+  need(ctok, torch::kInt32, "context tok");
+  need(slots, torch::kInt32, "slots");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= 1 && V <= logits.size(1), "logits [B, >=V]");
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(cnt.dim() == 1 && end.dim() == 2 && btok.dim() == 2 && cnt.is_contiguous() && end.is_contiguous() &&
+                  btok.is_contiguous() && end.size(0) == cnt.size(0) && btok.size(0) == cnt.size(0) &&
+                  cnt.size(0) >= 1 && end.size(1) >= 1 && btok.size(1) >= 1,
+              "bad_words: the table is contiguous cnt [slots], end [slots, N], tok [slots, T]");
+  TORCH_CHECK(ctok.dim() == 2 && ctok.is_contiguous() && plen.dim() == 1 && plen.is_contiguous() &&
+                  plen.size(0) == cnt.size(0) && ctok.size(0) == cnt.size(0) && ctok.size(1) >= 1,
+              "bad_words: the context table is contiguous plen [slots], tok [slots, max_seq] over the same slots");
+  TORCH_CHECK(slots.numel() == B && slots.is_contiguous(), "bad_words: slots must be contiguous [B]");
+  const long long* sp = nullptr;
+  if (step.has_value()) {
+    need(*step, torch::kInt64, "step");
+    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
+    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
+  }
+  float* sm = nullptr;
+  long ldseg = 0;
+  if (segmax.has_value()) {
+    need(*segmax, torch::kFloat32, "segmax");
+    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && logits.size(1) % 8 == 0 &&
+                    logits.stride(0) % 8 == 0 && segmax->size(1) == logits.size(1) / 8,
+                "segmax must be fp32 [B, logits row length / 8] (row length % 8 == 0)");
+    sm = segmax->data_ptr<float>();
+    ldseg = segmax->stride(0);
+  }
+  check_hip(lsd_bad_words(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V, cnt.data_ptr<int>(),
+                          end.data_ptr<int>(), (int)end.size(1), btok.data_ptr<int>(), (int)btok.size(1),
+                          plen.data_ptr<int>(), ctok.data_ptr<int>(), (int)ctok.size(1), (int)cnt.size(0),
+                          slots.data_ptr<int>(), sp, sm, ldseg, cur_stream()), "bad_words");
+}
+
 // tok[slots[i], plen[slots[i]] + step[i] - back] = tokens[i] for active rows
 // (all rows without `active`); step absent = the prefill draw, right behind
 // the prompt.  back = 1 after sample_into, which has already advanced the
@@ -1058,6 +1111,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("segmax") = py::none());
   m.def("repetition", &repetition, py::arg("logits"), py::arg("V"), py::arg("plen"), py::arg("rpen"), py::arg("ngram"),
         py::arg("tok"), py::arg("slots"), py::arg("step") = py::none(), py::arg("segmax") = py::none());
+  m.def("bad_words", &bad_words, py::arg("logits"), py::arg("V"), py::arg("cnt"), py::arg("end"), py::arg("tok"),
+        py::arg("plen"), py::arg("ctx_tok"), py::arg("slots"), py::arg("step") = py::none(),
+        py::arg("segmax") = py::none());
   m.def("record_context", &record_context, py::arg("tok"), py::arg("plen"), py::arg("slots"), py::arg("step"),
         py::arg("tokens"), py::arg("active") = py::none(), py::arg("back") = 0);
   m.def("record_tokens", &record_tokens, py::arg("hist"), py::arg("slots"), py::arg("step"), py::arg("tokens"),

@@ -107,6 +107,8 @@ PYBIND11_MODULE(_runtime, m) {
            py::arg("stop_at_eos"))
       .def("add_many", &SchedCore::add_many, py::arg("sids"), py::arg("prompt_lens"),
            py::arg("wants"), py::arg("stops"))
+      .def("set_stops", &SchedCore::set_stops, py::arg("sid"), py::arg("flat_tokens"), py::arg("lengths"),
+           py::arg("min_tokens"))
       .def("has_work", &SchedCore::has_work)
       .def("plan", [](SchedCore& c, int64_t step) {
              std::vector<int64_t> admitted;

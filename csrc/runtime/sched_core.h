@@ -13,7 +13,7 @@
 //     under the token budget, decode rows, power-of-two row bucket and
 //     256-position context bucket;
 //   * readout assignment: sampled ids -> per-sequence events, EOS stop,
-//     and slot release at a sequence's last item.
+//     per-request stop sequences, and slot release at a sequence's last item.
 // The reference has no scheduler at all. Its coordinator runs one request's
 // token loop per HTTP call (`server.py:154-206`); see SURVEY.md §5.2.
 //
@@ -26,6 +26,7 @@
 #include <cstdint>
 #include <deque>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -80,9 +81,11 @@ using RowOut = std::tuple<int64_t, int, int, int, int>;
 // (g, ret, n, b, ctxb, rows_changed, chunks, rows)
 using GroupOut = std::tuple<int, int, int, int, int, bool, std::vector<ChunkOut>, std::vector<RowOut>>;
 // (sid, token, flags): FIRST = first token of the sequence, FINISH = the
-// request is complete now, RELEASE = its slot went back to the pool (token -1)
+// request is complete now, RELEASE = its slot went back to the pool (token -1),
+// STOP (beside FINISH) = the token completed one of the request's stop sequences
 using Event = std::tuple<int64_t, int, int>;
-constexpr int EV_FIRST = 1, EV_FINISH = 2, EV_RELEASE = 4;
+constexpr int EV_FIRST = 1, EV_FINISH = 2, EV_RELEASE = 4, EV_STOP = 8;
+constexpr int MAX_STOP_LEN = 32;  // tokens of the longest stop sequence, and of the tail kept for matching
 
 class SchedCore {
  public:
@@ -113,6 +116,34 @@ class SchedCore {
     for (size_t i = 0; i < n; ++i)
       if (prompt_lens[i] <= 0) throw std::invalid_argument("empty prompt");
     for (size_t i = 0; i < n; ++i) add(sids[i], prompt_lens[i], wants[i], stops[i]);
+  }
+
+  // Stop sequences of a sequence that was added and has no token yet:
+  // lengths[e] tokens of flat_tokens each, tried in this order.  After its
+  // j-th generated token is read back (the prefill draw is token 1) a stop
+  // sequence matches when it equals the last len generated tokens -- the
+  // prompt never takes part -- and the match counts when j > min_tokens; the
+  // first counting match ends the sequence as a read-back EOS does.
+  void set_stops(int64_t sid, const std::vector<int>& flat_tokens, const std::vector<int>& lengths,
+                 int min_tokens) {
+    auto it = seqs_.find(sid);
+    if (it == seqs_.end()) throw std::invalid_argument("set_stops: unknown sequence");
+    if (it->second.ntok > 0) throw std::invalid_argument("set_stops: the sequence has tokens already");
+    size_t total = 0;
+    for (int n : lengths) {
+      if (n < 1 || n > MAX_STOP_LEN) throw std::invalid_argument("set_stops: a stop sequence holds 1 to 32 tokens");
+      total += (size_t)n;
+    }
+    if (total != flat_tokens.size()) throw std::invalid_argument("set_stops: lengths do not add up to the tokens");
+    if (lengths.empty()) {
+      it->second.stops.reset();
+      return;
+    }
+    auto st = std::make_shared<Stops>();
+    st->toks = flat_tokens;
+    st->lens = lengths;
+    st->min_tokens = min_tokens;
+    it->second.stops = std::move(st);
   }
 
   bool has_work() const {
@@ -212,12 +243,21 @@ class SchedCore {
   int n_expect() const { return (int)expect_.size(); }
 
  private:
+  // stop sequences of a request that gave some, and the last generated tokens
+  // they are matched against (sequences without stops keep neither)
+  struct Stops {
+    std::vector<int> toks, lens;
+    int min_tokens = 0;
+    int tail[MAX_STOP_LEN];  // the last min(ntok, 32) generated tokens, oldest first
+    int ntail = 0;
+  };
   struct Seq {
     int rep = 0, g = -1, slot = -1;
     int prompt_len = 0, prefilled = 0, issued = 0, pos = 0, sstep = 1;
     int want = 0, ntok = 0;
     bool stop_at_eos = false, stop = false, finished = false;
     std::vector<int> toks;  // assign_collect only
+    std::shared_ptr<Stops> stops;  // null without stop sequences
   };
   struct Produced {
     int b = 0;
@@ -400,6 +440,25 @@ class SchedCore {
     return true;
   }
 
+  // The token `tok`, the ntok-th of the sequence (already counted), goes
+  // into the tail; true when it completes a stop sequence and ntok >
+  // min_tokens.
+  static bool stop_match(Stops& st, int tok, int ntok) {
+    if (st.ntail == MAX_STOP_LEN) {
+      std::copy(st.tail + 1, st.tail + MAX_STOP_LEN, st.tail);
+      --st.ntail;
+    }
+    st.tail[st.ntail++] = tok;
+    if (ntok <= st.min_tokens) return false;
+    size_t at = 0;
+    for (int n : st.lens) {
+      if (n <= st.ntail && std::equal(st.toks.begin() + at, st.toks.begin() + at + n, st.tail + st.ntail - n))
+        return true;
+      at += (size_t)n;
+    }
+    return false;
+  }
+
   void give(int64_t sid, int tok, int eos, std::vector<Event>* ev) {
     auto it = seqs_.find(sid);
     if (it == seqs_.end()) return;
@@ -407,7 +466,13 @@ class SchedCore {
     if (s.finished || s.ntok >= s.want) return;
     int flags = s.ntok == 0 ? EV_FIRST : 0;
     s.ntok += 1;
-    if (s.stop_at_eos && tok == eos) s.stop = true;
+    const bool hit = s.stops && stop_match(*s.stops, tok, s.ntok);
+    if (s.stop_at_eos && tok == eos) {
+      s.stop = true;
+    } else if (hit) {
+      s.stop = true;
+      flags |= EV_STOP;
+    }
     if (s.ntok >= s.want || s.stop) {
       s.finished = true;
       flags |= EV_FINISH;
@@ -423,7 +488,13 @@ class SchedCore {
     int flags = s.ntok == 0 ? EV_FIRST : 0;
     s.ntok += 1;
     s.toks.push_back(tok);
-    if (s.stop_at_eos && tok == eos) s.stop = true;
+    const bool hit = s.stops && stop_match(*s.stops, tok, s.ntok);
+    if (s.stop_at_eos && tok == eos) {
+      s.stop = true;
+    } else if (hit) {
+      s.stop = true;
+      flags |= EV_STOP;
+    }
     if (s.ntok >= s.want || s.stop) {
       s.finished = true;
       flags |= EV_FINISH;

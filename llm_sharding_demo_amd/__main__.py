@@ -70,6 +70,14 @@ def main(argv=None) -> int:
                    help="logits of tokens in the prompt or generated so far: / r if positive, * r if negative ((0, 10])")
     g.add_argument("--no-repeat-ngram-size", type=int, default=0, metavar="G",
                    help="never complete a G-gram that is already in the prompt or the output ([0, 32])")
+    g.add_argument("--stop", action="append", metavar="TEXT",
+                   help="end the output where it completes this text, as the tokenizer splits it (repeatable); "
+                        "the text itself is left out")
+    g.add_argument("--stop-token-id", action="append", type=int, metavar="ID",
+                   help="end the output at this token (repeatable)")
+    g.add_argument("--include-stop-in-output", action="store_true", help="keep the matched stop tokens")
+    g.add_argument("--bad-word", action="append", metavar="TEXT",
+                   help="never complete this text, tokenised as given and with a leading space (repeatable)")
     g.add_argument("--logprobs", type=int, default=None, metavar="N",
                    help="also print every generated token's logprob and its N most likely alternatives")
     g.add_argument("--seed", type=int)
@@ -85,12 +93,18 @@ def main(argv=None) -> int:
         if llm.engine.mode == "dist" and llm.engine.rank != 0:
             llm.engine.worker_loop()
             return 0
+        from .utils.tokenizer import encode_bad_words, encode_stops
+
         out = llm.generate_text(args.prompt, args.max_new_tokens, greedy=args.greedy,
                                 temperature=args.temperature, top_k=args.top_k, seed=args.seed,
                                 top_p=args.top_p, min_p=args.min_p, presence_penalty=args.presence_penalty,
                                 frequency_penalty=args.frequency_penalty, logprobs=args.logprobs,
                                 repetition_penalty=args.repetition_penalty,
-                                no_repeat_ngram_size=args.no_repeat_ngram_size)
+                                no_repeat_ngram_size=args.no_repeat_ngram_size,
+                                stop_sequences=encode_stops(llm.tokenizer, args.stop) if args.stop else None,
+                                stop_token_ids=args.stop_token_id,
+                                include_stop_in_output=args.include_stop_in_output,
+                                bad_words=encode_bad_words(llm.tokenizer, args.bad_word) if args.bad_word else None)
         print(out)
         llm.engine.shutdown()
         return 0

@@ -176,6 +176,11 @@ def model_config_from_hf_json(path: str) -> ModelConfig:
 
 MAX_LOGPROBS_CEILING = 20  # alternatives per token the logprob kernel's record can hold
 MAX_LOGIT_EDITS_CEILING = 1024  # entries per request the logit-edit kernel's 256 threads visit in 4 trips
+MAX_BAD_WORDS_CEILING = 256  # sequences per request: one thread of the bad_words kernel's workgroup each
+MAX_BAD_WORD_TOKENS_CEILING = 4096  # tokens of a request's bad_words in all
+MAX_STOP_SEQUENCES_CEILING = 64  # stop sequences per request (stop_token_ids and stop_sequences together)
+MAX_STOP_LEN = 32  # tokens of one stop sequence: the scheduler core keeps a request's last 32 tokens to match
+MAX_BAD_WORD_LEN = 32  # tokens of one sequence: its prefix fits the kernel's 31-token context tail
 INT32_MAX = 2 ** 31 - 1
 
 
@@ -293,7 +298,48 @@ class SamplingParams:
     the engine wants prompt + max_new_tokens below the number of allowed
     tokens that are not banned.  The list travels as a bitmask over the
     vocabulary, so its length costs nothing.  Asking never changes another
-    request's draws."""
+    request's draws.
+
+    bad_words: None (off; nothing runs, travels or is allocated for the
+    request) or a list of non-empty token-id sequences that may never be
+    completed (HF bad_words_ids, vLLM bad_words).  Before every draw, the
+    prefill draw (draw 0) included, the request's context is its prompt
+    followed by the tokens it has generated so far -- the context
+    no_repeat_ngram_size reads -- and every sequence whose tokens but the last
+    the context ends with has its last token's fp32 logit set to -inf; a
+    sequence of one token is a plain ban.  The pass runs right after the
+    repetition pass, ahead of the presence / frequency penalties, the logit
+    edits, the allowed-token mask, temperature, top-k, top-p, min-p and the
+    greedy argmax -- greedy requests are banned too -- and logprobs are taken
+    after it.  Bans are pure stores of -inf, so they commute with every other
+    edit.  Exact duplicates collapse.  A request carries at most
+    EngineConfig.max_bad_words sequences of 1 to 32 tokens each and
+    EngineConfig.max_bad_word_tokens tokens in all; the ids must lie in the
+    vocabulary, and some token must stay drawable: the vocabulary (or the
+    allowed set) minus the request's own bans minus the distinct last tokens
+    must be positive, with an n-gram ban also minus prompt + max_new_tokens.
+    Such a request's prompt reaches the last stage, as with
+    no_repeat_ngram_size.  Asking never changes another request's draws.
+
+    stop_token_ids / stop_sequences / include_stop_in_output end a request
+    when its output completes a token sequence; the sampler is not involved
+    and the draws do not change.  stop_token_ids are token ids (duplicates
+    collapse), each a stop sequence of one token; stop_sequences are non-empty
+    token-id sequences.  After the request's j-th generated token is read back
+    (the prefill draw is token 1) the sequences are tried in order --
+    stop_token_ids ascending, then stop_sequences as given -- and one matches
+    when it equals the last len generated tokens: the prompt never takes part.
+    A match counts only when j > min_new_tokens, the draw from which EOS itself
+    may appear; the first counting match ends the request as a read-back EOS
+    does (stop_at_eos is checked first): it leaves at the next step and its
+    KV slot is released.  Request.output drops the matched tokens unless
+    include_stop_in_output is set, Request.logprobs is trimmed to the same
+    length, Request.finish_reason is "stop" and Request.stop_reason the index
+    of the matched sequence in the order above (else "length" or "eos", and
+    None).  A request carries at most EngineConfig.max_stop_sequences
+    sequences of 1 to 32 tokens; the ids must lie in the vocabulary.  The
+    defaults (None / None / False) are off: such a request takes the path it
+    always took."""
 
     temperature: float = 0.6
     top_k: int = 40
@@ -312,6 +358,69 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
     allowed_token_ids: Optional[Sequence[int]] = None
+    bad_words: Optional[Sequence[Sequence[int]]] = None
+    stop_token_ids: Optional[Sequence[int]] = None
+    stop_sequences: Optional[Sequence[Sequence[int]]] = None
+    include_stop_in_output: bool = False
+
+    @property
+    def has_stops(self) -> bool:
+        return bool(self.stop_token_ids) or bool(self.stop_sequences)
+
+    def stop_list(self) -> list:
+        """The request's stop sequences as tuples of ints in the order they
+        are tried: stop_token_ids ascending (duplicates collapsed), then
+        stop_sequences as given (empty without any)."""
+        out = []
+        for name in ("stop_token_ids", "stop_sequences"):
+            v = getattr(self, name)
+            if v is not None and (isinstance(v, (str, bytes, Mapping)) or not hasattr(v, "__iter__")):
+                raise ValueError(f"{name} must be a sequence")
+        if self.stop_token_ids is not None:
+            out += [(t,) for t in sorted({_strict_id(t) for t in self.stop_token_ids})]
+        for w in self.stop_sequences or ():
+            if isinstance(w, (str, bytes, Mapping)) or not hasattr(w, "__iter__"):
+                raise ValueError("stop_sequences must be a sequence of token-id sequences")
+            out.append(tuple(_strict_id(t) for t in w))
+        return out
+
+    def stop_match(self, generated: Sequence[int], stops: Optional[list] = None) -> Optional[int]:
+        """The index in stop_list() of the first stop sequence that the
+        generated tokens end with, when the match counts (more tokens than
+        min_new_tokens); None otherwise."""
+        n = len(generated)
+        if n <= self.min_new_tokens:
+            return None
+        for i, w in enumerate(self.stop_list() if stops is None else stops):
+            if len(w) <= n and tuple(generated[n - len(w):]) == tuple(w):
+                return i
+        return None
+
+    def bad_word_list(self) -> list:
+        """The distinct bad_words sequences as tuples of ints, in the order
+        given (empty without any)."""
+        if self.bad_words is None:
+            return []
+        bw = self.bad_words
+        if isinstance(bw, (str, bytes, Mapping)) or not hasattr(bw, "__iter__"):
+            raise ValueError("bad_words must be a sequence of token-id sequences")
+        out = {}
+        for w in bw:
+            if isinstance(w, (str, bytes, Mapping)) or not hasattr(w, "__iter__"):
+                raise ValueError("bad_words must be a sequence of token-id sequences")
+            out[tuple(_strict_id(t) for t in w)] = None
+        return list(out)
+
+    def bad_word_entries(self) -> Optional[tuple]:
+        """The request's bad_words as the last stage's table row holds them:
+        (exclusive end offsets, the sequences' tokens back to back), or None
+        without any."""
+        ws = self.bad_word_list()
+        if not ws:
+            return None
+        import itertools
+
+        return tuple(itertools.accumulate(map(len, ws))), tuple(t for w in ws for t in w)
 
     def allowed_set(self) -> Optional[frozenset]:
         """The distinct allowed token ids, or None without a list."""
@@ -370,7 +479,8 @@ class SamplingParams:
         rows.sort(key=lambda r: (r[0], -r[2]))
         return tuple(zip(*rows)) if rows else None
 
-    def validate(self, max_logprobs: int = MAX_LOGPROBS_CEILING, max_logit_edits: int = 300) -> None:
+    def validate(self, max_logprobs: int = MAX_LOGPROBS_CEILING, max_logit_edits: int = 300,
+                 max_bad_words: int = 64, max_bad_word_tokens: int = 512, max_stop_sequences: int = 16) -> None:
         if self.max_new_tokens < 0:
             raise ValueError("max_new_tokens must be >= 0")
         m = self.min_new_tokens
@@ -392,6 +502,28 @@ class SamplingParams:
                 raise ValueError("allowed_token_ids must not be empty (None turns the mask off)")
             if any(t < 0 or t > INT32_MAX for t in ids):
                 raise ValueError("allowed_token_ids must be >= 0")
+        if not isinstance(self.include_stop_in_output, bool):
+            raise ValueError("include_stop_in_output must be a bool")
+        if self.stop_token_ids is not None or self.stop_sequences is not None:
+            st = self.stop_list()
+            if any(not 1 <= len(w) <= MAX_STOP_LEN for w in st):
+                raise ValueError(f"stop_sequences: every sequence must hold 1 to {MAX_STOP_LEN} tokens")
+            if any(t < 0 or t > INT32_MAX for w in st for t in w):
+                raise ValueError("stop_token_ids / stop_sequences: token ids must be >= 0")
+            if len(st) > max_stop_sequences:
+                raise ValueError(f"stop_token_ids and stop_sequences make {len(st)} sequences; at most "
+                                 f"{max_stop_sequences} (max_stop_sequences)")
+        if self.bad_words is not None:
+            ws = self.bad_word_list()
+            if any(not 1 <= len(w) <= MAX_BAD_WORD_LEN for w in ws):
+                raise ValueError(f"bad_words: every sequence must hold 1 to {MAX_BAD_WORD_LEN} tokens")
+            if any(t < 0 or t > INT32_MAX for w in ws for t in w):
+                raise ValueError("bad_words: token ids must be >= 0")
+            if len(ws) > max_bad_words:
+                raise ValueError(f"bad_words: {len(ws)} sequences; at most {max_bad_words} (max_bad_words)")
+            if sum(map(len, ws)) > max_bad_word_tokens:
+                raise ValueError(f"bad_words: {sum(map(len, ws))} tokens in all; at most {max_bad_word_tokens} "
+                                 "(max_bad_word_tokens)")
         if self.logit_bias is not None or self.banned_token_ids is not None:
             if self.logit_bias is not None and not isinstance(self.logit_bias, Mapping):
                 raise ValueError("logit_bias must map token ids to values")
@@ -525,8 +657,24 @@ class EngineConfig:
     # slots x (4 + 12 E) bytes, allocated when the first such request arrives.
     # At most 1024.
     max_logit_edits: int = 300
+    # Most bad_words sequences a request may carry and most tokens they hold in
+    # all (SamplingParams.bad_words); size the last stage's bad-words table,
+    # slots x (4 + 4 N + 4 T) bytes, allocated when the first such request
+    # arrives.  At most 256 and 4096.
+    max_bad_words: int = 64
+    max_bad_word_tokens: int = 512
+    # Most stop sequences a request may carry (SamplingParams.stop_token_ids and
+    # stop_sequences together); the scheduler core tries them at every token of
+    # such a request.  At most 64.
+    max_stop_sequences: int = 16
 
     def __post_init__(self):
+        if not (1 <= self.max_stop_sequences <= MAX_STOP_SEQUENCES_CEILING):
+            raise ValueError(f"max_stop_sequences must be in [1, {MAX_STOP_SEQUENCES_CEILING}]")
+        if not (1 <= self.max_bad_words <= MAX_BAD_WORDS_CEILING):
+            raise ValueError(f"max_bad_words must be in [1, {MAX_BAD_WORDS_CEILING}]")
+        if not (1 <= self.max_bad_word_tokens <= MAX_BAD_WORD_TOKENS_CEILING):
+            raise ValueError(f"max_bad_word_tokens must be in [1, {MAX_BAD_WORD_TOKENS_CEILING}]")
         if not (0 <= self.max_logprobs <= MAX_LOGPROBS_CEILING):
             raise ValueError(f"max_logprobs must be in [0, {MAX_LOGPROBS_CEILING}]")
         if not (1 <= self.max_logit_edits <= MAX_LOGIT_EDITS_CEILING):
@@ -566,6 +714,9 @@ class EngineConfig:
             metrics_every=int(_env("METRICS_EVERY", "16")),
             max_logprobs=int(_env("MAX_LOGPROBS", "5")),
             max_logit_edits=int(_env("MAX_LOGIT_EDITS", "300")),
+            max_bad_words=int(_env("MAX_BAD_WORDS", "64")),
+            max_bad_word_tokens=int(_env("MAX_BAD_WORD_TOKENS", "512")),
+            max_stop_sequences=int(_env("MAX_STOP_SEQUENCES", "16")),
         )
         if cfg.split_points and cfg.num_stages == 1:
             cfg.num_stages = len(cfg.split_points) + 1

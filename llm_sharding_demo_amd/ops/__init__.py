@@ -139,6 +139,14 @@ class ReferenceBackend(Backend):
     def record_context(self, table, slots, step, tokens, active=None, back: int = 0) -> None:
         ref.record_context(table, slots, step, tokens, active, back)
 
+    def bad_words(self, logits, table, ctx_table, slots, step, vocab: int) -> None:
+        """The rows' bad_words (table = the last stage's per-slot cnt, end,
+        tok; ctx_table = its context table): -inf at the last token of every
+        sequence whose other tokens the row's prompt + generated tokens end
+        with, in place on the fp32 logits, right after the repetition pass;
+        step None = draw 0."""
+        ref.bad_words(logits, table, ctx_table, slots, step, vocab)
+
     def allow_mask(self, logits, table, slots, vocab: int) -> None:
         """The rows' allowed_token_ids (table = the last stage's per-slot on,
         bits): -inf at every token of [0, vocab) whose bit is clear, in place

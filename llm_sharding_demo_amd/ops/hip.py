@@ -395,6 +395,20 @@ class HipBackend(Backend):
     def record_context(self, table, slots, step, tokens, active=None, back: int = 0) -> None:
         self.C.record_context(table[3], table[0], slots, step, tokens, active, back)
 
+    def bad_words(self, logits, table, ctx_table, slots, step, vocab: int) -> None:
+        # bad_words.hip: one workgroup per row, right after the repetition pass;
+        # rows whose slot holds no sequence return at once; the segment maxima
+        # are repaired too.  A thread takes a sequence, so a table wider than
+        # the workgroup is refused, as is a context longer than the context
+        # table's own limit
+        N, L = table[1].shape[1], ctx_table[3].shape[1]
+        if N > 256:
+            raise ValueError(f"bad_words: {N} sequences per slot exceed the kernel's 256")
+        if L > 8192:
+            raise ValueError(f"bad_words: a context of {L} tokens exceeds the context table's 8192")
+        self.C.bad_words(logits, vocab, table[0], table[1], table[2], ctx_table[0], ctx_table[3], slots, step,
+                         getattr(logits, "_lsd_segmax", None))
+
     def allow_mask(self, logits, table, slots, vocab: int) -> None:
         # allow_mask.hip: one workgroup per row, ahead of the draw; rows whose
         # slot gave no allowed list return at once; the segment maxima are repaired too

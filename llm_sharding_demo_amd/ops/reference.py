@@ -303,6 +303,61 @@ def repetition(logits: torch.Tensor, table, slots: torch.Tensor, step: Optional[
     return logits if segmax is None else (logits, segmax)
 
 
+def bad_words(logits: torch.Tensor, table, ctx_table, slots: torch.Tensor, step: Optional[torch.Tensor], vocab: int,
+              segmax: Optional[torch.Tensor] = None):
+    """Per-request bad_words (HF bad_words_ids): token sequences that may never
+    be completed, right after `repetition` and ahead of `penalize`,
+    `logit_edits`, `allow_mask` and `sample`.
+
+    table = (cnt [slots] int, end [slots, N] int, tok [slots, T] int): the
+    sequence e < min(cnt[s], N) of KV slot s is w = tok[s, end[s, e - 1] ..
+    end[s, e]) (end[s, -1] = 0), m = len(w) tokens.  ctx_table is `repetition`'s
+    table, of which plen and tok are read: the context of row r on slot s =
+    slots[r] is x = tok[s, 0 .. n), n = min(plen[s] + c, L), c = step[r], the
+    row's sampler counter before the draw (step None: c = 0, the prefill
+    draw).  Every sequence with m - 1 <= n and x[n - m + 1 .. n) == w[: m - 1]
+    (raw ids; m = 1: always) does
+        logit[w[m - 1]] <- -inf
+    when that token is in [0, vocab): a pure store, every other logit keeps its
+    bits.  A sequence whose offsets do not describe 1 to 32 tokens inside the
+    row is skipped.  Rows whose slot is outside the table or has cnt == 0 are
+    untouched.
+
+    fp32 `logits` [B, >= vocab] are rewritten in place and returned.  With
+    `segmax` [B, width / 8] (linear_f32's 8-logit segment maxima, padding
+    columns included) the maximum of every segment holding a banned token is
+    recomputed from its 8 stored logits in place too, and (logits, segmax) is
+    returned.
+    """
+    assert logits.dtype == torch.float32, "bad_words rewrites fp32 logits in place"
+    cnt, end, tok = table
+    plen, ctok = ctx_table[0], ctx_table[3]
+    N, T, L = end.shape[1], tok.shape[1], ctok.shape[1]
+    for r in range(logits.shape[0]):
+        s = int(slots[r])
+        if not 0 <= s < cnt.shape[0] or int(cnt[s]) <= 0:
+            continue
+        c = int(step[r]) if step is not None else 0
+        n = max(0, min(int(plen[s]) + c, L))
+        x = ctok[s, max(0, n - 31): n].tolist()
+        ends, banned = [0] + end[s, : min(int(cnt[s]), N)].tolist(), []
+        for b, e in zip(ends, ends[1:]):
+            m = e - b
+            if b < 0 or e > T or not 1 <= m <= 32 or m - 1 > n:
+                continue
+            w = tok[s, b:e].tolist()
+            if x[len(x) - (m - 1):] == w[:-1] and 0 <= w[-1] < vocab:
+                banned.append(w[-1])
+        if banned:
+            ban = torch.unique(torch.tensor(banned))
+            logits[r, ban] = float("-inf")
+            if segmax is not None:
+                segs = torch.unique(ban // 8)
+                idx = segs[:, None] * 8 + torch.arange(8)
+                segmax[r, segs] = logits[r][idx].max(dim=1).values
+    return logits if segmax is None else (logits, segmax)
+
+
 def record_context(table, slots: torch.Tensor, step: Optional[torch.Tensor], tokens: torch.Tensor,
                    active: Optional[torch.Tensor] = None, back: int = 0) -> None:
     """tok[slots[i], plen[slots[i]] + step[i] - back] = tokens[i] for active

@@ -2,11 +2,12 @@
 
 A `StageWorker` (parallel/pipeline.py) moves a step through its stage; its
 `DrawStage` decides what runs on the logits of the last stage: the repetition
-pass, the penalty pass, the logit edits, the allowed-token mask, the sampler,
-the token history, the context and the logprob records, for the decode rows of a group (`rows`,
+pass, the bad-words pass, the penalty pass, the logit edits, the allowed-token
+mask, the sampler, the token history, the context and the logprob records,
+for the decode rows of a group (`rows`,
 captured into the decode graphs) and for the first draw of a finished prompt
 (`finals`, eager); `chunks` copies the prompts that the repetition pass reads
-into its table as they are prefilled.  It owns the five per-KV-slot tables
+into its table as they are prefilled.  It owns the six per-KV-slot tables
 these passes read and write, and counts the items that ran each pass.  Every
 stage has one; off the last stage it stays empty.
 """
@@ -18,7 +19,7 @@ import numpy as np
 import torch
 
 from ..runtime.batch import SamplingState
-from ..runtime.plan import has_allow, has_context, has_edits, row_features
+from ..runtime.plan import has_allow, has_bad, has_context, has_edits, row_features
 from ..utils import racecheck
 
 
@@ -47,6 +48,9 @@ class DrawStage(racecheck.Shared):
         self.repetition_launches = 0
         self.allow_tab: Optional[tuple] = None  # allowed_token_ids: a flag and a bitmask over the logits' columns
         self.allow_launches = 0
+        self.bad_tab: Optional[tuple] = None  # bad_words: the sequences back to back, N = max_bad_words, T = max_bad_word_tokens
+        self.max_bad_words, self.max_bad_word_tokens = 64, 512
+        self.bad_words_launches = 0
 
     # ------------------------------------------------------------------
     # tables
@@ -142,17 +146,41 @@ class DrawStage(racecheck.Shared):
                 torch.cuda.current_stream(dev).synchronize()
         return self.allow_tab
 
+    def _bad_tab(self) -> tuple:
+        """Bad-words table: (cnt [KV slots, scratch and compat included]
+        int32, end [.., N] int32, tok [.., T] int32), N = max_bad_words, T =
+        max_bad_word_tokens: sequence e < cnt of a slot is tok[end[e - 1] ..
+        end[e]) of its row (end[-1] = 0), and the bad-words pass touches only
+        rows whose slot has cnt != 0.  Like the edit table's counts its stale
+        counts ARE read -- by the other rows of a group with an asking row,
+        and by every pad row on the scratch slot -- so they start at zero,
+        visibly to every lane: this thread waits for the fill (_edit_tab).
+        Allocated once, outside any capture, and never reallocated: captured
+        graphs hold its addresses.  From then on every final chunk writes its
+        slot's count (finals)."""
+        if self.bad_tab is None:
+            S, N, T, dev = self.slots, self.max_bad_words, self.max_bad_word_tokens, self.stage.device
+            self.bad_tab = (torch.zeros(S, dtype=torch.int32, device=dev),
+                            torch.zeros(S, N, dtype=torch.int32, device=dev),
+                            torch.zeros(S, T, dtype=torch.int32, device=dev))
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()
+        return self.bad_tab
+
     def prepare(self, feats: tuple) -> None:
-        """A composition with the features (cut, pen, lp, edit[, ctx[, allow]])
-        is being applied: what they need -- the token history, the logprob
-        records, the edit table, the context table, the allowed-token table --
-        allocated here, on the host side of the change (never inside a
-        capture)."""
+        """A composition with the features (cut, pen, lp, edit[, ctx[, allow[,
+        bad]]]) is being applied: what they need -- the token history, the
+        logprob records, the edit table, the context table, the allowed-token
+        table, the bad-words table -- allocated here, on the host side of the
+        change (never inside a capture)."""
         _, pen, lp, edit, *more = feats
         if more and more[0]:
             self._ctx_tab()
         if more[1:] and more[1]:
             self._allow_tab()
+        if more[2:] and more[2]:
+            self._ctx_tab()
+            self._bad_tab()
         if pen:
             self._hist()
         if lp:
@@ -184,6 +212,8 @@ class DrawStage(racecheck.Shared):
             self.repetition_launches += 1
         if gs.allow:
             self.allow_launches += 1
+        if gs.bad:
+            self.bad_words_launches += 1
 
     def chunks(self, gs, chunks) -> None:
         """Prefill chunks are about to run on the last stage (every prefill
@@ -239,11 +269,15 @@ class DrawStage(racecheck.Shared):
         the repetition pass first of all, and record_context behind the draw.
         One with a row that gave allowed_token_ids runs the mask pass last of
         the edits: the sampler and the logprob kernel see the masked logits.
-        Any other runs the sampler alone."""
+        One with a row that gave bad_words -- a context row too -- runs the
+        bad-words pass right after the repetition pass, which reads the same
+        context.  Any other runs the sampler alone."""
         be, V = self.stage.backend, self.stage.cfg.vocab_size
         slots, step, out = gs.slots[:b], gs.sstep[:b], gs.tokret[:b]
         if gs.ctx:
             be.repetition(logits, self.ctx_tab, slots, step, V)
+        if gs.bad:
+            be.bad_words(logits, self.bad_tab, self.ctx_tab, slots, step, V)
         if gs.pen:
             be.penalize(logits, self.pen_hist, slots, step, gs.presence[:b], gs.frequency[:b], V)
         if gs.edit:
@@ -275,18 +309,25 @@ class DrawStage(racecheck.Shared):
         The allowed-token table goes like the edit table: nothing without a
         table and without an asking chunk; once it exists every final chunk
         writes its slot's flag, zero included, an asking one its mask words too,
-        and the mask pass runs last ahead of the draw."""
+        and the mask pass runs last ahead of the draw.  So does the bad-words
+        table: every final chunk writes its slot's count, zero included, an
+        asking one its end offsets and tokens too, and the bad-words pass
+        runs right after the repetition pass, over the prompt."""
         be, V, dev = self.stage.backend, self.stage.cfg.vocab_size, self.stage.device
         _, pen, lp = row_features(fc)
-        ed, cx, al = has_edits(fc), has_context(fc), has_allow(fc)
+        ed, cx, al, bw = has_edits(fc), has_context(fc), has_allow(fc), has_bad(fc)
         tab = self._edit_tab() if ed or self.edit_tab is not None else None
         atab = self._allow_tab() if al or self.allow_tab is not None else None
+        btab = self._bad_tab() if bw or self.bad_tab is not None else None
         slots = nlp = None
-        if tab is not None or atab is not None or pen or lp or cx:
-            slots, nlp = self._stage_finals(gs, fc, tab, atab)
+        if tab is not None or atab is not None or btab is not None or pen or lp or cx:
+            slots, nlp = self._stage_finals(gs, fc, tab, atab, btab)
         if cx:
             be.repetition(logits, self._ctx_tab(), slots, None, V)
             self.repetition_launches += 1
+        if bw:
+            be.bad_words(logits, btab, self._ctx_tab(), slots, None, V)
+            self.bad_words_launches += 1
         if ed:
             be.logit_edits(logits, tab, slots, None, V)
             self.logit_edit_launches += 1
@@ -304,7 +345,8 @@ class DrawStage(racecheck.Shared):
             self.logprob_launches += 1
         return ids
 
-    def _stage_finals(self, gs, fc, tab: Optional[tuple], atab: Optional[tuple] = None) -> tuple:
+    def _stage_finals(self, gs, fc, tab: Optional[tuple], atab: Optional[tuple] = None,
+                      btab: Optional[tuple] = None) -> tuple:
         """What the passes around the first draw of `fc` read, on the device
         in ONE host-to-device copy through the group's pinned staging ring:
         [slots J | logprob widths J | edit counts J], then with n edits among
@@ -312,7 +354,10 @@ class DrawStage(racecheck.Shared):
         a table, its rows are written from the copy.  With an allowed-token
         table `atab` then [allow flags J], and with k asking chunks among them
         [their slots k | their mask words k W]; its flags and rows are written
-        from the copy too.  -> (slots, widths)."""
+        from the copy too.  With a bad-words table `btab` then [sequence
+        counts J], and with m sequences of t tokens among them [flat end index
+        m | end offsets m | flat token index t | tokens t], written likewise.
+        -> (slots, widths)."""
         cols = [[c.slot for c in fc], [c.logprobs for c in fc], [c.nedits for c in fc]]
         if tab is not None:
             cnt, tok, val, until = tab
@@ -335,6 +380,21 @@ class DrawStage(racecheck.Shared):
             cols += [[1 if c.allow else 0 for c in fc]]
             if ask:
                 cols += [[c.slot for c in ask], np.frombuffer(b"".join(c.mask for c in ask), dtype=np.int32)]
+        words = []
+        if btab is not None:
+            bcnt, bend, btok = btab
+            N, T = bend.shape[1], btok.shape[1]
+            words = [c for c in fc if c.nbad]
+            if any(c.bad is None or len(c.bad[0]) != c.nbad or c.nbad > N or len(c.bad[1]) > T
+                   or len(c.bad[1]) != c.bad[0][-1] or not 0 <= c.slot < self.slots for c in words):
+                raise ValueError("a final chunk's bad_words are missing or exceed max_bad_words = "
+                                 f"{N} / max_bad_word_tokens = {T}")
+            cols += [[c.nbad for c in fc]]
+            if words:
+                cols += [np.concatenate([c.slot * N + np.arange(c.nbad) for c in words]),
+                         [e for c in words for e in c.bad[0]],
+                         np.concatenate([c.slot * T + np.arange(len(c.bad[1])) for c in words]),
+                         [t for c in words for t in c.bad[1]]]
         arr = np.concatenate([np.asarray(c, dtype=np.int32) for c in cols])
         dev = self.stage.device
         if dev.type == "cuda":
@@ -350,6 +410,12 @@ class DrawStage(racecheck.Shared):
             on.index_copy_(0, slots.long(), more[0])
             if ask:
                 bits.index_copy_(0, more[1].long(), more[2].view(len(ask), W))
+            more = more[3 if ask else 1:]
+        if btab is not None:
+            bcnt.index_copy_(0, slots.long(), more[0])
+            if words:
+                bend.view(-1).index_copy_(0, more[1].long(), more[2])
+                btok.view(-1).index_copy_(0, more[3].long(), more[4])
         if edits:
             at, t, v, u = edits
             at = at.long()

@@ -43,8 +43,8 @@ import torch
 
 from ..models.stage import StageModel
 from ..runtime.batch import BatchMeta, MixedMeta
-from ..runtime.plan import (NO_FEATURES, ROW_FIELDS, GroupPlan, StepPlan, device_fields, has_allow, has_context,
-                            has_edits, pack_rows, packed_size, row_features)
+from ..runtime.plan import (NO_FEATURES, ROW_FIELDS, GroupPlan, StepPlan, device_fields, has_allow, has_bad,
+                            has_context, has_edits, pack_rows, packed_size, row_features)
 from ..utils.tracing import trace_range
 from ..utils import racecheck
 from .comm import Handle, SendHandle, Transport
@@ -216,6 +216,11 @@ class GroupState(racecheck.Shared):
         # right ahead of the sampler.  A flag like `edit` -- a per-slot table,
         # no row vector -- and the sixth feature in the decode graphs' key
         self.allow = False
+        # a row with bad_words (plan.has_bad; such a row has a context too):
+        # the bad-words pass runs right after the repetition pass.  A flag
+        # like `edit` -- a per-slot table, no row vector -- and the seventh
+        # feature in the decode graphs' key
+        self.bad = False
         if w.last:
             for f in ROW_FIELDS:  # the sampler's row vectors, idle: temp, topk, greedy, seeds, sstep, ...
                 setattr(self, f.vec, torch.full((cap,), f.idle, dtype=getattr(torch, f.dtype), device=dev))
@@ -950,13 +955,14 @@ class StageWorker(racecheck.Shared):
         self.mixed_items += 1
 
     def _features(self, gp: GroupPlan, gs: GroupState) -> tuple:
-        """(cut, pen, lp, edit, ctx, allow) of the group once this item ran: the
-        current ones, or those of the item's new composition -- one pass over its
-        rows, kept with the plan item, so whichever path runs it reads the same six."""
+        """(cut, pen, lp, edit, ctx, allow, bad) of the group once this item ran:
+        the current ones, or those of the item's new composition -- one pass over
+        its rows, kept with the plan item, so whichever path runs it reads the
+        same seven."""
         if gp.rows is None:
-            return gs.cut, gs.pen, gs.lp, gs.edit, gs.ctx, gs.allow
+            return gs.cut, gs.pen, gs.lp, gs.edit, gs.ctx, gs.allow, gs.bad
         if not self.last:
-            return NO_FEATURES + (False, False, False)
+            return NO_FEATURES + (False, False, False, False)
         if gp.feats is None:
             gp.feats = row_features(gp.rows)
         if gp.edit is None:
@@ -965,15 +971,18 @@ class StageWorker(racecheck.Shared):
             gp.ctx = has_context(gp.rows)
         if gp.allow is None:
             gp.allow = has_allow(gp.rows)
-        return gp.feats + (gp.edit, gp.ctx, gp.allow)
+        if gp.bad is None:
+            gp.bad = has_bad(gp.rows)
+        return gp.feats + (gp.edit, gp.ctx, gp.allow, gp.bad)
 
     def _set_features(self, gs: GroupState, feats: tuple) -> None:
         """A composition change is being applied: the group's features from
         now on, and the tables they need, on the host side of the change (never
         inside a capture)."""
-        gs.cut, gs.pen, gs.lp, gs.edit, *more = feats  # a 4-tuple: no context; a 5-tuple: no mask
+        gs.cut, gs.pen, gs.lp, gs.edit, *more = feats  # a 4-tuple: no context; a 5-tuple: no mask; 6: no bad_words
         gs.ctx = bool(more and more[0])
         gs.allow = bool(more[1:] and more[1])
+        gs.bad = bool(more[2:] and more[2])
         self.draw.prepare(feats)
 
     def _apply_rows(self, gp: GroupPlan, gs: GroupState) -> None:
@@ -1194,7 +1203,7 @@ class StageWorker(racecheck.Shared):
         slot[2] = True
 
     def _decode(self, gp: GroupPlan, gs: GroupState, inp: torch.Tensor, io: bool = False) -> torch.Tensor:
-        key = (gp.b, gp.ctxb, io, gs.cut, gs.pen, gs.lp, gs.edit, gs.ctx, gs.allow)
+        key = (gp.b, gp.ctxb, io, gs.cut, gs.pen, gs.lp, gs.edit, gs.ctx, gs.allow, gs.bad)
         lane = self.lane_of(gp.g)
         self.draw.count(gs)
 

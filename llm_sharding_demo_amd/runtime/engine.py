@@ -351,6 +351,7 @@ class Engine(racecheck.Shared):
         w.merge_prefill = w.MERGE_PREFILL and self.cfg.merge_prefill
         w.draw.max_logprobs = self.cfg.max_logprobs
         w.draw.max_logit_edits = self.cfg.max_logit_edits
+        w.draw.max_bad_words, w.draw.max_bad_word_tokens = self.cfg.max_bad_words, self.cfg.max_bad_word_tokens
         return w
 
     @property
@@ -370,10 +371,18 @@ class Engine(racecheck.Shared):
     # requests
     # ------------------------------------------------------------------
     def _validate(self, prompt: List[int], sp: SamplingParams) -> None:
-        sp.validate(self.cfg.max_logprobs, self.cfg.max_logit_edits)
+        sp.validate(self.cfg.max_logprobs, self.cfg.max_logit_edits, self.cfg.max_bad_words,
+                    self.cfg.max_bad_word_tokens, self.cfg.max_stop_sequences)
+        if sp.has_stops:
+            for w in sp.stop_list():
+                for t in w:
+                    if not 0 <= t < self.mcfg.vocab_size:
+                        raise ValueError(f"stop_token_ids / stop_sequences: token id {t} outside the vocabulary "
+                                         f"[0, {self.mcfg.vocab_size})")
         if sp.has_logit_edits:
             self._validate_edits(sp)
         left = self._validate_allowed(sp) if sp.allowed_token_ids is not None else None
+        lasts = self._validate_bad_words(sp, left) if sp.bad_words is not None else 0
         if sp.logprobs is not None and self.mode == "dist":
             # the records stay on the last stage until the request finishes and
             # are read from there directly; fetching them over the control
@@ -391,11 +400,11 @@ class Engine(racecheck.Shared):
             banned = sum(v == float("-inf") for v in ed[1]) if ed else 0
             if left is not None:
                 # with an allowed list only its tokens that are not banned can be drawn
-                if len(prompt) + sp.max_new_tokens >= left:
+                if len(prompt) + sp.max_new_tokens + lasts >= left:
                     raise ValueError(f"no_repeat_ngram_size: prompt ({len(prompt)}) + max_new_tokens "
                                      f"({sp.max_new_tokens}) must stay below the {left} allowed tokens that "
                                      "are not banned")
-            elif len(prompt) + sp.max_new_tokens + banned >= self.mcfg.vocab_size:
+            elif len(prompt) + sp.max_new_tokens + banned + lasts >= self.mcfg.vocab_size:
                 raise ValueError(f"no_repeat_ngram_size: prompt ({len(prompt)}) + max_new_tokens "
                                  f"({sp.max_new_tokens}) + banned tokens ({banned}) must stay below the "
                                  f"vocabulary size {self.mcfg.vocab_size}")
@@ -429,6 +438,27 @@ class Engine(racecheck.Shared):
         if left == 0:
             raise ValueError("allowed_token_ids: banned_token_ids and min_new_tokens leave no allowed token to draw")
         return left
+
+    def _validate_bad_words(self, sp: SamplingParams, left: Optional[int]) -> int:
+        """What SamplingParams.validate cannot know of bad_words: the ids lie
+        in the vocabulary, and the vocabulary -- or the allowed tokens -- less
+        the request's own bans (`left` with an allowed list) and less the
+        sequences' distinct last tokens, all of which can be banned at one
+        draw, leaves a token to draw.  -> the distinct last tokens."""
+        V = self.mcfg.vocab_size
+        ws = sp.bad_word_list()
+        for w in ws:
+            for t in w:
+                if not 0 <= t < V:
+                    raise ValueError(f"bad_words: token id {t} outside the vocabulary [0, {V})")
+        lasts = len({w[-1] for w in ws})
+        if left is None:
+            ed = sp.logit_edits(self.mcfg.eos_token_id)
+            left = V - len({t for t, v in zip(ed[0], ed[1]) if v == float("-inf")} if ed else ())
+        if left - lasts <= 0:
+            raise ValueError(f"bad_words: {lasts} distinct last tokens beside the request's other bans leave no "
+                             "token to draw")
+        return lasts
 
     @property
     def mask_words(self) -> int:

@@ -66,6 +66,14 @@ class Chunk:
     # slot's table
     allow: int = 0
     mask: Optional[bytes] = None
+    # bad_words: the request's sequences on every chunk of an asking request
+    # (has_bad), which is a context request too -- the pass reads the slot's
+    # context, so plen is set and the ids travel as with no_repeat_ngram_size;
+    # the entries, SamplingParams.bad_word_entries' (exclusive end offsets,
+    # tokens back to back), on the final chunk only, whose stage writes them to
+    # the slot's table
+    nbad: int = 0
+    bad: Optional[tuple] = None
 
     @property
     def qlen(self) -> int:
@@ -73,7 +81,7 @@ class Chunk:
 
     @property
     def ctx(self) -> bool:
-        return self.rpen != 1.0 or self.ngram != 0
+        return self.rpen != 1.0 or self.ngram != 0 or self.nbad > 0
 
 
 @dataclass
@@ -99,6 +107,7 @@ class Row:
     nedits: int = 0     # logit-edit entries in the slot's table: the group's edit gate (has_edits)
     ctx: int = 0        # repetition_penalty / no_repeat_ngram_size asked: the group's context gate (has_context)
     allow: int = 0      # allowed_token_ids asked: the group's mask gate (has_allow)
+    bad: int = 0        # bad_words asked (then ctx = 1 too): the group's bad-words gate (has_bad)
 
 
 def has_edits(xs) -> bool:
@@ -124,6 +133,13 @@ def has_allow(xs) -> bool:
     return any(map(operator.attrgetter("allow"), xs))
 
 
+def has_bad(xs) -> bool:
+    """Some Row (its flag) / Chunk (its sequence count) asks for bad_words: the
+    bad-words pass runs right after the repetition pass.  A flag of its own
+    like has_edits: the pass reads two per-slot tables and adds no row vector."""
+    return any(map(operator.attrgetter("nbad" if xs and type(xs[0]) is Chunk else "bad"), xs))
+
+
 @dataclass
 class GroupPlan:
     g: int                                  # group (microbatch) index
@@ -144,6 +160,8 @@ class GroupPlan:
     ctx: Optional[bool] = field(default=None, compare=False, repr=False)
     # has_allow(rows), likewise (never sent)
     allow: Optional[bool] = field(default=None, compare=False, repr=False)
+    # has_bad(rows), likewise (never sent)
+    bad: Optional[bool] = field(default=None, compare=False, repr=False)
 
     @property
     def n_final(self) -> int:
@@ -392,7 +410,31 @@ def _pack_group(gp: GroupPlan, ids: bool, ctx_ids: bool = False):
     if has_allow(gp.chunks) or (gp.rows is not None and has_allow(gp.rows)):
         # one more: 12, the edits' and the context's places held by None without any
         out += (None,) * (11 - len(out)) + (_pack_allow(gp),)
+    if has_bad(gp.chunks) or (gp.rows is not None and has_bad(gp.rows)):
+        # one more: 13, behind the mask's place (the context's is taken: an asking request has one)
+        out += (None,) * (12 - len(out)) + (_pack_bad(gp),)
     return out
+
+
+def _pack_bad(gp: GroupPlan) -> tuple:
+    """The bad_words of a group, the last element of its wire tuple: (the rows'
+    bad column or None, the chunks' -- (nbad column, offsets [n + 1] into the
+    concatenated entries of the chunks that carry theirs (the final asking
+    ones), end offsets int32, token offsets [n + 1], tokens int32) -- or
+    None)."""
+    import numpy as np
+
+    rows = np.array([r.bad for r in gp.rows], dtype=np.int8) if gp.rows is not None else None
+    ch = None
+    if gp.chunks:
+        bd = [c.bad or ((), ()) for c in gp.chunks]
+        eoff, toff = np.zeros(len(bd) + 1, dtype=np.int64), np.zeros(len(bd) + 1, dtype=np.int64)
+        np.cumsum([len(b[0]) for b in bd], out=eoff[1:])
+        np.cumsum([len(b[1]) for b in bd], out=toff[1:])
+        ends = np.fromiter(itertools.chain.from_iterable(b[0] for b in bd), dtype=np.int32, count=int(eoff[-1]))
+        toks = np.fromiter(itertools.chain.from_iterable(b[1] for b in bd), dtype=np.int32, count=int(toff[-1]))
+        ch = (np.array([c.nbad for c in gp.chunks], dtype=np.int32), eoff, ends, toff, toks)
+    return rows, ch
 
 
 def _pack_allow(gp: GroupPlan) -> tuple:
@@ -460,7 +502,7 @@ def _unpack_edits(ed) -> tuple:
     return (rows.tolist() if rows is not None else None), n.tolist(), edits
 
 
-def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None, al=None) -> GroupPlan:
+def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None, al=None, bw=None) -> GroupPlan:
     """Inverse of _pack_group.  Chunks sent without their token ids carry
     range(len) in their place (their stage reads only the lengths)."""
     gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb, kind=kind, fwd_rows=fwd_rows)
@@ -488,6 +530,16 @@ def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None
                 masks.append(buf[at: at + n] if n >= 0 else None)
                 at += max(n, 0)
             more_c.update(allow=flag.tolist(), mask=masks)
+    if bw is not None:
+        rb, cb = bw
+        if rb is not None:
+            more_r["bad"] = rb.tolist()
+        if cb is not None:
+            nb, eoff, ends, toff, toks = cb
+            eoff, ends, toff, toks = eoff.tolist(), ends.tolist(), toff.tolist(), toks.tolist()
+            more_c.update(nbad=nb.tolist(),
+                          bad=[(tuple(ends[a:b]), tuple(toks[c:d])) if b > a else None
+                               for a, b, c, d in zip(eoff, eoff[1:], toff, toff[1:])])
     if ch is not None:
         ints, floats, seeds, tok = ch
         gp.chunks = _unpack_cols(Chunk, _CHUNK_INTS, ints, floats, seed=seeds.tolist(),

@@ -15,8 +15,9 @@ that all stages execute:
     their prompts are prefilled by that step's item (chunked when
     PREFILL_CHUNK is set), and the final chunk's sample is their first token;
   * a sequence LEAVES its group at the step after its last token was
-    scheduled (max_new_tokens) or after its EOS was read back (stop_at_eos),
-    so a short request never waits behind a long one;
+    scheduled (max_new_tokens) or after its EOS (stop_at_eos) or the end of
+    one of its stop sequences was read back, so a short request never waits
+    behind a long one;
   * decode rows are kept compacted and padded to a power-of-two bucket, so
     the per-(group, bucket) hipGraphs stay valid across steps and requests;
   * sampled token ids come back to the host asynchronously (D2H copy + event
@@ -79,6 +80,8 @@ class Request:
     output: Optional[List[int]] = None
     error: Optional[BaseException] = None
     logprobs: Optional[Logprobs] = None  # set before finish() when params.logprobs is not None
+    finish_reason: Optional[str] = None  # "length" | "eos" | "stop", once finished without an error
+    stop_reason: Optional[int] = None    # the matched stop sequence's index in params.stop_list(), with "stop"
     _flag: bool = False
     _ev: Optional[threading.Event] = None
 
@@ -100,6 +103,8 @@ class Request:
 
     def finish(self, output=None, error=None) -> None:
         self.output, self.error = output, error
+        if error is None and self.finish_reason is None:
+            self.finish_reason = "length"
         self.t_done = time.monotonic()
         with _FINISH:
             self._flag = True
@@ -222,7 +227,8 @@ def make_batch_queue(max_batch: int, length_ratio: float = 4.0, native: bool = T
 # tests/test_sched_core.py)
 # ---------------------------------------------------------------------------
 
-EV_FIRST, EV_FINISH, EV_RELEASE = 1, 2, 4
+EV_FIRST, EV_FINISH, EV_RELEASE, EV_STOP = 1, 2, 4, 8
+MAX_STOP_LEN = 32  # tokens of the longest stop sequence, and of the tail a sequence with stops keeps
 
 
 @dataclass
@@ -241,6 +247,10 @@ class _Seq:
     stop: bool = False          # EOS read back (stop_at_eos): leave at the next step
     toks: List[int] = field(default_factory=list)  # assign_collect only
     finished: bool = False
+    # set_stops: (stop sequences as tuples, min_tokens) and the last generated
+    # tokens they are matched against; None / unused without stop sequences
+    stops: Optional[tuple] = None
+    tail: Optional[List[int]] = None
 
 
 @dataclass
@@ -320,6 +330,40 @@ class PySchedCore:
             raise ValueError("empty prompt")
         for a in zip(sids, prompt_lens, wants, stops):
             self.add(*a)
+
+    def set_stops(self, sid: int, flat_tokens, lengths, min_tokens: int) -> None:
+        """lsd_rt::SchedCore::set_stops: the stop sequences of a sequence that
+        has no token yet, lengths[e] tokens of flat_tokens each, tried in this
+        order against its last generated tokens; a match counts from token
+        min_tokens + 1 on."""
+        s = self.seqs.get(sid)
+        if s is None:
+            raise ValueError("set_stops: unknown sequence")
+        if s.ntok > 0:
+            raise ValueError("set_stops: the sequence has tokens already")
+        if any(not 1 <= n <= MAX_STOP_LEN for n in lengths):
+            raise ValueError("set_stops: a stop sequence holds 1 to 32 tokens")
+        if sum(lengths) != len(flat_tokens):
+            raise ValueError("set_stops: lengths do not add up to the tokens")
+        if not lengths:
+            s.stops = s.tail = None
+            return
+        ends = list(itertools.accumulate(lengths))
+        s.stops = ([tuple(flat_tokens[e - n: e]) for n, e in zip(lengths, ends)], int(min_tokens))
+        s.tail = []
+
+    @staticmethod
+    def _stop_match(s: "_Seq", tok: int) -> bool:
+        """The token, the ntok-th of the sequence (already counted), goes into
+        the tail; True when it completes a stop sequence and ntok > min_tokens."""
+        tail = s.tail
+        if len(tail) == MAX_STOP_LEN:
+            del tail[0]
+        tail.append(tok)
+        words, min_tokens = s.stops
+        if s.ntok <= min_tokens:
+            return False
+        return any(len(w) <= len(tail) and tuple(tail[len(tail) - len(w):]) == w for w in words)
 
     def has_work(self) -> bool:
         if self.waiting:
@@ -476,8 +520,12 @@ class PySchedCore:
         flags = EV_FIRST if s.ntok == 0 else 0
         s.ntok += 1
         s.toks.append(tok)
+        hit = s.stops is not None and self._stop_match(s, tok)
         if s.stop_at_eos and tok == eos:
             s.stop = True
+        elif hit:
+            s.stop = True
+            flags |= EV_STOP
         if s.ntok >= s.want or s.stop:
             s.finished = True
             flags |= EV_FINISH
@@ -491,8 +539,12 @@ class PySchedCore:
             return
         flags = EV_FIRST if s.ntok == 0 else 0
         s.ntok += 1
+        hit = s.stops is not None and self._stop_match(s, tok)
         if s.stop_at_eos and tok == eos:
             s.stop = True
+        elif hit:
+            s.stop = True
+            flags |= EV_STOP
         if s.ntok >= s.want or s.stop:
             s.finished = True
             flags |= EV_FINISH
@@ -533,6 +585,8 @@ class _Meta:
     edits: Optional[tuple] = None  # SamplingParams.logit_edits: (tokens, values, untils) sorted by token
     context: Optional[tuple] = None  # SamplingParams.context_knobs: (repetition_penalty as fp32, no_repeat_ngram_size)
     mask: Optional[bytes] = None  # the bytes of SamplingParams.allowed_mask: the allowed list as packed int32 words
+    stops: Optional[list] = None  # SamplingParams.stop_list: the stop sequences in the order they are tried
+    bad: Optional[tuple] = None  # SamplingParams.bad_word_entries: (exclusive end offsets, tokens back to back)
     rep: int = 0        # replica and KV slot, from the request's first prefill chunk
     slot: int = -1
     done: bool = False  # finished by this scheduler (plain flag: the readout loop's hot path)
@@ -568,6 +622,7 @@ class Scheduler(racecheck.Shared):
         self._edited = 0  # live requests with logit edits: _group looks at chunks and rows only then
         self._contexts = 0  # live requests with repetition_penalty / no_repeat_ngram_size, likewise
         self._allowing = 0  # live requests with allowed_token_ids, likewise
+        self._badwords = 0  # live requests with bad_words, likewise
 
     # -- admission ---------------------------------------------------------
     def submit(self, prompt_ids: List[int], params: SamplingParams) -> Request:
@@ -624,7 +679,7 @@ class Scheduler(racecheck.Shared):
             racecheck.note(self, "_pending")
             reqs = [self._pending.pop(i) for i in ids]
         meta, rng = self.meta, self._rng
-        lens, wants, stops = [], [], []
+        lens, wants, stops, asking = [], [], [], []
         for i, req in zip(ids, reqs):
             p = req.params
             seed = p.seed if p.seed is not None else rng.getrandbits(62)
@@ -638,10 +693,18 @@ class Scheduler(racecheck.Shared):
             if p.allowed_token_ids is not None:
                 meta[i].mask = p.allowed_mask(self.eng.mask_words).tobytes()
                 self._allowing += 1
+            if p.bad_words is not None and p.bad_word_entries() is not None:  # an empty list asks for nothing
+                meta[i].bad = p.bad_word_entries()
+                self._badwords += 1
+            if p.stop_token_ids or p.stop_sequences:
+                asking.append((i, p))
             lens.append(len(req.prompt_ids))
             wants.append(p.max_new_tokens)
             stops.append(bool(p.stop_at_eos))
         self.core.add_many(ids, lens, wants, stops)
+        for i, p in asking:  # the requests with stop sequences alone: the core matches their last tokens
+            st = meta[i].stops = p.stop_list()
+            self.core.set_stops(i, [t for w in st for t in w], [len(w) for w in st], p.min_new_tokens)
 
     def has_work(self) -> bool:
         """Anything left to plan OR to read back: token readouts still queued
@@ -725,10 +788,26 @@ class Scheduler(racecheck.Shared):
                 for r in gp.rows:
                     if meta[r.seq].mask is not None:
                         r.allow = 1
+        if self._badwords:
+            # requests with bad_words: every chunk says how many sequences and
+            # is a context chunk (the pass reads the slot's prompt + draws, so
+            # the prompt's length and ids travel as with an n-gram ban), the
+            # final chunk brings the entries, every row both gates
+            for c in gp.chunks:
+                m = meta[c.seq]
+                if m.bad is not None:
+                    c.nbad, c.plen = len(m.bad[0]), len(m.req.prompt_ids)
+                    if c.final:
+                        c.bad = m.bad
+            if changed:
+                for r in gp.rows:
+                    if meta[r.seq].bad is not None:
+                        r.bad = r.ctx = 1
         if changed:
             gp.edit = bool(self._edited) and any(r.nedits for r in gp.rows)
-            gp.ctx = bool(self._contexts) and any(r.ctx for r in gp.rows)
+            gp.ctx = bool(self._contexts or self._badwords) and any(r.ctx for r in gp.rows)
             gp.allow = bool(self._allowing) and any(r.allow for r in gp.rows)
+            gp.bad = bool(self._badwords) and any(r.bad for r in gp.rows)
         return gp
 
     # -- token readout -----------------------------------------------------------
@@ -817,6 +896,8 @@ class Scheduler(racecheck.Shared):
                     self._contexts -= 1
                 if m is not None and m.mask is not None:
                     self._allowing -= 1
+                if m is not None and m.bad is not None:
+                    self._badwords -= 1
                 if m is not None and flags & EV_FINISH and not m.done:
                     m.done = True
                     self._finish(m, done.get(sid, []))
@@ -836,6 +917,16 @@ class Scheduler(racecheck.Shared):
         slot is still the request's: it goes back to the pool after this
         readout at the earliest, and draws issued past the last token write
         records at or past len(toks) only."""
+        p = m.req.params
+        if p.stop_at_eos and toks and toks[-1] == self.eng.mcfg.eos_token_id:
+            m.req.finish_reason = "eos"
+        elif m.stops is not None:
+            # the rule the core stopped by: its first counting match ends the collected tokens
+            hit = p.stop_match(toks, m.stops)
+            if hit is not None:
+                m.req.finish_reason, m.req.stop_reason = "stop", hit
+                if not p.include_stop_in_output:
+                    toks = toks[: len(toks) - len(m.stops[hit])]
         n = m.logprobs
         if n >= 0:
             try:
@@ -855,7 +946,7 @@ class Scheduler(racecheck.Shared):
                 m.done = True
                 m.req.finish(error=err)
         self.meta.clear()
-        self._edited = self._contexts = self._allowing = 0
+        self._edited = self._contexts = self._allowing = self._badwords = 0
         self.core.reset()
         self.readouts.clear()
         with self._plock:

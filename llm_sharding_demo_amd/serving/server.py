@@ -16,10 +16,12 @@ Roles (env SHARD_ROLE, `server.py:21`):
   all          one process answers every endpoint (debug)
 Additions: optional sampling fields on /generate (temperature, top_k, top_p,
 min_p, presence_penalty, frequency_penalty, logprobs, logit_bias, banned_token_ids,
-min_new_tokens, repetition_penalty, no_repeat_ngram_size, allowed_token_ids, greedy, seed,
-stop_at_eos;
+min_new_tokens, repetition_penalty, no_repeat_ngram_size, allowed_token_ids, bad_words,
+bad_words_ids, stop, stop_token_ids, include_stop_in_output, greedy, seed, stop_at_eos;
 defaults = reference sampler; with logprobs the response gains a "logprobs" object
-beside "generated"), 422 on empty/over-long
+beside "generated"; with stop / stop_token_ids it gains "finish_reason" and, after
+a stop, "stop_reason"; a stop string is tokenised with the server's tokenizer as
+given and matches that tokenisation only), 422 on empty/over-long
 prompts (instead of the reference's 500, quirk Q9), GET /health, GET /metrics
 (Prometheus text).  Concurrent /generate calls are batched at decode-step
 granularity by the engine's continuous-batching scheduler
@@ -31,7 +33,7 @@ from __future__ import annotations
 
 import logging
 import time
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Union
 
 import torch
 from pydantic import BaseModel
@@ -39,7 +41,7 @@ from pydantic import BaseModel
 from ..config import EngineConfig, SamplingParams
 from ..utils import racecheck
 from ..utils.metrics import Metrics
-from ..utils.tokenizer import load_tokenizer
+from ..utils.tokenizer import encode_bad_words, encode_stops, load_tokenizer
 
 log = logging.getLogger("llm_sharding_demo_amd.server")
 
@@ -78,6 +80,16 @@ class GenerateReq(BaseModel):
     no_repeat_ngram_size: int = 0
     # the only tokens that may be drawn (None = the whole vocabulary): every other logit is -inf
     allowed_token_ids: Optional[List[int]] = None
+    # token sequences that may never be completed over prompt + output: as strings -- each tokenised
+    # with the server's tokenizer as given and, when that differs, with a leading space -- and as ids
+    bad_words: Optional[List[str]] = None
+    bad_words_ids: Optional[List[List[int]]] = None
+    # the request ends when its output completes one of these: strings -- each tokenised with the
+    # server's tokenizer as given; a stop string matches that tokenisation only -- and token ids.
+    # The matched tokens are left out of the output unless include_stop_in_output is set
+    stop: Optional[Union[str, List[str]]] = None
+    stop_token_ids: Optional[List[int]] = None
+    include_stop_in_output: bool = False
 
 
 def logprobs_json(lp) -> dict:
@@ -189,6 +201,11 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         if not _role_is("coordinator"):
             return {"error": "This instance is not coordinator."}
         ids = tok.encode(req.prompt)
+        bad = None
+        if req.bad_words is not None or req.bad_words_ids is not None:
+            bad = [list(w) for w in req.bad_words_ids or ()] + encode_bad_words(tok, req.bad_words or ())
+        stops = encode_stops(tok, req.stop) if req.stop is not None else None
+        asked_stop = req.stop is not None or req.stop_token_ids is not None
         sp = SamplingParams(temperature=req.temperature, top_k=req.top_k, greedy=req.greedy,
                             seed=req.seed, max_new_tokens=req.max_new_tokens,
                             stop_at_eos=req.stop_at_eos, top_p=req.top_p, min_p=req.min_p,
@@ -197,7 +214,9 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                             banned_token_ids=req.banned_token_ids, min_new_tokens=req.min_new_tokens,
                             repetition_penalty=req.repetition_penalty,
                             no_repeat_ngram_size=req.no_repeat_ngram_size,
-                            allowed_token_ids=req.allowed_token_ids)
+                            allowed_token_ids=req.allowed_token_ids, bad_words=bad,
+                            stop_token_ids=req.stop_token_ids, stop_sequences=stops,
+                            include_stop_in_output=req.include_stop_in_output)
         if req.max_new_tokens == 0 and req.logprobs is None:
             return {"generated": tok.decode(ids, skip_special_tokens=True)}
         if not ids:
@@ -206,8 +225,10 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         from ..runtime.scheduler import RequestTimeout
 
         lp = None
+        reason = ("length", None)
         try:
-            sp.validate(cfg.max_logprobs, cfg.max_logit_edits)
+            sp.validate(cfg.max_logprobs, cfg.max_logit_edits, cfg.max_bad_words, cfg.max_bad_word_tokens,
+                        cfg.max_stop_sequences)
             if req.max_new_tokens == 0:
                 from ..runtime.scheduler import Logprobs
 
@@ -218,11 +239,11 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                                      f"exceeds the context limit {engine.max_seq}")
                 req_ = engine.submit(ids, sp)
                 out = req_.wait(timeout=cfg.request_timeout_s)
-                lp = req_.logprobs
+                lp, reason = req_.logprobs, (req_.finish_reason, req_.stop_reason)
                 metrics.observe_request(len(out), time.perf_counter() - t0,
                                         ttft_s=(req_.t_first - req_.t_submit) if req_.t_first else None)
             else:
-                out, lp = http_generate(cfg, ids, sp, records=True)
+                out, lp, reason = http_generate(cfg, ids, sp, records=True, reasons=True)
                 metrics.observe_request(len(out), time.perf_counter() - t0)
         except ValueError as e:
             raise HTTPException(422, str(e))
@@ -235,6 +256,10 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         body = {"generated": tok.decode(ids + out, skip_special_tokens=True)}
         if lp is not None:
             body["logprobs"] = logprobs_json(lp)
+        if asked_stop:
+            body["finish_reason"] = reason[0]
+            if reason[1] is not None:
+                body["stop_reason"] = reason[1]
         return body
 
     @app.get("/health")
@@ -281,7 +306,8 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
     return app
 
 
-def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records: bool = False):
+def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records: bool = False,
+                  reasons: bool = False):
     """Reference-style coordinator loop over remote shards (`server.py:169-206`):
     full-sequence recompute on every step, hidden states relayed through here.
     Kept for deployments where the shards are separate hosts without xGMI.
@@ -290,7 +316,10 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
     here; logit_bias, banned_token_ids and
     min_new_tokens are applied on the host (ops/reference.py logit_edits; ids
     outside the vocabulary are ignored), allowed_token_ids behind them
-    (ops/reference.py allow_mask).  records=True: -> (tokens, the logprob
+    (ops/reference.py allow_mask), bad_words ahead of both over prompt +
+    output (ops/reference.py bad_words); stop_token_ids and stop_sequences end
+    the loop by SamplingParams.stop_match (reasons=True: -> (tokens, records,
+    (finish_reason, stop_reason))).  records=True: -> (tokens, the logprob
     records of a request that asked for them or None), computed on the host
     from the logits this loop already holds (ops/reference.py logprobs)."""
     import requests
@@ -315,6 +344,12 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
     if sp.allowed_token_ids is not None:
         allow = (torch.ones(1, dtype=torch.int32),
                  torch.from_numpy(sp.allowed_mask((cfg.model.vocab_padded + 31) // 32))[None])
+    bad = None
+    if sp.bad_words is not None and sp.bad_word_entries() is not None:
+        ends, toks = sp.bad_word_entries()
+        bad = (torch.tensor([len(ends)], dtype=torch.int32), torch.tensor([ends], dtype=torch.int32),
+               torch.tensor([toks], dtype=torch.int32))
+    stops, reason = sp.stop_list(), ("length", None)
     seq = list(ids)
     url_a = f"http://{cfg.shard_a_service}:{cfg.shard_port}/forward"
     url_b = f"http://{cfg.shard_b_service}:{cfg.shard_port}/forward_b"
@@ -325,6 +360,10 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
         r2 = requests.post(url_b, json={"hidden_states": hidden}, timeout=30)
         r2.raise_for_status()
         logits = torch.tensor(r2.json()["logits"], dtype=torch.float32)[0, -1:]
+        if bad is not None:
+            # a one-slot context table: the whole sequence so far as the prompt, draw 0
+            ctx = (torch.tensor([len(seq)], dtype=torch.int32), None, None, torch.tensor([seq], dtype=torch.int32))
+            ref.bad_words(logits, bad, ctx, torch.tensor([0]), None, min(vocab, logits.shape[1]))
         if table is not None:
             ref.logit_edits(logits, table, torch.tensor([0]), torch.tensor([step]), vocab)
         if allow is not None:
@@ -339,4 +378,15 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
             t, ti, tv = ref.logprobs(logits, torch.tensor([nxt]), [sp.logprobs], vocab, sp.logprobs)
             lp.token_logprobs.append(float(t[0]))
             lp.top_logprobs.append([(i, v) for i, v in zip(ti[0].tolist(), tv[0].tolist()) if i >= 0])
+        hit = sp.stop_match(out, stops) if stops else None
+        if hit is not None:
+            reason = ("stop", hit)
+            if not sp.include_stop_in_output:
+                keep = len(out) - len(stops[hit])
+                del out[keep:]  # the records' token list too
+                if lp is not None:
+                    del lp.token_logprobs[keep:], lp.top_logprobs[keep:]
+            break
+    if reasons:
+        return out, lp, reason
     return (out, lp) if records else out

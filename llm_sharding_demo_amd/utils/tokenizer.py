@@ -83,6 +83,22 @@ class BPETokenizer:
         return self.tok.decode(ids, skip_special_tokens=skip_special_tokens)
 
 
+def encode_stops(tok, stop) -> List[List[int]]:
+    """Stop strings (one string or a list) as token-id sequences: each string
+    tokenised as given -- a stop string matches that tokenisation only."""
+    return [tok.encode(w) for w in ([stop] if isinstance(stop, str) else stop)]
+
+
+def encode_bad_words(tok, words) -> List[List[int]]:
+    """bad_words strings as token-id sequences: each string tokenised as given
+    and, when that differs, with a leading space (vLLM's behaviour)."""
+    out = []
+    for word in words:
+        plain, spaced = tok.encode(word), tok.encode(" " + word)
+        out += [plain] if spaced == plain else [plain, spaced]
+    return out
+
+
 def load_tokenizer(model_id: str, arch: str = "gpt2", weights: Optional[str] = None,
                    eos_id: Optional[int] = None):
     for path in (os.environ.get("TOKENIZER_PATH"), weights, model_id):
