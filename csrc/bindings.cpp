@@ -92,6 +92,12 @@ hipError_t lsd_allow_mask(float* logits, long ld, int B, int V, const int* on, c
 hipError_t lsd_bad_words(float* logits, long ld, int B, int V, const int* cnt, const int* end, int N, const int* btok,
                          int T, const int* plen, const int* ctok, int L, int nslots, const int* slots,
                          const long long* step, float* segmax, long ldseg, hipStream_t st);
+hipError_t lsd_guide_mask(float* logits, long ld, int B, int V, const short* gcls, long Vp, const short* gnext,
+                          long cells, const int* gdim, int G, const int* gsl, int nslots, const int* slots,
+                          float* segmax, long ldseg, hipStream_t st);
+hipError_t lsd_guide_advance(int* gsl, int nslots, const short* gcls, long Vp, const short* gnext, long cells,
+                             const int* gdim, int G, int V, const int* slots, const int* tokens, const int* active,
+                             int B, hipStream_t st);
 hipError_t lsd_repeat_penalty(float* logits, long ld, int B, int V, const int* plen, const float* rpen, const int* ngram,
                               const int* tok, int L, int nslots, const int* slots, const long long* step,
                               float* segmax, long ldseg, hipStream_t st);
@@ -830,6 +836,75 @@ void allow_mask(torch::Tensor logits, int64_t V, torch::Tensor on, torch::Tensor
             "allow_mask");
 }
 
+// The layout checks the two guide passes share: gcls [G, Vp] and gnext [G, cells]
+// int16, gdim [G, 2] and gsl [slots, 2] int32, all contiguous.
+void need_guide_table(const torch::Tensor& gcls, const torch::Tensor& gnext, const torch::Tensor& gdim,
+                      const torch::Tensor& gsl, const char* what) {
+  need(gcls, torch::kInt16, "gcls");
+  need(gnext, torch::kInt16, "gnext");
+  need(gdim, torch::kInt32, "gdim");
+  need(gsl, torch::kInt32, "gsl");
+  TORCH_CHECK(gcls.dim() == 2 && gcls.is_contiguous() && gnext.dim() == 2 && gnext.is_contiguous() &&
+                  gnext.size(0) == gcls.size(0) && gdim.dim() == 2 && gdim.is_contiguous() &&
+                  gdim.size(0) == gcls.size(0) && gdim.size(1) == 2 && gsl.dim() == 2 && gsl.is_contiguous() &&
+                  gsl.size(1) == 2,
+              what, ": the table is contiguous gcls [G, Vp], gnext [G, cells], gdim [G, 2], gsl [slots, 2]");
+}
+
+// Per-request guided decoding, the mask (guide.hip).  Row i whose KV slot s =
+// slots[i] follows guide g = gsl[s, 0] in state gsl[s, 1] gets, in place on
+// its fp32 logits (repairing linear_f32's segment maxima, when given), -inf at
+// every token of [0, V) whose class has no next state there.  What the
+// arguments must satisfy beyond their types and layouts is lsd_guide_mask's to
+// refuse.
+void guide_mask(torch::Tensor logits, int64_t V, torch::Tensor gcls, torch::Tensor gnext, torch::Tensor gdim,
+                torch::Tensor gsl, torch::Tensor slots, c10::optional<torch::Tensor> segmax) {
+  need(logits, torch::kFloat32, "logits");
+  need(slots, torch::kInt32, "slots");
+  need_guide_table(gcls, gnext, gdim, gsl, "guide_mask");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits [B, width]");
+  const int64_t B = logits.size(0), ld = logits.size(1);
+  TORCH_CHECK(B <= 1 || logits.stride(0) == ld, "guide_mask: the rows of logits must be dense");
+  TORCH_CHECK(V >= 0 && V <= INT32_MAX, "guide_mask: V");
+  TORCH_CHECK(slots.numel() == B && slots.is_contiguous(), "guide_mask: slots must be contiguous [B]");
+  float* sm = nullptr;
+  long ldseg = 0;
+  if (segmax.has_value()) {
+    need(*segmax, torch::kFloat32, "segmax");
+    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && segmax->size(1) * 8 >= ld,
+                "segmax must be fp32 [B, >= logits row length / 8]");
+    sm = segmax->data_ptr<float>();
+    ldseg = B <= 1 ? segmax->size(1) : segmax->stride(0);
+  }
+  check_hip(lsd_guide_mask(logits.data_ptr<float>(), ld, (int)B, (int)V, gcls.data_ptr<int16_t>(), gcls.size(1),
+                           gnext.data_ptr<int16_t>(), gnext.size(1), gdim.data_ptr<int>(), (int)gcls.size(0),
+                           gsl.data_ptr<int>(), (int)gsl.size(0), slots.data_ptr<int>(), sm, ldseg, cur_stream()),
+            "guide_mask");
+}
+
+// Guided decoding, the step behind the draw (guide.hip): gsl[slots[i], 1] <-
+// the state after tokens[i], for active rows (all rows without `active`) on a
+// guided slot.
+void guide_advance(torch::Tensor gcls, torch::Tensor gnext, torch::Tensor gdim, torch::Tensor gsl, int64_t V,
+                   torch::Tensor slots, torch::Tensor tokens, c10::optional<torch::Tensor> active) {
+  need(slots, torch::kInt32, "slots");
+  need(tokens, torch::kInt32, "tokens");
+  need_guide_table(gcls, gnext, gdim, gsl, "guide_advance");
+  const int64_t B = tokens.numel();
+  TORCH_CHECK(V >= 0 && V <= INT32_MAX, "guide_advance: V");
+  TORCH_CHECK(slots.numel() == B && slots.is_contiguous() && tokens.is_contiguous(), "guide_advance: [B] vectors");
+  const int* act = nullptr;
+  if (active.has_value()) {
+    need(*active, torch::kInt32, "active");
+    TORCH_CHECK(active->numel() == B && active->is_contiguous(), "active must be contiguous int32 [B]");
+    act = active->data_ptr<int>();
+  }
+  check_hip(lsd_guide_advance(gsl.data_ptr<int>(), (int)gsl.size(0), gcls.data_ptr<int16_t>(), gcls.size(1),
+                              gnext.data_ptr<int16_t>(), gnext.size(1), gdim.data_ptr<int>(), (int)gcls.size(0),
+                              (int)V, slots.data_ptr<int>(), tokens.data_ptr<int>(), act, (int)B, cur_stream()),
+            "guide_advance");
+}
+
 // HF-style repetition_penalty and no_repeat_ngram_size (repeat.hip).  Row i
 // reads the context of its KV slot s = slots[i] -- tok[s, 0 .. min(plen[s] +
 // step[i], L)), the prompt and then the generated tokens (step absent = draw 0)
@@ -1109,6 +1184,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("until"), py::arg("slots"), py::arg("step") = py::none(), py::arg("segmax") = py::none());
   m.def("allow_mask", &allow_mask, py::arg("logits"), py::arg("V"), py::arg("on"), py::arg("bits"), py::arg("slots"),
         py::arg("segmax") = py::none());
+  m.def("guide_mask", &guide_mask, py::arg("logits"), py::arg("V"), py::arg("gcls"), py::arg("gnext"), py::arg("gdim"),
+        py::arg("gsl"), py::arg("slots"), py::arg("segmax") = py::none());
+  m.def("guide_advance", &guide_advance, py::arg("gcls"), py::arg("gnext"), py::arg("gdim"), py::arg("gsl"),
+        py::arg("V"), py::arg("slots"), py::arg("tokens"), py::arg("active") = py::none());
   m.def("repetition", &repetition, py::arg("logits"), py::arg("V"), py::arg("plen"), py::arg("rpen"), py::arg("ngram"),
         py::arg("tok"), py::arg("slots"), py::arg("step") = py::none(), py::arg("segmax") = py::none());
   m.def("bad_words", &bad_words, py::arg("logits"), py::arg("V"), py::arg("cnt"), py::arg("end"), py::arg("tok"),

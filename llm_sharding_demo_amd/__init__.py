@@ -11,9 +11,10 @@ from __future__ import annotations
 from typing import Optional
 
 from .config import MODEL_PRESETS, EngineConfig, ModelConfig, SamplingParams, get_model_config
+from .guide import TokenGuide, compile_choice, compile_regex
 
 __all__ = ["EngineConfig", "ModelConfig", "SamplingParams", "MODEL_PRESETS", "get_model_config",
-           "Engine", "LLM", "generate_text"]
+           "Engine", "LLM", "generate_text", "TokenGuide", "compile_regex", "compile_choice"]
 __version__ = "0.1.0"
 
 

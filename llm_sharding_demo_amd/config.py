@@ -180,6 +180,9 @@ MAX_BAD_WORDS_CEILING = 256  # sequences per request: one thread of the bad_word
 MAX_BAD_WORD_TOKENS_CEILING = 4096  # tokens of a request's bad_words in all
 MAX_STOP_SEQUENCES_CEILING = 64  # stop sequences per request (stop_token_ids and stop_sequences together)
 MAX_STOP_LEN = 32  # tokens of one stop sequence: the scheduler core keeps a request's last 32 tokens to match
+MAX_GUIDES_CEILING = 64  # rows of the last stage's guide table: guides in flight at once
+MAX_GUIDE_CLASSES_CEILING = 4096  # token classes of one guide: the mask kernel's LDS flags, one byte each
+MAX_GUIDE_CELLS_CEILING = 1 << 20  # states x classes of one guide
 MAX_BAD_WORD_LEN = 32  # tokens of one sequence: its prefix fits the kernel's 31-token context tail
 INT32_MAX = 2 ** 31 - 1
 
@@ -339,7 +342,46 @@ class SamplingParams:
     None).  A request carries at most EngineConfig.max_stop_sequences
     sequences of 1 to 32 tokens; the ids must lie in the vocabulary.  The
     defaults (None / None / False) are off: such a request takes the path it
-    always took."""
+    always took.
+
+    guide: None (off; nothing runs, travels or is allocated for the request)
+    or a guide.TokenGuide, a deterministic automaton over tokens
+    (guide.compile_regex / compile_choice build one from a regular expression
+    or a list of strings): the request starts in state 0, and before every
+    draw, the prefill draw (draw 0) included, every token t of the vocabulary
+    with next[state, cls[t]] < 0 has its fp32 logit set to -inf; behind the
+    draw the state becomes next[state, cls[drawn token]].  The state lives on
+    the last stage and advances inside the captured decode graphs: the host
+    never reads it.  The mask is the last edit of the logits: after the
+    repetition pass, the bad-words pass, the presence / frequency penalties,
+    the logit edits and the allowed-token mask, ahead of temperature, top-k,
+    top-p, min-p and the greedy argmax -- greedy requests are guided too.
+    Logprobs are taken after it: a token the guide forbids has logprob -inf.
+    EOS is an ordinary token of the guide; a compiled guide allows it exactly
+    where the match is complete, so with stop_at_eos the output matches the
+    pattern as a whole, and without an EOS (or when max_new_tokens ends the
+    request first) it is a prefix of a match.  A guide has at most
+    EngineConfig.max_guide_classes token classes and max_guide_cells = states
+    x classes cells, its vocab must be the model's and its eos the model's or
+    None, and every state reachable from the start must keep a token to draw.
+    No static check shows that a token stays drawable beside another field
+    that can itself produce -inf, so a guide is refused together with
+    banned_token_ids, allowed_token_ids, bad_words, no_repeat_ngram_size and
+    min_new_tokens > 0; it combines with temperature, top-k, top-p, min-p, the
+    presence / frequency penalties, repetition_penalty, finite logit_bias,
+    logprobs and the stop sequences.  Equal guides (TokenGuide.digest) share
+    one of the EngineConfig.max_guides rows of the last stage's table (G rows
+    of the classes of the padded vocabulary's Vp columns and of
+    max_guide_cells cells, and a (row, state) pair per KV slot: G x (2 Vp +
+    2 max_guide_cells + 8) + 8 x slots bytes, allocated when the first guided
+    request arrives); a row is pinned from submit until the request's KV slot
+    is released, a new guide takes a free row or the least recently used
+    unpinned one, and a request whose guide finds none is refused.  A row's
+    contents are never rewritten while an enqueued or in-flight kernel can
+    read them: the pin goes back once the tokens of the last item that held
+    one of the request's rows have been read back, and the state's step is
+    enqueued ahead of that token return.  Asking never changes another
+    request's draws."""
 
     temperature: float = 0.6
     top_k: int = 40
@@ -362,6 +404,7 @@ class SamplingParams:
     stop_token_ids: Optional[Sequence[int]] = None
     stop_sequences: Optional[Sequence[Sequence[int]]] = None
     include_stop_in_output: bool = False
+    guide: Optional["TokenGuide"] = None
 
     @property
     def has_stops(self) -> bool:
@@ -480,7 +523,8 @@ class SamplingParams:
         return tuple(zip(*rows)) if rows else None
 
     def validate(self, max_logprobs: int = MAX_LOGPROBS_CEILING, max_logit_edits: int = 300,
-                 max_bad_words: int = 64, max_bad_word_tokens: int = 512, max_stop_sequences: int = 16) -> None:
+                 max_bad_words: int = 64, max_bad_word_tokens: int = 512, max_stop_sequences: int = 16,
+                 max_guide_classes: int = 1024, max_guide_cells: int = 1 << 18) -> None:
         if self.max_new_tokens < 0:
             raise ValueError("max_new_tokens must be >= 0")
         m = self.min_new_tokens
@@ -502,6 +546,20 @@ class SamplingParams:
                 raise ValueError("allowed_token_ids must not be empty (None turns the mask off)")
             if any(t < 0 or t > INT32_MAX for t in ids):
                 raise ValueError("allowed_token_ids must be >= 0")
+        if self.guide is not None:
+            from .guide import TokenGuide
+
+            if not isinstance(self.guide, TokenGuide):
+                raise ValueError("guide must be None or a TokenGuide")
+            self.guide.validate(max_classes=max_guide_classes, max_cells=max_guide_cells)
+            clash = [name for name, on in (("banned_token_ids", bool(self.banned_token_ids)),
+                                           ("allowed_token_ids", self.allowed_token_ids is not None),
+                                           ("bad_words", bool(self.bad_words)),
+                                           ("no_repeat_ngram_size", G != 0),
+                                           ("min_new_tokens", m > 0)) if on]
+            if clash:
+                raise ValueError(f"guide cannot be combined with {', '.join(clash)}: each can set logits to -inf "
+                                 "itself, and no static check shows that a token stays drawable in every state")
         if not isinstance(self.include_stop_in_output, bool):
             raise ValueError("include_stop_in_output must be a bool")
         if self.stop_token_ids is not None or self.stop_sequences is not None:
@@ -667,8 +725,22 @@ class EngineConfig:
     # stop_sequences together); the scheduler core tries them at every token of
     # such a request.  At most 64.
     max_stop_sequences: int = 16
+    # Guided decoding (SamplingParams.guide): the distinct guides in flight at
+    # once, and the most token classes and states x classes cells one may have;
+    # size the last stage's guide table, G x (2 Vp + 2 max_guide_cells + 8) +
+    # 8 x slots bytes, allocated when the first such request arrives.  At most
+    # 64, 4096 and 1 << 20.
+    max_guides: int = 8
+    max_guide_classes: int = 1024
+    max_guide_cells: int = 1 << 18
 
     def __post_init__(self):
+        if not (1 <= self.max_guides <= MAX_GUIDES_CEILING):
+            raise ValueError(f"max_guides must be in [1, {MAX_GUIDES_CEILING}]")
+        if not (1 <= self.max_guide_classes <= MAX_GUIDE_CLASSES_CEILING):
+            raise ValueError(f"max_guide_classes must be in [1, {MAX_GUIDE_CLASSES_CEILING}]")
+        if not (1 <= self.max_guide_cells <= MAX_GUIDE_CELLS_CEILING):
+            raise ValueError(f"max_guide_cells must be in [1, {MAX_GUIDE_CELLS_CEILING}]")
         if not (1 <= self.max_stop_sequences <= MAX_STOP_SEQUENCES_CEILING):
             raise ValueError(f"max_stop_sequences must be in [1, {MAX_STOP_SEQUENCES_CEILING}]")
         if not (1 <= self.max_bad_words <= MAX_BAD_WORDS_CEILING):
@@ -717,6 +789,9 @@ class EngineConfig:
             max_bad_words=int(_env("MAX_BAD_WORDS", "64")),
             max_bad_word_tokens=int(_env("MAX_BAD_WORD_TOKENS", "512")),
             max_stop_sequences=int(_env("MAX_STOP_SEQUENCES", "16")),
+            max_guides=int(_env("MAX_GUIDES", "8")),
+            max_guide_classes=int(_env("MAX_GUIDE_CLASSES", "1024")),
+            max_guide_cells=int(_env("MAX_GUIDE_CELLS", str(1 << 18))),
         )
         if cfg.split_points and cfg.num_stages == 1:
             cfg.num_stages = len(cfg.split_points) + 1

@@ -153,6 +153,18 @@ class ReferenceBackend(Backend):
         on the fp32 logits, after the edits and ahead of the sampler."""
         ref.allow_mask(logits, table, slots, vocab)
 
+    def guide_mask(self, logits, table, slots, vocab: int) -> None:
+        """The rows' guides (table = the last stage's gcls, gnext, gdim, gsl):
+        -inf at every token of [0, vocab) that the state of the row's slot
+        does not allow, in place on the fp32 logits, the last edit ahead of
+        the sampler."""
+        ref.guide_mask(logits, table, slots, vocab)
+
+    def guide_advance(self, table, slots, tokens, vocab: int, active=None) -> None:
+        """Behind the draw: the state of every active guided row's slot
+        becomes the one its drawn token leads to."""
+        ref.guide_advance(table, slots, tokens, vocab, active)
+
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         ref.record_tokens(hist, slots, step, tokens, active, back)
 

@@ -414,6 +414,15 @@ class HipBackend(Backend):
         # slot gave no allowed list return at once; the segment maxima are repaired too
         self.C.allow_mask(logits, vocab, table[0], table[1], slots, getattr(logits, "_lsd_segmax", None))
 
+    def guide_mask(self, logits, table, slots, vocab: int) -> None:
+        # guide.hip: one workgroup per row, the last edit ahead of the draw; rows
+        # whose slot follows no guide return at once; the segment maxima are repaired too
+        self.C.guide_mask(logits, vocab, *table, slots, getattr(logits, "_lsd_segmax", None))
+
+    def guide_advance(self, table, slots, tokens, vocab: int, active=None) -> None:
+        # guide.hip: one thread per row, behind the draw
+        self.C.guide_advance(*table, vocab, slots, tokens, active)
+
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         self.C.record_tokens(hist, slots, step, tokens, active, back)
 

@@ -377,6 +377,95 @@ def record_context(table, slots: torch.Tensor, step: Optional[torch.Tensor], tok
             tok[s, j] = int(tokens[i])
 
 
+def _guide_state(table, s: int) -> Optional[tuple]:
+    """(guide row g, state, S, C) of KV slot `s` when the guide passes act on
+    it: the slot lies in the table, g in [0, G), the state in [0, S) and its
+    row of C cells, 1 <= C <= 4096 (the classes the mask kernel's LDS flags
+    hold), within the row's max_cells; None otherwise."""
+    gcls, gnext, gdim, gsl = table
+    if not 0 <= s < gsl.shape[0]:
+        return None
+    g, st = int(gsl[s, 0]), int(gsl[s, 1])
+    if not 0 <= g < gcls.shape[0]:
+        return None
+    S, C = int(gdim[g, 0]), int(gdim[g, 1])
+    if st < 0 or st >= S or not 1 <= C <= 4096 or (st + 1) * C > gnext.shape[1]:
+        return None
+    return g, st, S, C
+
+
+def guide_mask(logits: torch.Tensor, table, slots: torch.Tensor, vocab: int,
+               segmax: Optional[torch.Tensor] = None):
+    """Per-request guided decoding, the mask: after `allow_mask`, the last edit
+    ahead of `sample` and `logprobs`.
+
+    table = (gcls [G, Vp] int16, gnext [G, max_cells] int16, gdim [G, 2] int32,
+    gsl [slots, 2] int32): guide row g holds a TokenGuide -- the class of every
+    logits column, its next[S, C] row-major, (S, C) -- and gsl[s] = (the guide
+    row of KV slot s or -1, its current state).  Row r reads (g, state) of its
+    slot s = slots[r]; a slot outside the table, g outside [0, G), a state
+    outside [0, S) or a state row that does not fit max_cells leaves the row
+    untouched, whatever the tables hold.  Otherwise every t in [0, vocab)
+    whose class c = gcls[g, t] is outside [0, C) or has gnext[g, state * C +
+    c] < 0 gets
+        logit[t] <- -inf
+    a pure select: every other logit keeps its bits.  Columns at or past
+    `vocab` are never written and their classes never matter.  The tables are
+    only read.
+
+    fp32 `logits` [B, >= vocab] are rewritten in place and returned; `segmax`
+    as in `allow_mask`: every 8-logit segment that holds a cleared t < vocab is
+    recomputed as the maximum of its 8 stored logits, padding columns included.
+    """
+    assert logits.dtype == torch.float32, "guide_mask rewrites fp32 logits in place"
+    gcls, gnext, gdim, gsl = table
+    width, dev = logits.shape[1], logits.device
+    assert vocab <= width <= gcls.shape[1]
+    t = torch.arange(vocab, device=dev)
+    for r in range(logits.shape[0]):
+        st = _guide_state(table, int(slots[r]))
+        if st is None:
+            continue
+        g, s, _, C = st
+        c = gcls[g, :vocab].to(dev).long()
+        inside = (c >= 0) & (c < C)
+        cell = gnext[g].to(dev)[(s * C + c.clamp(0, C - 1)).clamp(0, gnext.shape[1] - 1)]
+        clear = ~(inside & (cell >= 0))
+        logits[r, :vocab] = torch.where(clear, torch.full_like(logits[r, :vocab], -math.inf), logits[r, :vocab])
+        if segmax is not None:
+            segs = torch.unique(t[clear] >> 3)
+            if segs.numel():
+                idx = segs[:, None] * 8 + torch.arange(8, device=dev)
+                segmax[r, segs] = logits[r][idx].max(dim=1).values
+    return logits if segmax is None else (logits, segmax)
+
+
+def guide_advance(table, slots: torch.Tensor, tokens: torch.Tensor, vocab: int,
+                  active: Optional[torch.Tensor] = None) -> None:
+    """Guided decoding, the step behind the draw: for every active row (all
+    rows when `active` is None) whose slot holds a valid (g, state) -- as
+    `guide_mask` decides -- and whose token lies in [0, vocab), with a class c
+    = gcls[g, token] in [0, C):
+        gsl[slot].state <- gnext[g, state * C + c]
+    (-1 once the guide is dead: the mask pass then leaves the row alone).
+    Everything else is left as it is.  Each row owns its slot."""
+    gcls, gnext, _, gsl = table
+    new = []
+    for i in range(tokens.shape[0]):
+        if active is not None and int(active[i]) == 0:
+            continue
+        s, tok = int(slots[i]), int(tokens[i])
+        st = _guide_state(table, s)
+        if st is None or not 0 <= tok < vocab:
+            continue
+        g, cur, _, C = st
+        c = int(gcls[g, tok])
+        if 0 <= c < C:
+            new.append((s, int(gnext[g, cur * C + c])))
+    for s, v in new:
+        gsl[s, 1] = v
+
+
 def record_tokens(hist: torch.Tensor, slots: torch.Tensor, step: Optional[torch.Tensor], tokens: torch.Tensor,
                   active: Optional[torch.Tensor] = None, back: int = 0) -> None:
     """hist[slots[i], step[i] - back] = tokens[i] for active rows (all rows

@@ -3,12 +3,12 @@
 A `StageWorker` (parallel/pipeline.py) moves a step through its stage; its
 `DrawStage` decides what runs on the logits of the last stage: the repetition
 pass, the bad-words pass, the penalty pass, the logit edits, the allowed-token
-mask, the sampler, the token history, the context and the logprob records,
-for the decode rows of a group (`rows`,
+mask, the guide's mask, the sampler, the guide's step, the token history, the
+context and the logprob records, for the decode rows of a group (`rows`,
 captured into the decode graphs) and for the first draw of a finished prompt
 (`finals`, eager); `chunks` copies the prompts that the repetition pass reads
-into its table as they are prefilled.  It owns the six per-KV-slot tables
-these passes read and write, and counts the items that ran each pass.  Every
+into its table as they are prefilled.  It owns the six per-KV-slot tables and
+the guide table these passes read and write, and counts the items that ran each pass.  Every
 stage has one; off the last stage it stays empty.
 """
 from __future__ import annotations
@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from ..runtime.batch import SamplingState
-from ..runtime.plan import has_allow, has_bad, has_context, has_edits, row_features
+from ..runtime.plan import has_allow, has_bad, has_context, has_edits, has_guide, row_features
 from ..utils import racecheck
 
 
@@ -51,6 +51,10 @@ class DrawStage(racecheck.Shared):
         self.bad_tab: Optional[tuple] = None  # bad_words: the sequences back to back, N = max_bad_words, T = max_bad_word_tokens
         self.max_bad_words, self.max_bad_word_tokens = 64, 512
         self.bad_words_launches = 0
+        self.guide_tab: Optional[tuple] = None  # guide: G guides' classes and cells, and (guide row, state) per KV slot
+        self.max_guides, self.max_guide_cells = 8, 1 << 18
+        self.guide_launches = 0
+        self._guide_lock = racecheck.Lock("draw.guide")  # the table is first asked for by a submitting thread (load_guide)
 
     # ------------------------------------------------------------------
     # tables
@@ -167,12 +171,70 @@ class DrawStage(racecheck.Shared):
                 torch.cuda.current_stream(dev).synchronize()
         return self.bad_tab
 
+    def _guide_tab(self) -> tuple:
+        """Guide table: (gcls [G, Vp] int16, gnext [G, max_guide_cells] int16,
+        gdim [G, 2] int32, gsl [KV slots, scratch and compat included, 2]
+        int32), G = max_guides: row g holds one TokenGuide -- the class of
+        every column of the padded vocabulary (columns at or past the
+        vocabulary: 0), its next[S, C] row-major, (S, C) -- and gsl[s] = (the
+        guide row the request on slot s follows or -1, its current state).
+        G x (2 Vp + 2 max_guide_cells + 8) + 8 x slots bytes.  Like the edit
+        table's counts the stale entries of gsl ARE read -- by the other rows
+        of a group with a guided row, and by every pad row on the scratch slot
+        -- so they start at (-1, 0), "off", and the guide rows at zero, visibly
+        to every lane: this thread waits for the fill (_edit_tab).  Allocated
+        once, outside any capture, and never reallocated: captured graphs hold
+        its addresses.  From then on every final chunk writes its slot's entry
+        (finals), and the engine writes a guide's row before the first request
+        that follows it is planned (load_guide)."""
+        with self._guide_lock:
+            if self.guide_tab is None:
+                S, G, dev = self.slots, self.max_guides, self.stage.device
+                gsl = torch.zeros(S, 2, dtype=torch.int32, device=dev)
+                gsl[:, 0] = -1
+                tab = (torch.zeros(G, self.stage.cfg.vocab_padded, dtype=torch.int16, device=dev),
+                       torch.zeros(G, self.max_guide_cells, dtype=torch.int16, device=dev),
+                       torch.zeros(G, 2, dtype=torch.int32, device=dev), gsl)
+                if dev.type == "cuda":
+                    torch.cuda.current_stream(dev).synchronize()
+                self.guide_tab = tab
+            return self.guide_tab
+
+    def load_guide(self, row: int, guide) -> None:
+        """Write `guide` (a validated TokenGuide) into row `row` of the guide
+        table.  For the engine's submitting thread, before the first request
+        that follows the guide is handed to the scheduler.  The row's contents
+        are never rewritten while an enqueued or in-flight kernel can read
+        them: the engine reuses a row only when no request pins it, and a
+        request unpins its row when its KV slot is released -- after the
+        tokens of the last item that held one of its rows were read back, and
+        guide_advance is enqueued ahead of the token return, so by then
+        nothing reads the row; a stale gsl entry that still names it belongs
+        to a free slot, which no row of a plan uses until a final chunk has
+        rewritten the entry.  The copy is waited for here, and the whole runs
+        under a shared hold of the capture gate (a sibling stage thread may be
+        capturing), as fetch_logprobs does."""
+        dev = self.stage.device
+        with self._gpu():
+            gcls, gnext, gdim, _ = self._guide_tab()
+            S, C, V = guide.S, guide.C, guide.vocab
+            if not 0 <= row < gcls.shape[0] or V > gcls.shape[1] or S * C > gnext.shape[1]:
+                raise ValueError(f"guide: row {row}, vocabulary {V} or {S} x {C} cells do not fit the guide table "
+                                 f"({gcls.shape[0]} rows, {gcls.shape[1]} columns, {gnext.shape[1]} cells)")
+            cls = np.zeros(gcls.shape[1], dtype=np.int16)
+            cls[:V] = guide.cls
+            gcls[row].copy_(torch.from_numpy(cls))
+            gnext[row, : S * C].copy_(torch.from_numpy(np.ascontiguousarray(guide.next).reshape(-1)))
+            gdim[row].copy_(torch.tensor([S, C], dtype=torch.int32))
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()
+
     def prepare(self, feats: tuple) -> None:
         """A composition with the features (cut, pen, lp, edit[, ctx[, allow[,
-        bad]]]) is being applied: what they need -- the token history, the
-        logprob records, the edit table, the context table, the allowed-token
-        table, the bad-words table -- allocated here, on the host side of the
-        change (never inside a capture)."""
+        bad[, guide]]]]) is being applied: what they need -- the token history,
+        the logprob records, the edit table, the context table, the
+        allowed-token table, the bad-words table, the guide table -- allocated
+        here, on the host side of the change (never inside a capture)."""
         _, pen, lp, edit, *more = feats
         if more and more[0]:
             self._ctx_tab()
@@ -181,6 +243,8 @@ class DrawStage(racecheck.Shared):
         if more[2:] and more[2]:
             self._ctx_tab()
             self._bad_tab()
+        if more[3:] and more[3]:
+            self._guide_tab()
         if pen:
             self._hist()
         if lp:
@@ -214,6 +278,8 @@ class DrawStage(racecheck.Shared):
             self.allow_launches += 1
         if gs.bad:
             self.bad_words_launches += 1
+        if gs.guide:
+            self.guide_launches += 1
 
     def chunks(self, gs, chunks) -> None:
         """Prefill chunks are about to run on the last stage (every prefill
@@ -271,7 +337,11 @@ class DrawStage(racecheck.Shared):
         the edits: the sampler and the logprob kernel see the masked logits.
         One with a row that gave bad_words -- a context row too -- runs the
         bad-words pass right after the repetition pass, which reads the same
-        context.  Any other runs the sampler alone."""
+        context.  One with a row that follows a guide runs the guide's mask
+        right after the allowed-token mask -- the last edit: the sampler and
+        the logprob kernel see it -- and the guide's step behind the sampler,
+        beside the records and ahead of the token return.  Any other runs the
+        sampler alone."""
         be, V = self.stage.backend, self.stage.cfg.vocab_size
         slots, step, out = gs.slots[:b], gs.sstep[:b], gs.tokret[:b]
         if gs.ctx:
@@ -284,7 +354,11 @@ class DrawStage(racecheck.Shared):
             be.logit_edits(logits, self.edit_tab, slots, step, V)
         if gs.allow:
             be.allow_mask(logits, self.allow_tab, slots, V)
+        if gs.guide:
+            be.guide_mask(logits, self.guide_tab, slots, V)
         be.sample_into(logits, gs.samp(b), V, out, meta)
+        if gs.guide:
+            be.guide_advance(self.guide_tab, slots, out, V, gs.active[:b])
         if gs.pen:
             # the sampler has advanced the counters: the draw used counter - 1
             be.record_tokens(self.pen_hist, slots, step, out, gs.active[:b], 1)
@@ -312,16 +386,21 @@ class DrawStage(racecheck.Shared):
         and the mask pass runs last ahead of the draw.  So does the bad-words
         table: every final chunk writes its slot's count, zero included, an
         asking one its end offsets and tokens too, and the bad-words pass
-        runs right after the repetition pass, over the prompt."""
+        runs right after the repetition pass, over the prompt.  The guide
+        table likewise: once it exists every final chunk writes its slot's
+        entry, (its guide's row or -1, state 0) -- a request that reuses a slot
+        inherits nothing -- the guide's mask runs with the start state last
+        ahead of the draw, and the guide's step behind it."""
         be, V, dev = self.stage.backend, self.stage.cfg.vocab_size, self.stage.device
         _, pen, lp = row_features(fc)
-        ed, cx, al, bw = has_edits(fc), has_context(fc), has_allow(fc), has_bad(fc)
+        ed, cx, al, bw, gd = has_edits(fc), has_context(fc), has_allow(fc), has_bad(fc), has_guide(fc)
         tab = self._edit_tab() if ed or self.edit_tab is not None else None
         atab = self._allow_tab() if al or self.allow_tab is not None else None
         btab = self._bad_tab() if bw or self.bad_tab is not None else None
+        gtab = self._guide_tab() if gd or self.guide_tab is not None else None
         slots = nlp = None
-        if tab is not None or atab is not None or btab is not None or pen or lp or cx:
-            slots, nlp = self._stage_finals(gs, fc, tab, atab, btab)
+        if tab is not None or atab is not None or btab is not None or gtab is not None or pen or lp or cx:
+            slots, nlp = self._stage_finals(gs, fc, tab, atab, btab, gtab)
         if cx:
             be.repetition(logits, self._ctx_tab(), slots, None, V)
             self.repetition_launches += 1
@@ -334,7 +413,12 @@ class DrawStage(racecheck.Shared):
         if al:
             be.allow_mask(logits, atab, slots, V)
             self.allow_launches += 1
+        if gd:
+            be.guide_mask(logits, gtab, slots, V)
+            self.guide_launches += 1
         ids = be.sample(logits, SamplingState.of(fc, dev), V)
+        if gd:
+            be.guide_advance(gtab, slots, ids, V, None)
         if pen:
             be.record_tokens(self._hist(), slots, None, ids, None, 0)
             self.penalty_launches += 1
@@ -346,7 +430,7 @@ class DrawStage(racecheck.Shared):
         return ids
 
     def _stage_finals(self, gs, fc, tab: Optional[tuple], atab: Optional[tuple] = None,
-                      btab: Optional[tuple] = None) -> tuple:
+                      btab: Optional[tuple] = None, gtab: Optional[tuple] = None) -> tuple:
         """What the passes around the first draw of `fc` read, on the device
         in ONE host-to-device copy through the group's pinned staging ring:
         [slots J | logprob widths J | edit counts J], then with n edits among
@@ -357,6 +441,8 @@ class DrawStage(racecheck.Shared):
         from the copy too.  With a bad-words table `btab` then [sequence
         counts J], and with m sequences of t tokens among them [flat end index
         m | end offsets m | flat token index t | tokens t], written likewise.
+        With a guide table `gtab` then [guide rows J | states J] (the chunk's
+        guide row or -1, 0), written to the slots' entries.
         -> (slots, widths)."""
         cols = [[c.slot for c in fc], [c.logprobs for c in fc], [c.nedits for c in fc]]
         if tab is not None:
@@ -395,6 +481,10 @@ class DrawStage(racecheck.Shared):
                          [e for c in words for e in c.bad[0]],
                          np.concatenate([c.slot * T + np.arange(len(c.bad[1])) for c in words]),
                          [t for c in words for t in c.bad[1]]]
+        if gtab is not None:
+            if any(not -1 <= c.guide < gtab[0].shape[0] or not 0 <= c.slot < self.slots for c in fc):
+                raise ValueError(f"a final chunk's guide row lies outside the guide table's {gtab[0].shape[0]} rows")
+            cols += [[c.guide for c in fc], [0] * len(fc)]
         arr = np.concatenate([np.asarray(c, dtype=np.int32) for c in cols])
         dev = self.stage.device
         if dev.type == "cuda":
@@ -403,6 +493,10 @@ class DrawStage(racecheck.Shared):
         else:
             buf = torch.from_numpy(arr)
         slots, nlp, counts, *more = buf.split([len(c) for c in cols])
+        if gtab is not None:
+            gsl = gtab[3]
+            gsl.index_copy_(0, slots.long(), torch.stack(more[-2:], dim=1))
+            more = more[:-2]
         edits, more = (more[:4], more[4:]) if tab is not None and ent else ((), more)
         if tab is not None:
             cnt.index_copy_(0, slots.long(), counts)

@@ -44,7 +44,7 @@ import torch
 from ..models.stage import StageModel
 from ..runtime.batch import BatchMeta, MixedMeta
 from ..runtime.plan import (NO_FEATURES, ROW_FIELDS, GroupPlan, StepPlan, device_fields, has_allow, has_bad,
-                            has_context, has_edits, pack_rows, packed_size, row_features)
+                            has_context, has_edits, has_guide, pack_rows, packed_size, row_features)
 from ..utils.tracing import trace_range
 from ..utils import racecheck
 from .comm import Handle, SendHandle, Transport
@@ -221,6 +221,11 @@ class GroupState(racecheck.Shared):
         # like `edit` -- a per-slot table, no row vector -- and the seventh
         # feature in the decode graphs' key
         self.bad = False
+        # a row that follows a guide (plan.has_guide): the guide's mask runs
+        # last ahead of the sampler, its step behind it.  A flag like `edit`
+        # -- the guide table and the slots' states, no row vector -- and the
+        # eighth feature in the decode graphs' key (_graph_key puts it ahead of ctx)
+        self.guide = False
         if w.last:
             for f in ROW_FIELDS:  # the sampler's row vectors, idle: temp, topk, greedy, seeds, sstep, ...
                 setattr(self, f.vec, torch.full((cap,), f.idle, dtype=getattr(torch, f.dtype), device=dev))
@@ -651,7 +656,7 @@ class StageWorker(racecheck.Shared):
             if self.P > 1 and not io:
                 return False
             gs = self.groups[gp.g]
-            key = (gp.b, gp.ctxb, io, *self._features(gp, gs))  # after this item's change
+            key = self._graph_key(gp, io, self._features(gp, gs))  # after this item's change
             ent = gs.graphs.get(key)
             if ent is None:
                 return False
@@ -955,14 +960,14 @@ class StageWorker(racecheck.Shared):
         self.mixed_items += 1
 
     def _features(self, gp: GroupPlan, gs: GroupState) -> tuple:
-        """(cut, pen, lp, edit, ctx, allow, bad) of the group once this item ran:
-        the current ones, or those of the item's new composition -- one pass over
-        its rows, kept with the plan item, so whichever path runs it reads the
-        same seven."""
+        """(cut, pen, lp, edit, ctx, allow, bad, guide) of the group once this
+        item ran: the current ones, or those of the item's new composition -- one
+        pass over its rows, kept with the plan item, so whichever path runs it
+        reads the same eight."""
         if gp.rows is None:
-            return gs.cut, gs.pen, gs.lp, gs.edit, gs.ctx, gs.allow, gs.bad
+            return gs.cut, gs.pen, gs.lp, gs.edit, gs.ctx, gs.allow, gs.bad, gs.guide
         if not self.last:
-            return NO_FEATURES + (False, False, False, False)
+            return NO_FEATURES + (False, False, False, False, False)
         if gp.feats is None:
             gp.feats = row_features(gp.rows)
         if gp.edit is None:
@@ -973,7 +978,16 @@ class StageWorker(racecheck.Shared):
             gp.allow = has_allow(gp.rows)
         if gp.bad is None:
             gp.bad = has_bad(gp.rows)
-        return gp.feats + (gp.edit, gp.ctx, gp.allow, gp.bad)
+        if gp.guide is None:
+            gp.guide = has_guide(gp.rows)
+        return gp.feats + (gp.edit, gp.ctx, gp.allow, gp.bad, gp.guide)
+
+    @staticmethod
+    def _graph_key(gp: GroupPlan, io: bool, feats: tuple) -> tuple:
+        """A decode graph's key from _features' eight: the guide flag stands
+        ahead of ctx, so the key still ends with (ctx, allow, bad)."""
+        cut, pen, lp, edit, ctx, allow, bad, guide = feats
+        return (gp.b, gp.ctxb, io, cut, pen, lp, edit, guide, ctx, allow, bad)
 
     def _set_features(self, gs: GroupState, feats: tuple) -> None:
         """A composition change is being applied: the group's features from
@@ -983,6 +997,7 @@ class StageWorker(racecheck.Shared):
         gs.ctx = bool(more and more[0])
         gs.allow = bool(more[1:] and more[1])
         gs.bad = bool(more[2:] and more[2])
+        gs.guide = bool(more[3:] and more[3])
         self.draw.prepare(feats)
 
     def _apply_rows(self, gp: GroupPlan, gs: GroupState) -> None:
@@ -1203,7 +1218,7 @@ class StageWorker(racecheck.Shared):
         slot[2] = True
 
     def _decode(self, gp: GroupPlan, gs: GroupState, inp: torch.Tensor, io: bool = False) -> torch.Tensor:
-        key = (gp.b, gp.ctxb, io, gs.cut, gs.pen, gs.lp, gs.edit, gs.ctx, gs.allow, gs.bad)
+        key = self._graph_key(gp, io, (gs.cut, gs.pen, gs.lp, gs.edit, gs.ctx, gs.allow, gs.bad, gs.guide))
         lane = self.lane_of(gp.g)
         self.draw.count(gs)
 

@@ -39,6 +39,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from ..config import EngineConfig, SamplingParams
+from ..guide import GuideRows
 from ..utils import racecheck
 from ..models.stage import StageModel
 from ..parallel.comm import (DeviceLoopFabric, GlooPlanChannel, LocalFabric, LocalPlanChannel,
@@ -231,6 +232,9 @@ class Engine(racecheck.Shared):
         # one KV-slot pool per pipeline replica (the scheduler allocates for all)
         self.slot_pools = [_make_slot_allocator(self.kv_slots) for _ in range(self.R)]
         self.slots = self.slot_pools[0]
+        # the rows of the last stage's guide table (SamplingParams.guide): which
+        # guide each holds and how many live requests pin it
+        self.guides = GuideRows(cfg.max_guides)
         self.scheduler = Scheduler(self, self.M, self.group_cap)
         if self.rank == 0:
             self.workers[0].readout = self.scheduler.on_readout
@@ -352,6 +356,7 @@ class Engine(racecheck.Shared):
         w.draw.max_logprobs = self.cfg.max_logprobs
         w.draw.max_logit_edits = self.cfg.max_logit_edits
         w.draw.max_bad_words, w.draw.max_bad_word_tokens = self.cfg.max_bad_words, self.cfg.max_bad_word_tokens
+        w.draw.max_guides, w.draw.max_guide_cells = self.cfg.max_guides, self.cfg.max_guide_cells
         return w
 
     @property
@@ -372,7 +377,20 @@ class Engine(racecheck.Shared):
     # ------------------------------------------------------------------
     def _validate(self, prompt: List[int], sp: SamplingParams) -> None:
         sp.validate(self.cfg.max_logprobs, self.cfg.max_logit_edits, self.cfg.max_bad_words,
-                    self.cfg.max_bad_word_tokens, self.cfg.max_stop_sequences)
+                    self.cfg.max_bad_word_tokens, self.cfg.max_stop_sequences,
+                    max_guide_classes=self.cfg.max_guide_classes, max_guide_cells=self.cfg.max_guide_cells)
+        if sp.guide is not None:
+            g = sp.guide
+            if g.vocab != self.mcfg.vocab_size:
+                raise ValueError(f"guide: built for a vocabulary of {g.vocab} tokens, the model's has "
+                                 f"{self.mcfg.vocab_size}")
+            if g.eos is not None and g.eos != self.mcfg.eos_token_id:
+                raise ValueError(f"guide: its EOS token {g.eos} is not the model's ({self.mcfg.eos_token_id})")
+            if self.mode == "dist":
+                # the guide's table is written directly into the last stage's
+                # memory; shipping it to a rank process over the control plane
+                # is not built
+                raise ValueError("a guide needs the last stage in the coordinator process")
         if sp.has_stops:
             for w in sp.stop_list():
                 for t in w:
@@ -466,6 +484,51 @@ class Engine(racecheck.Shared):
         the widest logits a last stage draws from (the padded vocabulary)."""
         return (self.mcfg.vocab_padded + 31) // 32
 
+    def pin_guide(self, guide) -> int:
+        """The row of the last stages' guide table that holds `guide`, pinned
+        for one more request (-1 without a guide).  Equal guides share a row;
+        a new one takes a free row or the least recently used row no live
+        request pins, and is written there -- on every last stage of this
+        process, waited for -- before this returns: the request reaches the
+        scheduler only afterwards.  With every row pinned by other guides: a
+        ValueError that names max_guides.  Thread-safe."""
+        if guide is None:
+            return -1
+        with self.guides.lock:
+            row, fresh = self.guides.acquire(guide)
+            if fresh:
+                try:
+                    for w in self.workers:
+                        if w.last:
+                            w.draw.load_guide(row, guide)
+                except BaseException:
+                    self.guides.forget(row)
+                    raise
+        return row
+
+    def unpin_guide(self, row: Optional[int]) -> None:
+        """A request gives its pin back (its KV slot was released, or it never
+        got one); None: every request failed."""
+        if row is None:
+            self.guides.reset()
+        elif row >= 0:
+            self.guides.release(row)
+
+    def _pin_guides(self, params: List[SamplingParams]) -> Optional[List[int]]:
+        """pin_guide for a batch: None when no request follows a guide; all
+        pins go back when one cannot be had."""
+        if not any(sp.guide is not None for sp in params):
+            return None
+        rows: List[int] = []
+        try:
+            for sp in params:
+                rows.append(self.pin_guide(sp.guide))
+        except BaseException:
+            for r in rows:
+                self.unpin_guide(r)
+            raise
+        return rows
+
     def submit(self, prompt_ids: List[int], params: SamplingParams) -> Request:
         """Thread-safe: queue one request; the driver loop admits it at the
         next decode-step boundary."""
@@ -474,7 +537,15 @@ class Engine(racecheck.Shared):
         if not self.healthy:
             raise RuntimeError(f"engine unhealthy: {self.last_error}")
         self._validate(prompt_ids, params)
-        req = self.scheduler.submit(prompt_ids, params)
+        if params.guide is None:
+            req = self.scheduler.submit(prompt_ids, params)
+        else:
+            row = self.pin_guide(params.guide)
+            try:
+                req = self.scheduler.submit(prompt_ids, params, row)
+            except BaseException:
+                self.unpin_guide(row)
+                raise
         self._wake.set()
         return req
 
@@ -492,7 +563,7 @@ class Engine(racecheck.Shared):
             raise RuntimeError(f"engine unhealthy: {self.last_error}")
         if microbatches and microbatches != self.M and self.loop_thread is None:
             self.set_groups(microbatches)
-        reqs = self.scheduler.submit_many(prompts, params)
+        reqs = self._submit_many(prompts, params)
         if self.loop_thread is not None:
             return [r.wait() for r in reqs]
         if ph is not None:
@@ -504,6 +575,15 @@ class Engine(racecheck.Shared):
         if ph is not None:
             self._phase("collect", tp)
         return out
+
+    def _submit_many(self, prompts: List[List[int]], params: List[SamplingParams]) -> List[Request]:
+        rows = self._pin_guides(params)
+        try:
+            return self.scheduler.submit_many(prompts, params, rows)
+        except BaseException:
+            for r in rows or ():
+                self.unpin_guide(r)
+            raise
 
     def generate_requests(self, prompts: List[List[int]], params, microbatches: Optional[int] = None,
                           record_timing: bool = False) -> List[Request]:
@@ -518,7 +598,7 @@ class Engine(racecheck.Shared):
             raise RuntimeError(f"engine unhealthy: {self.last_error}")
         if microbatches and microbatches != self.M and self.loop_thread is None:
             self.set_groups(microbatches)
-        reqs = self.scheduler.submit_many(prompts, params)
+        reqs = self._submit_many(prompts, params)
         if self.loop_thread is None:
             with self._lock:
                 self._drive(lambda: all(r.done for r in reqs), timing=record_timing)

@@ -74,6 +74,11 @@ class Chunk:
     # the slot's table
     nbad: int = 0
     bad: Optional[tuple] = None
+    # guide: the row of the last stage's guide table that holds the request's
+    # TokenGuide (the engine put it there before the request was planned), on
+    # every chunk of an asking request; -1 without one (has_guide).  The final
+    # chunk's stage writes (row, state 0) to the slot's entry
+    guide: int = -1
 
     @property
     def qlen(self) -> int:
@@ -108,6 +113,7 @@ class Row:
     ctx: int = 0        # repetition_penalty / no_repeat_ngram_size asked: the group's context gate (has_context)
     allow: int = 0      # allowed_token_ids asked: the group's mask gate (has_allow)
     bad: int = 0        # bad_words asked (then ctx = 1 too): the group's bad-words gate (has_bad)
+    guide: int = 0      # a guide asked: the group's guide gate (has_guide)
 
 
 def has_edits(xs) -> bool:
@@ -140,6 +146,16 @@ def has_bad(xs) -> bool:
     return any(map(operator.attrgetter("nbad" if xs and type(xs[0]) is Chunk else "bad"), xs))
 
 
+def has_guide(xs) -> bool:
+    """Some Row (its flag) / Chunk (its table row, -1 without) follows a guide:
+    the guide's mask runs last ahead of the draw and its step behind it.  A
+    flag of its own like has_edits: the passes read the guide table and the
+    slots' states and add no row vector."""
+    if xs and type(xs[0]) is Chunk:
+        return any(c.guide >= 0 for c in xs)
+    return any(map(operator.attrgetter("guide"), xs))
+
+
 @dataclass
 class GroupPlan:
     g: int                                  # group (microbatch) index
@@ -162,6 +178,8 @@ class GroupPlan:
     allow: Optional[bool] = field(default=None, compare=False, repr=False)
     # has_bad(rows), likewise (never sent)
     bad: Optional[bool] = field(default=None, compare=False, repr=False)
+    # has_guide(rows), likewise (never sent)
+    guide: Optional[bool] = field(default=None, compare=False, repr=False)
 
     @property
     def n_final(self) -> int:
@@ -413,7 +431,22 @@ def _pack_group(gp: GroupPlan, ids: bool, ctx_ids: bool = False):
     if has_bad(gp.chunks) or (gp.rows is not None and has_bad(gp.rows)):
         # one more: 13, behind the mask's place (the context's is taken: an asking request has one)
         out += (None,) * (12 - len(out)) + (_pack_bad(gp),)
+    if has_guide(gp.chunks) or (gp.rows is not None and has_guide(gp.rows)):
+        # one more: 14, every earlier place held by None without its feature
+        out += (None,) * (13 - len(out)) + (_pack_guide(gp),)
     return out
+
+
+def _pack_guide(gp: GroupPlan) -> tuple:
+    """The guides of a group, the last element of its wire tuple: (the rows'
+    guide column or None, the chunks' table rows or None).  Small integers
+    only: the guides' arrays never travel, the engine has written them into
+    the last stage's table."""
+    import numpy as np
+
+    rows = np.array([r.guide for r in gp.rows], dtype=np.int8) if gp.rows is not None else None
+    ch = np.array([c.guide for c in gp.chunks], dtype=np.int16) if gp.chunks else None
+    return rows, ch
 
 
 def _pack_bad(gp: GroupPlan) -> tuple:
@@ -502,7 +535,8 @@ def _unpack_edits(ed) -> tuple:
     return (rows.tolist() if rows is not None else None), n.tolist(), edits
 
 
-def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None, al=None, bw=None) -> GroupPlan:
+def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None, al=None, bw=None,
+                  gd=None) -> GroupPlan:
     """Inverse of _pack_group.  Chunks sent without their token ids carry
     range(len) in their place (their stage reads only the lengths)."""
     gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb, kind=kind, fwd_rows=fwd_rows)
@@ -530,6 +564,12 @@ def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None
                 masks.append(buf[at: at + n] if n >= 0 else None)
                 at += max(n, 0)
             more_c.update(allow=flag.tolist(), mask=masks)
+    if gd is not None:
+        rg, cg = gd
+        if rg is not None:
+            more_r["guide"] = rg.tolist()
+        if cg is not None:
+            more_c["guide"] = cg.tolist()
     if bw is not None:
         rb, cb = bw
         if rb is not None:

@@ -82,6 +82,7 @@ class Request:
     logprobs: Optional[Logprobs] = None  # set before finish() when params.logprobs is not None
     finish_reason: Optional[str] = None  # "length" | "eos" | "stop", once finished without an error
     stop_reason: Optional[int] = None    # the matched stop sequence's index in params.stop_list(), with "stop"
+    guide_row: int = -1  # the row of the last stage's guide table the engine pinned for params.guide (-1: none)
     _flag: bool = False
     _ev: Optional[threading.Event] = None
 
@@ -587,6 +588,7 @@ class _Meta:
     mask: Optional[bytes] = None  # the bytes of SamplingParams.allowed_mask: the allowed list as packed int32 words
     stops: Optional[list] = None  # SamplingParams.stop_list: the stop sequences in the order they are tried
     bad: Optional[tuple] = None  # SamplingParams.bad_word_entries: (exclusive end offsets, tokens back to back)
+    guide: int = -1  # Request.guide_row: the pinned row of the guide table, given back when the KV slot is released
     rep: int = 0        # replica and KV slot, from the request's first prefill chunk
     slot: int = -1
     done: bool = False  # finished by this scheduler (plain flag: the readout loop's hot path)
@@ -623,11 +625,17 @@ class Scheduler(racecheck.Shared):
         self._contexts = 0  # live requests with repetition_penalty / no_repeat_ngram_size, likewise
         self._allowing = 0  # live requests with allowed_token_ids, likewise
         self._badwords = 0  # live requests with bad_words, likewise
+        self._guided = 0  # live requests that follow a guide, likewise
 
     # -- admission ---------------------------------------------------------
-    def submit(self, prompt_ids: List[int], params: SamplingParams) -> Request:
+    def submit(self, prompt_ids: List[int], params: SamplingParams, guide_row: int = -1) -> Request:
+        """guide_row: the guide-table row the engine pinned for params.guide;
+        the pin goes back (Engine.unpin_guide) when the request's KV slot is
+        released, or here when the request never gets one."""
         req = Request(list(map(int, prompt_ids)), params)
+        req.guide_row = guide_row
         if params.max_new_tokens == 0:
+            self.eng.unpin_guide(guide_row)
             req.finish([])
             return req
         rid = next(self._ids)
@@ -641,7 +649,8 @@ class Scheduler(racecheck.Shared):
             raise RuntimeError("scheduler is closed")
         return req
 
-    def submit_many(self, prompts: List[List[int]], params: List[SamplingParams]) -> List[Request]:
+    def submit_many(self, prompts: List[List[int]], params: List[SamplingParams],
+                    guide_rows: Optional[List[int]] = None) -> List[Request]:
         """submit() for a whole batch: one pass under the pending-map lock
         (a 4096-sequence bench session submits everything at once)."""
         now = time.monotonic()
@@ -650,9 +659,14 @@ class Scheduler(racecheck.Shared):
         # 17 ms of a 4096-prompt session); anything else is converted
         reqs = [Request(list(p) if type(p) is list and p and type(p[0]) is int else list(map(int, p)), sp, now)
                 for p, sp in zip(prompts, params)]
+        if guide_rows is not None:  # submit's guide_row, per request
+            for req, row in zip(reqs, guide_rows):
+                req.guide_row = row
         live = []
         for req in reqs:
             if req.params.max_new_tokens == 0:
+                if req.guide_row >= 0:
+                    self.eng.unpin_guide(req.guide_row)
                 req.finish([])
             else:
                 live.append((next(self._ids), req))
@@ -696,6 +710,9 @@ class Scheduler(racecheck.Shared):
             if p.bad_words is not None and p.bad_word_entries() is not None:  # an empty list asks for nothing
                 meta[i].bad = p.bad_word_entries()
                 self._badwords += 1
+            if req.guide_row >= 0:
+                meta[i].guide = req.guide_row
+                self._guided += 1
             if p.stop_token_ids or p.stop_sequences:
                 asking.append((i, p))
             lens.append(len(req.prompt_ids))
@@ -803,11 +820,22 @@ class Scheduler(racecheck.Shared):
                 for r in gp.rows:
                     if meta[r.seq].bad is not None:
                         r.bad = r.ctx = 1
+        if self._guided:
+            # requests that follow a guide: every chunk names the guide's row
+            # of the last stage's table (the final chunk's stage starts the
+            # slot's state there), every row carries the gate
+            for c in gp.chunks:
+                c.guide = meta[c.seq].guide
+            if changed:
+                for r in gp.rows:
+                    if meta[r.seq].guide >= 0:
+                        r.guide = 1
         if changed:
             gp.edit = bool(self._edited) and any(r.nedits for r in gp.rows)
             gp.ctx = bool(self._contexts or self._badwords) and any(r.ctx for r in gp.rows)
             gp.allow = bool(self._allowing) and any(r.allow for r in gp.rows)
             gp.bad = bool(self._badwords) and any(r.bad for r in gp.rows)
+            gp.guide = bool(self._guided) and any(r.guide for r in gp.rows)
         return gp
 
     # -- token readout -----------------------------------------------------------
@@ -898,6 +926,11 @@ class Scheduler(racecheck.Shared):
                     self._allowing -= 1
                 if m is not None and m.bad is not None:
                     self._badwords -= 1
+                if m is not None and m.guide >= 0:
+                    # the last item that held one of its rows has been read back:
+                    # nothing enqueued or in flight reads the guide's row for it
+                    self._guided -= 1
+                    self.eng.unpin_guide(m.guide)
                 if m is not None and flags & EV_FINISH and not m.done:
                     m.done = True
                     self._finish(m, done.get(sid, []))
@@ -946,7 +979,8 @@ class Scheduler(racecheck.Shared):
                 m.done = True
                 m.req.finish(error=err)
         self.meta.clear()
-        self._edited = self._contexts = self._allowing = self._badwords = 0
+        self._edited = self._contexts = self._allowing = self._badwords = self._guided = 0
+        self.eng.unpin_guide(None)
         self.core.reset()
         self.readouts.clear()
         with self._plock:

@@ -17,7 +17,8 @@ Roles (env SHARD_ROLE, `server.py:21`):
 Additions: optional sampling fields on /generate (temperature, top_k, top_p,
 min_p, presence_penalty, frequency_penalty, logprobs, logit_bias, banned_token_ids,
 min_new_tokens, repetition_penalty, no_repeat_ngram_size, allowed_token_ids, bad_words,
-bad_words_ids, stop, stop_token_ids, include_stop_in_output, greedy, seed, stop_at_eos;
+bad_words_ids, stop, stop_token_ids, include_stop_in_output, guided_regex, guided_choice,
+greedy, seed, stop_at_eos;
 defaults = reference sampler; with logprobs the response gains a "logprobs" object
 beside "generated"; with stop / stop_token_ids it gains "finish_reason" and, after
 a stop, "stop_reason"; a stop string is tokenised with the server's tokenizer as
@@ -90,6 +91,46 @@ class GenerateReq(BaseModel):
     stop: Optional[Union[str, List[str]]] = None
     stop_token_ids: Optional[List[int]] = None
     include_stop_in_output: bool = False
+    # guided decoding: the output, as bytes, matches the regular expression as a whole (guide.py
+    # compile_regex's syntax) or is one of the strings; at most one of the two.  Compiled with the
+    # server's tokenizer; EOS is allowed exactly where the match is complete, so set stop_at_eos
+    guided_regex: Optional[str] = None
+    guided_choice: Optional[List[str]] = None
+
+
+class GuideCache:
+    """The guides /generate compiled, least recently used out first: (kind,
+    pattern) -> TokenGuide.  Thread-safe; a guide is compiled outside the lock,
+    so two first requests for one pattern may both compile it (equal guides:
+    the engine interns them to one table row)."""
+
+    def __init__(self, tok, vocab: int, eos: Optional[int], size: int = 32):
+        import collections
+
+        self.tok, self.vocab, self.eos, self.size = tok, vocab, eos, size
+        self._bytes = None
+        self._lru = collections.OrderedDict()
+        self._lock = racecheck.Lock("guide_cache")
+
+    def get(self, kind: str, pattern):
+        from ..guide import compile_choice, compile_regex
+
+        key = (kind, pattern if kind == "regex" else tuple(pattern))
+        with self._lock:
+            g = self._lru.get(key)
+            if g is not None:
+                self._lru.move_to_end(key)
+                return g
+            if self._bytes is None:
+                self._bytes = self.tok.token_bytes(self.vocab)
+            tb = self._bytes
+        g = (compile_regex if kind == "regex" else compile_choice)(pattern, tb, self.eos)
+        with self._lock:
+            self._lru[key] = g
+            self._lru.move_to_end(key)
+            while len(self._lru) > self.size:
+                self._lru.popitem(last=False)
+        return g
 
 
 def logprobs_json(lp) -> dict:
@@ -141,6 +182,7 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
     role = cfg.role
     mc = cfg.model
     tok = load_tokenizer(cfg.model_id, mc.arch, cfg.weights, mc.eos_token_id)
+    guides = GuideCache(tok, mc.vocab_size, mc.eos_token_id)
     metrics = Metrics()
     app = FastAPI(title="llm-sharding-demo (MI355X)")
     app.state.engine, app.state.shard, app.state.metrics = engine, shard, metrics
@@ -205,6 +247,15 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         if req.bad_words is not None or req.bad_words_ids is not None:
             bad = [list(w) for w in req.bad_words_ids or ()] + encode_bad_words(tok, req.bad_words or ())
         stops = encode_stops(tok, req.stop) if req.stop is not None else None
+        guide = None
+        if req.guided_regex is not None and req.guided_choice is not None:
+            raise HTTPException(422, "guided_regex and guided_choice: give one of the two")
+        if req.guided_regex is not None or req.guided_choice is not None:
+            try:
+                guide = (guides.get("regex", req.guided_regex) if req.guided_regex is not None
+                         else guides.get("choice", req.guided_choice))
+            except ValueError as e:
+                raise HTTPException(422, str(e))
         asked_stop = req.stop is not None or req.stop_token_ids is not None
         sp = SamplingParams(temperature=req.temperature, top_k=req.top_k, greedy=req.greedy,
                             seed=req.seed, max_new_tokens=req.max_new_tokens,
@@ -216,7 +267,7 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                             no_repeat_ngram_size=req.no_repeat_ngram_size,
                             allowed_token_ids=req.allowed_token_ids, bad_words=bad,
                             stop_token_ids=req.stop_token_ids, stop_sequences=stops,
-                            include_stop_in_output=req.include_stop_in_output)
+                            include_stop_in_output=req.include_stop_in_output, guide=guide)
         if req.max_new_tokens == 0 and req.logprobs is None:
             return {"generated": tok.decode(ids, skip_special_tokens=True)}
         if not ids:
@@ -228,7 +279,8 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         reason = ("length", None)
         try:
             sp.validate(cfg.max_logprobs, cfg.max_logit_edits, cfg.max_bad_words, cfg.max_bad_word_tokens,
-                        cfg.max_stop_sequences)
+                        cfg.max_stop_sequences, max_guide_classes=cfg.max_guide_classes,
+                        max_guide_cells=cfg.max_guide_cells)
             if req.max_new_tokens == 0:
                 from ..runtime.scheduler import Logprobs
 
@@ -317,7 +369,9 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
     min_new_tokens are applied on the host (ops/reference.py logit_edits; ids
     outside the vocabulary are ignored), allowed_token_ids behind them
     (ops/reference.py allow_mask), bad_words ahead of both over prompt +
-    output (ops/reference.py bad_words); stop_token_ids and stop_sequences end
+    output (ops/reference.py bad_words), a guide last of all, its state in a
+    one-slot table here (ops/reference.py guide_mask / guide_advance);
+    stop_token_ids and stop_sequences end
     the loop by SamplingParams.stop_match (reasons=True: -> (tokens, records,
     (finish_reason, stop_reason))).  records=True: -> (tokens, the logprob
     records of a request that asked for them or None), computed on the host
@@ -349,6 +403,16 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
         ends, toks = sp.bad_word_entries()
         bad = (torch.tensor([len(ends)], dtype=torch.int32), torch.tensor([ends], dtype=torch.int32),
                torch.tensor([toks], dtype=torch.int32))
+    gtab = None
+    if sp.guide is not None:
+        import numpy as np
+
+        g, width = sp.guide, max(cfg.model.vocab_padded, sp.guide.vocab)
+        cls = np.zeros((1, width), dtype=np.int16)
+        cls[0, : g.vocab] = g.cls
+        # one guide row, one slot in the start state
+        gtab = (torch.from_numpy(cls), torch.from_numpy(np.ascontiguousarray(g.next).reshape(1, -1).copy()),
+                torch.tensor([[g.S, g.C]], dtype=torch.int32), torch.zeros(1, 2, dtype=torch.int32))
     stops, reason = sp.stop_list(), ("length", None)
     seq = list(ids)
     url_a = f"http://{cfg.shard_a_service}:{cfg.shard_port}/forward"
@@ -368,10 +432,14 @@ def http_generate(cfg: EngineConfig, ids: List[int], sp: SamplingParams, records
             ref.logit_edits(logits, table, torch.tensor([0]), torch.tensor([step]), vocab)
         if allow is not None:
             ref.allow_mask(logits, allow, torch.tensor([0]), min(vocab, logits.shape[1]))
+        if gtab is not None:
+            ref.guide_mask(logits, gtab, torch.tensor([0]), min(vocab, logits.shape[1]))
         u = counter_uniform(torch.tensor([seed]), torch.tensor([step]))
         nxt = int(ref.sample(logits, torch.tensor([sp.temperature]), torch.tensor([sp.top_k]),
                              torch.tensor([1 if sp.greedy else 0]), u, vocab,
                              torch.tensor([sp.top_p]), torch.tensor([sp.min_p]))[0])
+        if gtab is not None:
+            ref.guide_advance(gtab, torch.tensor([0]), torch.tensor([nxt]), min(vocab, logits.shape[1]))
         seq.append(nxt)
         out.append(nxt)
         if lp is not None:

@@ -56,6 +56,12 @@ class ByteTokenizer:
         parts.append(out.decode("utf-8", errors="replace"))
         return "".join(parts)
 
+    def token_bytes(self, vocab_size: int) -> List[bytes]:
+        """What every id of a vocabulary of `vocab_size` decodes to, for
+        guide.compile_regex: the ids this tokenizer maps to a byte give that
+        byte, every other id b"" (never drawable under a guide)."""
+        return [bytes([self.id_to_byte[i]]) if i in self.id_to_byte else b"" for i in range(vocab_size)]
+
 
 class BPETokenizer:
     name = "bpe"
@@ -81,6 +87,19 @@ class BPETokenizer:
         if skip_special_tokens:
             ids = [i for i in ids if i not in self.special]
         return self.tok.decode(ids, skip_special_tokens=skip_special_tokens)
+
+    def token_bytes(self, vocab_size: int) -> List[bytes]:
+        """What every id of a vocabulary of `vocab_size` decodes to, for
+        guide.compile_regex: get_vocab()'s strings with the bytes-to-unicode
+        stand-ins inverted; special tokens, ids without an entry and strings
+        that are no stand-ins give b"" (never drawable under a guide)."""
+        # the 188 printable bytes stand for themselves, the others for chr(256), chr(257), ...
+        back = {chr(256 + k - 188 if k >= 188 else b): b for k, b in enumerate(bytes_to_unicode_order())}
+        out = [b""] * vocab_size
+        for s, i in self.tok.get_vocab().items():
+            if 0 <= i < vocab_size and i not in self.special and all(ch in back for ch in s):
+                out[i] = bytes(back[ch] for ch in s)
+        return out
 
 
 def encode_stops(tok, stop) -> List[List[int]]:
