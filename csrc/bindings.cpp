@@ -89,6 +89,8 @@ hipError_t lsd_logit_edits(float* logits, long ld, int B, int V, const int* cnt,
                            float* segmax, long ldseg, hipStream_t st);
 hipError_t lsd_allow_mask(float* logits, long ld, int B, int V, const int* on, const int* bits, int W, int nslots,
                           const int* slots, float* segmax, long ldseg, hipStream_t st);
+hipError_t lsd_kv_fork(void* buf, int outer, int slots, int heads, int max_seq, long row_bytes, const int* src,
+                       const int* dst, const int* len, int F, int max_len, hipStream_t st);
 hipError_t lsd_bad_words(float* logits, long ld, int B, int V, const int* cnt, const int* end, int N, const int* btok,
                          int T, const int* plen, const int* ctok, int L, int nslots, const int* slots,
                          const long long* step, float* segmax, long ldseg, hipStream_t st);
@@ -836,6 +838,30 @@ void allow_mask(torch::Tensor logits, int64_t V, torch::Tensor on, torch::Tensor
             "allow_mask");
 }
 
+// Fork a prompt's KV into other slots (kv_fork.hip).  buf: a stage's whole KV
+// allocation [layers, 2, slots, kv_heads, max_seq, head_dim], any dtype; idx:
+// int32 [3 F] on the device, [src F | dst F | len F].  For fork f and every
+// (layer, K|V, head), positions [0, len[f]) of slot src[f] are copied to slot
+// dst[f].  max_len: the longest len of the launch.  That destinations are
+// distinct and never sources is the caller's to check (ops/hip.py kv_fork: it
+// holds the indices on the host).
+void kv_fork(torch::Tensor buf, torch::Tensor idx, int64_t F, int64_t max_len) {
+  TORCH_CHECK(buf.is_cuda() && buf.dim() == 6 && buf.is_contiguous() && buf.size(1) == 2,
+              "kv_fork: buf is a contiguous GPU tensor [layers, 2, slots, kv_heads, max_seq, head_dim]");
+  need(idx, torch::kInt32, "idx");
+  TORCH_CHECK(idx.is_contiguous() && F >= 0 && F <= 65535 && idx.numel() == 3 * F, "kv_fork: idx is int32 [3 F]");
+  TORCH_CHECK(max_len >= 0 && max_len <= buf.size(4), "kv_fork: max_len lies in [0, max_seq]");
+  TORCH_CHECK(buf.size(0) * 2 <= INT32_MAX && buf.size(2) <= INT32_MAX && buf.size(3) <= INT32_MAX &&
+                  buf.size(4) <= INT32_MAX,
+              "kv_fork: a dimension of buf exceeds int32");
+  if (F == 0 || max_len == 0) return;
+  const int* p = idx.data_ptr<int>();
+  check_hip(lsd_kv_fork(buf.data_ptr(), (int)(buf.size(0) * 2), (int)buf.size(2), (int)buf.size(3), (int)buf.size(4),
+                        (long)(buf.size(5) * buf.element_size()), p, p + F, p + 2 * F, (int)F, (int)max_len,
+                        cur_stream()),
+            "kv_fork");
+}
+
 // The layout checks the two guide passes share: gcls [G, Vp] and gnext [G, cells]
 // int16, gdim [G, 2] and gsl [slots, 2] int32, all contiguous.
 void need_guide_table(const torch::Tensor& gcls, const torch::Tensor& gnext, const torch::Tensor& gdim,
@@ -1184,6 +1210,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("until"), py::arg("slots"), py::arg("step") = py::none(), py::arg("segmax") = py::none());
   m.def("allow_mask", &allow_mask, py::arg("logits"), py::arg("V"), py::arg("on"), py::arg("bits"), py::arg("slots"),
         py::arg("segmax") = py::none());
+  m.def("kv_fork", &kv_fork, py::arg("buf"), py::arg("idx"), py::arg("F"), py::arg("max_len"));
   m.def("guide_mask", &guide_mask, py::arg("logits"), py::arg("V"), py::arg("gcls"), py::arg("gnext"), py::arg("gdim"),
         py::arg("gsl"), py::arg("slots"), py::arg("segmax") = py::none());
   m.def("guide_advance", &guide_advance, py::arg("gcls"), py::arg("gnext"), py::arg("gdim"), py::arg("gsl"),

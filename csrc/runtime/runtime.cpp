@@ -109,6 +109,9 @@ PYBIND11_MODULE(_runtime, m) {
            py::arg("wants"), py::arg("stops"))
       .def("set_stops", &SchedCore::set_stops, py::arg("sid"), py::arg("flat_tokens"), py::arg("lengths"),
            py::arg("min_tokens"))
+      .def("add_fork", &SchedCore::add_fork, py::arg("sid"), py::arg("parent"), py::arg("want"),
+           py::arg("stop_at_eos"))
+      .def("forks", [](const SchedCore& c) { return c.forks(); })
       .def("has_work", &SchedCore::has_work)
       .def("plan", [](SchedCore& c, int64_t step) {
              std::vector<int64_t> admitted;

@@ -13,7 +13,9 @@
 //     under the token budget, decode rows, power-of-two row bucket and
 //     256-position context bucket;
 //   * readout assignment: sampled ids -> per-sequence events, EOS stop,
-//     per-request stop sequences, and slot release at a sequence's last item.
+//     per-request stop sequences, and slot release at a sequence's last item;
+//   * families (add_fork): further samples of one prompt, admitted with their
+//     parent and started from a copy of its KV instead of a prefill.
 // The reference has no scheduler at all. Its coordinator runs one request's
 // token loop per HTTP call (`server.py:154-206`); see SURVEY.md §5.2.
 //
@@ -118,6 +120,46 @@ class SchedCore {
     for (size_t i = 0; i < n; ++i) add(sids[i], prompt_lens[i], wants[i], stops[i]);
   }
 
+  // A further sample of `parent`'s prompt (SamplingParams.n): a *fork*.  The
+  // parent must be known and still waiting.  The fork takes its prompt length
+  // and joins its family:
+  //   1. a family is admitted as a unit -- the head of the waiting queue with
+  //      k forks is taken only by a group with room for 1 + k sequences while
+  //      the pool has 1 + k free slots; otherwise admission stops there.  The
+  //      forks sit in the group's prefilling list from then on;
+  //   2. in the step after the one that planned the parent's final chunk every
+  //      fork gets its one chunk (sid, slot, L - 1, 1, final) in the parent's
+  //      group, ahead of the group's other chunks; it counts against the
+  //      prefill budget and is never stopped by it.  forks() names the slot to
+  //      copy positions [0, L - 1) from: the parent's;
+  //   3. the parent keeps its slot past that step: a sequence's slot goes back
+  //      with the read-back of the last item that held its decode row, and
+  //      the parent's first decode row is in the forks' item at the earliest
+  //      (a want = 1 parent included: its first row is issued and discarded).
+  // A prompt of one token has nothing to copy: the fork is a plain add().
+  void add_fork(int64_t sid, int64_t parent, int want, bool stop_at_eos) {
+    auto it = seqs_.find(parent);
+    if (it == seqs_.end()) throw std::invalid_argument("add_fork: unknown parent");
+    if (it->second.slot >= 0 || it->second.g >= 0 || it->second.parent >= 0)
+      throw std::invalid_argument("add_fork: the parent is admitted already, or is a fork itself");
+    if (seqs_.count(sid)) throw std::invalid_argument("add_fork: the sequence exists already");
+    const int L = it->second.prompt_len;
+    if (L == 1) {
+      add(sid, 1, want, stop_at_eos);
+      return;
+    }
+    Seq s;
+    s.prompt_len = L;
+    s.want = want;
+    s.stop_at_eos = stop_at_eos;
+    s.parent = parent;
+    seqs_[sid] = s;
+    seqs_.at(parent).forks.push_back(sid);
+  }
+
+  // (fork sid, source slot) of the fork chunks of the last plan(), in plan order
+  const std::vector<std::pair<int64_t, int>>& forks() const { return forks_; }
+
   // Stop sequences of a sequence that was added and has no token yet:
   // lengths[e] tokens of flat_tokens each, tried in this order.  After its
   // j-th generated token is read back (the prefill draw is token 1) a stop
@@ -159,6 +201,7 @@ class SchedCore {
   // that joined at this step.
   std::vector<std::vector<GroupOut>> plan(int64_t step, std::vector<int64_t>* admitted) {
     std::vector<std::vector<GroupOut>> out(R_);
+    forks_.clear();
     for (int rep = 0; rep < R_; ++rep)
       for (int g = 0; g < M_; ++g) {
         GroupOut go;
@@ -219,6 +262,7 @@ class SchedCore {
     waiting_.clear();
     expect_.clear();
     produced_.clear();
+    forks_.clear();
     groups_.assign(R_, std::vector<Group>(M_));
   }
 
@@ -258,6 +302,13 @@ class SchedCore {
     bool stop_at_eos = false, stop = false, finished = false;
     std::vector<int> toks;  // assign_collect only
     std::shared_ptr<Stops> stops;  // null without stop sequences
+    // families: a fork's parent (-1: none) and the slot its KV is copied from;
+    // ready once the parent's final chunk has been planned.  forks: the fork ids
+    // of a parent whose final chunk is not planned yet, cleared when it is
+    int64_t parent = -1;
+    int src_slot = -1;
+    bool ready = false;
+    std::vector<int64_t> forks;
   };
   struct Produced {
     int b = 0;
@@ -301,15 +352,27 @@ class SchedCore {
     std::vector<int64_t> out;
     while (!waiting_.empty() && room > 0 && pool->available() > 0) {
       const int64_t sid = waiting_.front();
-      waiting_.pop_front();
       Seq& s = seqs_.at(sid);
+      const int k = (int)s.forks.size();
+      if (room < 1 + k || pool->available() < 1 + k) break;  // a family is admitted as a unit
+      waiting_.pop_front();
       s.rep = rep;
       s.g = g;
       s.slot = pool->alloc(1)[0];
       out.push_back(sid);
       if (admitted) admitted->push_back(sid);
-      --room;
-      ++joins_;
+      for (int64_t fid : s.forks) {
+        Seq& f = seqs_.at(fid);
+        f.rep = rep;
+        f.g = g;
+        f.slot = pool->alloc(1)[0];
+        f.src_slot = s.slot;
+        f.prefilled = f.prompt_len - 1;
+        out.push_back(fid);
+        if (admitted) admitted->push_back(fid);
+      }
+      room -= 1 + k;
+      joins_ += 1 + k;
     }
     return out;
   }
@@ -367,8 +430,25 @@ class SchedCore {
     int64_t budget = budget_ > 0 ? budget_ : (int64_t(1) << 62);
     std::vector<int64_t> finals;
     const std::vector<int64_t> pf = gh.prefilling;
+    // forks whose parent's final chunk was planned in the previous step: one
+    // token each, ahead of every other chunk, whatever the budget has left
     for (int64_t sid : pf) {
       Seq& s = seqs_.at(sid);
+      if (s.parent < 0 || !s.ready) continue;
+      const int L = s.prompt_len;
+      budget -= 1;
+      chunks.emplace_back(sid, s.slot, L - 1, 1, true);
+      forks_.emplace_back(sid, s.src_slot);
+      s.prefilled = L;
+      gh.prefilling.erase(std::find(gh.prefilling.begin(), gh.prefilling.end(), sid));
+      finals.push_back(sid);
+      s.issued = 1;
+      s.pos = L;
+      s.sstep = 1;
+    }
+    for (int64_t sid : pf) {
+      Seq& s = seqs_.at(sid);
+      if (s.parent >= 0) continue;  // a fork: planned above, or waiting for its parent's final chunk
       const int L = s.prompt_len;
       const int take = chunk_ <= 0 ? L - s.prefilled : std::min(chunk_, L - s.prefilled);
       if (!chunks.empty() && take > budget) break;
@@ -383,6 +463,8 @@ class SchedCore {
         s.issued = 1;
         s.pos = L;
         s.sstep = 1;
+        for (int64_t fid : s.forks) seqs_.at(fid).ready = true;  // their chunks: the next step
+        s.forks.clear();
       }
     }
     // decode rows
@@ -524,6 +606,7 @@ class SchedCore {
   int64_t next_id_ = 0, joins_ = 0, leaves_ = 0, steps_ = 0, deferred_ = 0;
   int join_min_ = 1, max_wait_ = 0;
   int max_rows_ = 0;
+  std::vector<std::pair<int64_t, int>> forks_;
 };
 
 }  // namespace lsd_rt

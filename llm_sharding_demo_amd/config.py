@@ -174,6 +174,7 @@ def model_config_from_hf_json(path: str) -> ModelConfig:
 # Sampling
 # ---------------------------------------------------------------------------
 
+MAX_SAMPLES_CEILING = 64  # samples of one request (SamplingParams.n): one family, admitted as a unit
 MAX_LOGPROBS_CEILING = 20  # alternatives per token the logprob kernel's record can hold
 MAX_LOGIT_EDITS_CEILING = 1024  # entries per request the logit-edit kernel's 256 threads visit in 4 trips
 MAX_BAD_WORDS_CEILING = 256  # sequences per request: one thread of the bad_words kernel's workgroup each
@@ -405,6 +406,13 @@ class SamplingParams:
     stop_sequences: Optional[Sequence[Sequence[int]]] = None
     include_stop_in_output: bool = False
     guide: Optional["TokenGuide"] = None
+    # n samples of the prompt, each a sequence of its own: sample i draws with
+    # seed + i (of the one random seed the scheduler draws when seed is None)
+    # and every other field applies to each sample independently.  The prompt
+    # is prefilled once; samples 1 .. n - 1 start from a copy of its KV
+    # (csrc/kernels/kv_fork.hip).  At most EngineConfig.max_samples, the
+    # microbatch capacity and the KV slot count.  greedy gives n equal samples
+    n: int = 1
 
     @property
     def has_stops(self) -> bool:
@@ -527,6 +535,8 @@ class SamplingParams:
                  max_guide_classes: int = 1024, max_guide_cells: int = 1 << 18) -> None:
         if self.max_new_tokens < 0:
             raise ValueError("max_new_tokens must be >= 0")
+        if isinstance(self.n, bool) or not isinstance(self.n, int) or self.n < 1:
+            raise ValueError("n must be an integer >= 1")
         m = self.min_new_tokens
         if isinstance(m, bool) or not isinstance(m, int) or not (0 <= m <= self.max_new_tokens):
             raise ValueError("min_new_tokens must be an integer in [0, max_new_tokens]")
@@ -733,8 +743,14 @@ class EngineConfig:
     max_guides: int = 8
     max_guide_classes: int = 1024
     max_guide_cells: int = 1 << 18
+    # Most samples one request may ask for (SamplingParams.n); a request's
+    # samples are admitted together, so n is also bounded by the microbatch
+    # capacity and the KV slot count.  At most 64.
+    max_samples: int = 8
 
     def __post_init__(self):
+        if not (1 <= self.max_samples <= MAX_SAMPLES_CEILING):
+            raise ValueError(f"max_samples must be in [1, {MAX_SAMPLES_CEILING}]")
         if not (1 <= self.max_guides <= MAX_GUIDES_CEILING):
             raise ValueError(f"max_guides must be in [1, {MAX_GUIDES_CEILING}]")
         if not (1 <= self.max_guide_classes <= MAX_GUIDE_CLASSES_CEILING):
@@ -792,6 +808,7 @@ class EngineConfig:
             max_guides=int(_env("MAX_GUIDES", "8")),
             max_guide_classes=int(_env("MAX_GUIDE_CLASSES", "1024")),
             max_guide_cells=int(_env("MAX_GUIDE_CELLS", str(1 << 18))),
+            max_samples=int(_env("MAX_SAMPLES", "8")),
         )
         if cfg.split_points and cfg.num_stages == 1:
             cfg.num_stages = len(cfg.split_points) + 1

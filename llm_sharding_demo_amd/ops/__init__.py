@@ -175,6 +175,13 @@ class ReferenceBackend(Backend):
         W = rec[1].shape[2]
         ref.record_logprobs(rec, slots, step, nlp, *ref.logprobs(logits, tokens, nlp, vocab, W), active, back)
 
+    def kv_fork(self, buf, src, dst, lens, idx=None) -> None:
+        """Fork prompts' KV (SamplingParams.n): positions [0, lens[f]) of slot
+        src[f] of a stage's whole KV allocation go to slot dst[f], for every
+        layer, K and V, and head.  src, dst, lens: host integers; idx: the
+        same on the device (the HIP backend's kernel reads them there)."""
+        ref.kv_fork(buf, src, dst, lens)
+
     def gather_rows(self, x, idx):
         return x.index_select(0, idx.long())
 

@@ -22,6 +22,7 @@ from typing import Optional
 import torch
 
 from . import Backend, Residual
+from . import reference as ref
 from .routing import Routing
 
 _C = None
@@ -422,6 +423,19 @@ class HipBackend(Backend):
     def guide_advance(self, table, slots, tokens, vocab: int, active=None) -> None:
         # guide.hip: one thread per row, behind the draw
         self.C.guide_advance(*table, vocab, slots, tokens, active)
+
+    def kv_fork(self, buf, src, dst, lens, idx=None) -> None:
+        # kv_fork.hip: one launch for every fork, layer, K|V and head; 16 bytes
+        # per lane per access.  The indices are checked here, on the host; idx
+        # is [src F | dst F | len F] on the device (the worker's pinned staging
+        # ring brings it), made here when a caller has none
+        src, dst, lens = ref.check_forks(buf, src, dst, lens)
+        F = len(src)
+        if F == 0 or max(lens) == 0:
+            return
+        if idx is None:
+            idx = torch.tensor(src + dst + lens, dtype=torch.int32, device=buf.device)
+        self.C.kv_fork(buf, idx, F, max(lens))
 
     def record_tokens(self, hist, slots, step, tokens, active=None, back: int = 0) -> None:
         self.C.record_tokens(hist, slots, step, tokens, active, back)

@@ -601,3 +601,33 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
         j = int(torch.searchsorted(c, torch.tensor([u], dtype=c.dtype)).clamp(max=k - 1))
         out[r] = int(idx[j])
     return out
+
+
+def check_forks(buf: torch.Tensor, src, dst, lens) -> tuple:
+    """The host-side contract of kv_fork, for both backends: buf is a stage's
+    whole KV allocation [layers, 2, slots, kv_heads, max_seq, head_dim]; src,
+    dst and lens hold one entry per fork; slots lie in [0, slots) and lengths in
+    [0, max_seq]; destinations are distinct and no destination is a source (a
+    source may repeat).  -> (src, dst, lens) as lists of ints."""
+    src, dst, lens = [int(s) for s in src], [int(d) for d in dst], [int(n) for n in lens]
+    if buf.dim() != 6 or buf.shape[1] != 2 or not buf.is_contiguous():
+        raise ValueError("kv_fork: buf is a contiguous [layers, 2, slots, kv_heads, max_seq, head_dim]")
+    if not len(src) == len(dst) == len(lens):
+        raise ValueError("kv_fork: src, dst and lens hold one entry per fork")
+    S, L = buf.shape[2], buf.shape[4]
+    if any(not 0 <= s < S for s in src + dst) or any(not 0 <= n <= L for n in lens):
+        raise ValueError(f"kv_fork: a slot lies outside [0, {S}) or a length outside [0, {L}]")
+    if len(set(dst)) != len(dst) or set(dst) & set(src):
+        raise ValueError("kv_fork: destinations must be distinct and must not be sources")
+    return src, dst, lens
+
+
+def kv_fork(buf: torch.Tensor, src, dst, lens) -> None:
+    """Fork prompts' KV: for fork f and every (layer, K|V, head), positions
+    [0, lens[f]) of slot src[f] are copied to slot dst[f] of buf [layers, 2,
+    slots, kv_heads, max_seq, head_dim].  Nothing else is written.  The twin
+    of csrc/kernels/kv_fork.hip: what the CPU engine runs and what the GPU
+    tests compare the kernel with, bit for bit."""
+    for s, d, n in zip(*check_forks(buf, src, dst, lens)):
+        if n:
+            buf[:, :, d, :, :n] = buf[:, :, s, :, :n]

@@ -285,9 +285,10 @@ class DrawStage(racecheck.Shared):
         """Prefill chunks are about to run on the last stage (every prefill
         item, eager or replayed; never inside a capture).  Nothing while no
         context table exists and no chunk asks for one.  Once it exists every
-        chunk that opens a prompt writes its slot's (plen, rpen, ngram), the
-        defaults included -- a request that reuses a slot must not inherit its
-        predecessor's -- and every chunk that asks writes its token ids to
+        chunk that opens a prompt (start == 0, or a fork's chunk: Chunk.opens)
+        writes its slot's (plen, rpen, ngram), the defaults included -- a
+        request that reuses a slot must not inherit its predecessor's -- and
+        every chunk that asks writes its token ids to
         tok[slot, start : start + qlen].  ONE host-to-device copy through the
         group's pinned staging ring: [slots H | plen H | rpen bits H | ngram H]
         of the H opening chunks, then [flat table index T | ids T]."""
@@ -295,10 +296,19 @@ class DrawStage(racecheck.Shared):
         if self.ctx_tab is None and not flagged:
             return
         plen, rpen, ngram, tok = self._ctx_tab()
-        heads = [c for c in chunks if c.start == 0]
+        heads = [c for c in chunks if c.opens]
         if not heads and not flagged:
             return
         L = tok.shape[1]
+        for c in flagged:
+            # a fork's chunk (SamplingParams.n): the prompt's ids [0, start) are
+            # the source slot's, cloned on the device -- the source's own chunks
+            # wrote them on this lane, in an earlier item -- and the chunk's own
+            # id lands behind them below
+            if c.fork >= 0 and c.start > 0:
+                if not (0 <= c.fork < self.slots and 0 <= c.slot < self.slots and c.start < L):
+                    raise ValueError("a fork chunk's slots or start lie outside the context table")
+                tok[c.slot, : c.start].copy_(tok[c.fork, : c.start])
         for c in flagged:
             if isinstance(c.ids, range) or c.start + c.qlen > L or not 0 <= c.slot < self.slots:
                 raise ValueError("a prefill chunk with repetition_penalty / no_repeat_ngram_size reached the last "

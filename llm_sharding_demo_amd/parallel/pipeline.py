@@ -44,7 +44,7 @@ import torch
 from ..models.stage import StageModel
 from ..runtime.batch import BatchMeta, MixedMeta
 from ..runtime.plan import (NO_FEATURES, ROW_FIELDS, GroupPlan, StepPlan, device_fields, has_allow, has_bad,
-                            has_context, has_edits, has_guide, pack_rows, packed_size, row_features)
+                            has_context, has_edits, has_fork, has_guide, pack_rows, packed_size, row_features)
 from ..utils.tracing import trace_range
 from ..utils import racecheck
 from .comm import Handle, SendHandle, Transport
@@ -439,6 +439,7 @@ class StageWorker(racecheck.Shared):
         self.native_changes = 0  # composition-change items issued by exec_items
         self.mixed_items = 0     # decode + prefill items run as one forward (_mixed)
         self.io_items = 0  # decode items whose (graph) body carried its own transfers
+        self.kv_fork_launches = 0  # items that copied a parent's KV into its forks' slots (_fork_kv)
         # what runs on the last stage's logits, its per-KV-slot tables and
         # launch counters (parallel/draw.py); allocates nothing until asked
         self.draw = DrawStage(stage, max(scratch_slot, compat_slot) + 1, self._stage_h2d, self._gpu)
@@ -578,8 +579,10 @@ class StageWorker(racecheck.Shared):
         if not (getattr(self, "merge_prefill", self.MERGE_PREFILL) and self.P == 1 and len(items) > 1
                 and self.device.type == "cuda"):
             return items
+        # an item with fork chunks stays on its own group's lane: the stream
+        # that ordered its KV copy behind the parent's prefill
         pure = [gp for gp in items if gp.kind != "fwd_b" and gp.chunks and gp.b == 0 and gp.rows is None
-                and gp.ret == 0]
+                and gp.ret == 0 and not has_fork(gp.chunks)]
         if len(pure) < 2:
             return items
         rest = [gp for gp in items if not any(gp is q for q in pure)]
@@ -872,6 +875,8 @@ class StageWorker(racecheck.Shared):
         # --- composition change: rewrite the decode rows' state
         if gp.rows is not None:
             self._apply_rows(gp, gs)
+        if gp.chunks and has_fork(gp.chunks):
+            self._fork_kv(gs, gp.chunks)
         if gp.chunks and gp.b > 0 and self._mixed_ok(gp):
             self._mixed(gp, gs)
             return
@@ -908,6 +913,29 @@ class StageWorker(racecheck.Shared):
         else:
             for x in sends:
                 self.send_pending.setdefault(gp.g, []).append(self._send(x, self.r + 1, "fwd", lane))
+
+    def _fork_kv(self, gs: GroupState, chunks) -> None:
+        """The item's fork chunks (SamplingParams.n): copy positions [0,
+        start) of each one's source slot into its own slot, for every layer
+        whose KV this stage holds -- ONE kv_fork launch on the item's lane,
+        ahead of its forward (eager, prefill-graph replay or mixed), never
+        inside a capture.  The parent's prefill ran on this lane in an earlier
+        item, or a merged prefill that this lane waited for.  The three index
+        vectors travel as one copy through the group's pinned staging ring.
+        A stage that holds no KV skips the call."""
+        kv = self.stage.kv
+        if kv.n_layers == 0:
+            return
+        fk = [c for c in chunks if c.fork >= 0 and c.start > 0]
+        if not fk:
+            return
+        src, dst, lens = [c.fork for c in fk], [c.slot for c in fk], [c.start for c in fk]
+        idx = None
+        if self.device.type == "cuda":
+            idx = torch.empty(3 * len(fk), dtype=torch.int32, device=self.device)
+            self._stage_h2d(gs, np.asarray(src + dst + lens, dtype=np.int32), idx)
+        self.stage.backend.kv_fork(kv.buf, src, dst, lens, idx)
+        self.kv_fork_launches += 1
 
     # Mixed steps (one stage): a group whose step both decodes rows and
     # prefills joining prompts runs ONE eager forward over [decode rows |

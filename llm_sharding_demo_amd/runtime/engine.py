@@ -379,6 +379,13 @@ class Engine(racecheck.Shared):
         sp.validate(self.cfg.max_logprobs, self.cfg.max_logit_edits, self.cfg.max_bad_words,
                     self.cfg.max_bad_word_tokens, self.cfg.max_stop_sequences,
                     max_guide_classes=self.cfg.max_guide_classes, max_guide_cells=self.cfg.max_guide_cells)
+        if sp.n > 1:
+            # a request's samples are admitted together, into one group
+            top = min(self.cfg.max_samples, self.group_cap, self.kv_slots)
+            if sp.n > top:
+                raise ValueError(f"n = {sp.n} exceeds the {top} samples one request may have: max_samples = "
+                                 f"{self.cfg.max_samples}, {self.group_cap} rows per microbatch group, "
+                                 f"{self.kv_slots} KV slots")
         if sp.guide is not None:
             g = sp.guide
             if g.vocab != self.mcfg.vocab_size:
@@ -520,11 +527,15 @@ class Engine(racecheck.Shared):
         if not any(sp.guide is not None for sp in params):
             return None
         rows: List[int] = []
+        extra: List[int] = []
         try:
             for sp in params:
                 rows.append(self.pin_guide(sp.guide))
+                if sp.guide is not None:
+                    for _ in range(sp.n - 1):  # one pin per sample: each gives its own back
+                        extra.append(self.pin_guide(sp.guide))
         except BaseException:
-            for r in rows:
+            for r in rows + extra:
                 self.unpin_guide(r)
             raise
         return rows
@@ -541,10 +552,15 @@ class Engine(racecheck.Shared):
             req = self.scheduler.submit(prompt_ids, params)
         else:
             row = self.pin_guide(params.guide)
+            pins = 1
             try:
+                for _ in range(params.n - 1):  # one pin per sample: each gives its own back
+                    self.pin_guide(params.guide)
+                    pins += 1
                 req = self.scheduler.submit(prompt_ids, params, row)
             except BaseException:
-                self.unpin_guide(row)
+                for _ in range(pins):
+                    self.unpin_guide(row)
                 raise
         self._wake.set()
         return req
@@ -557,6 +573,9 @@ class Engine(racecheck.Shared):
         tp = time.monotonic() if ph is not None else 0.0
         if isinstance(params, SamplingParams):
             params = [params] * len(prompts)
+        if any(sp.n > 1 for sp in params):
+            raise ValueError("generate_ids returns one token list per prompt: a request with n > 1 goes through "
+                             "generate_samples (or generate_requests, whose Request.samples holds every sample)")
         for p, sp in zip(prompts, params):
             self._validate(p, sp)
         if not self.healthy:
@@ -581,8 +600,9 @@ class Engine(racecheck.Shared):
         try:
             return self.scheduler.submit_many(prompts, params, rows)
         except BaseException:
-            for r in rows or ():
-                self.unpin_guide(r)
+            for r, sp in zip(rows or (), params):
+                for _ in range(sp.n):
+                    self.unpin_guide(r)
             raise
 
     def generate_requests(self, prompts: List[List[int]], params, microbatches: Optional[int] = None,
@@ -598,6 +618,9 @@ class Engine(racecheck.Shared):
             raise RuntimeError(f"engine unhealthy: {self.last_error}")
         if microbatches and microbatches != self.M and self.loop_thread is None:
             self.set_groups(microbatches)
+            for p, sp in zip(prompts, params):
+                if sp.n > 1:  # the groups' capacity has changed: a family must still fit one
+                    self._validate(p, sp)
         reqs = self._submit_many(prompts, params)
         if self.loop_thread is None:
             with self._lock:
@@ -605,6 +628,15 @@ class Engine(racecheck.Shared):
         for r in reqs:
             r.wait(None if self.loop_thread is not None else 0)
         return reqs
+
+    def generate_samples(self, prompts: List[List[int]], params, microbatches: Optional[int] = None,
+                         record_timing: bool = False) -> List[List[List[int]]]:
+        """The generated ids of every sample of every prompt: out[i][k] is
+        sample k of prompt i, params.n of them (SamplingParams.n).  Each
+        prompt is prefilled once; samples 1 .. n - 1 start from a copy of its
+        KV and draw with seed + k."""
+        reqs = self.generate_requests(prompts, params, microbatches, record_timing)
+        return [[s.wait(0) for s in r.samples] for r in reqs]
 
     def fetch_logprobs(self, replica: int, slot: int, n: int) -> tuple:
         """Logprob records [0, n) of KV slot `slot` from the replica's last

@@ -79,6 +79,17 @@ class Chunk:
     # every chunk of an asking request; -1 without one (has_guide).  The final
     # chunk's stage writes (row, state 0) to the slot's entry
     guide: int = -1
+    # fork (SamplingParams.n): the KV slot whose positions [0, start) every
+    # stage copies into `slot` ahead of this chunk (csrc/kernels/kv_fork.hip),
+    # -1 for an ordinary chunk.  A fork's chunk is its prompt's last token
+    # (start = L - 1, final): it *opens* the prompt on its slot as a start == 0
+    # chunk does, without prefilling it
+    fork: int = -1
+
+    @property
+    def opens(self) -> bool:
+        """The first chunk its slot sees of a prompt."""
+        return self.start == 0 or self.fork >= 0
 
     @property
     def qlen(self) -> int:
@@ -401,6 +412,11 @@ def _unpack_cols(cls, ints_names: tuple, ints, floats, **more) -> list:
                                              for nm, d in _DEFAULTS[cls]))))
 
 
+def has_fork(xs) -> bool:
+    """Some Chunk starts from a copy of another slot's KV (Chunk.fork)."""
+    return any(c.fork >= 0 for c in xs)
+
+
 def _pack_group(gp: GroupPlan, ids: bool, ctx_ids: bool = False):
     """ctx_ids: the destination runs a last stage, which copies the prompt ids
     of chunks that ask for a context into its table -- a group with such a
@@ -434,6 +450,11 @@ def _pack_group(gp: GroupPlan, ids: bool, ctx_ids: bool = False):
     if has_guide(gp.chunks) or (gp.rows is not None and has_guide(gp.rows)):
         # one more: 14, every earlier place held by None without its feature
         out += (None,) * (13 - len(out)) + (_pack_guide(gp),)
+    if has_fork(gp.chunks):
+        # one more: 15, the chunks' source slots; a plan without a fork encodes as before
+        import numpy as np
+
+        out += (None,) * (14 - len(out)) + (np.array([c.fork for c in gp.chunks], dtype=np.int32),)
     return out
 
 
@@ -536,7 +557,7 @@ def _unpack_edits(ed) -> tuple:
 
 
 def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None, al=None, bw=None,
-                  gd=None) -> GroupPlan:
+                  gd=None, fk=None) -> GroupPlan:
     """Inverse of _pack_group.  Chunks sent without their token ids carry
     range(len) in their place (their stage reads only the lengths)."""
     gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb, kind=kind, fwd_rows=fwd_rows)
@@ -570,6 +591,8 @@ def _unpack_group(g, ret, n, b, ctxb, kind, fwd_rows, ch, rows, ed=None, cx=None
             more_r["guide"] = rg.tolist()
         if cg is not None:
             more_c["guide"] = cg.tolist()
+    if fk is not None:
+        more_c["fork"] = fk.tolist()
     if bw is not None:
         rb, cb = bw
         if rb is not None:

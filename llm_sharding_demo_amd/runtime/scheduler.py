@@ -85,8 +85,31 @@ class Request:
     guide_row: int = -1  # the row of the last stage's guide table the engine pinned for params.guide (-1: none)
     _flag: bool = False
     _ev: Optional[threading.Event] = None
+    # params.n > 1: the n samples in sample order, this request (sample 0) first;
+    # each has its own output, logprobs and finish reason
+    _samples: Optional[List["Request"]] = None
+
+    @property
+    def samples(self) -> List["Request"]:
+        """The request's params.n samples in sample order; sample 0 is the
+        request itself (`output` is sample 0's)."""
+        return self._samples if self._samples is not None else [self]
+
+    def fork_samples(self) -> None:
+        """Make the n - 1 further samples of a request with params.n > 1."""
+        n = self.params.n
+        if n > 1 and self._samples is None:
+            self._samples = [self] + [Request(self.prompt_ids, self.params, self.t_submit) for _ in range(n - 1)]
 
     def wait(self, timeout: Optional[float] = None) -> List[int]:
+        """Sample 0's tokens, once every sample has finished; `timeout`
+        bounds the whole wait, not each sample's."""
+        if self._samples is not None:
+            end = None if timeout is None else time.monotonic() + timeout
+            for s in self._samples[1:]:
+                s.wait(None if end is None else max(0.0, end - time.monotonic()))
+            if end is not None:
+                timeout = max(0.0, end - time.monotonic())
         if not self._flag:
             with _FINISH:
                 if not self._flag and self._ev is None:
@@ -100,9 +123,17 @@ class Request:
 
     @property
     def done(self) -> bool:
+        """Finished, every sample of it."""
+        if self._samples is not None:
+            return self._flag and all(s._flag for s in self._samples[1:])
         return self._flag
 
     def finish(self, output=None, error=None) -> None:
+        if self._samples is not None:
+            for s in self._samples[1:]:
+                # an error fails every sample; a request without tokens to draw has none anywhere
+                if not s._flag and (error is not None or self.params.max_new_tokens == 0):
+                    s.finish(output=None if error is not None else [], error=error)
         self.output, self.error = output, error
         if error is None and self.finish_reason is None:
             self.finish_reason = "length"
@@ -252,6 +283,14 @@ class _Seq:
     # tokens they are matched against; None / unused without stop sequences
     stops: Optional[tuple] = None
     tail: Optional[List[int]] = None
+    # families (add_fork): a fork's parent (-1: none) and the slot its KV is
+    # copied from; ready once the parent's final chunk has been planned.
+    # forks: the fork ids of a parent whose final chunk is not planned yet,
+    # cleared when it is
+    parent: int = -1
+    src_slot: int = -1
+    ready: bool = False
+    forks: List[int] = field(default_factory=list)
 
 
 @dataclass
@@ -298,6 +337,31 @@ class PySchedCore:
         self.expect: Dict[tuple, _Produced] = {}
         self.joins = self.leaves = self.max_rows = self.steps = 0
         self.join_min, self.max_wait, self.deferred = 1, 0, 0
+        self._forks: List[tuple] = []
+
+    def add_fork(self, sid: int, parent: int, want: int, stop_at_eos: bool) -> None:
+        """lsd_rt::SchedCore::add_fork: a further sample of `parent`'s prompt.
+        The parent must be known and still waiting; the fork takes its prompt
+        length, is admitted with it (the family as a unit) and gets its one
+        chunk (sid, slot, L - 1, 1, final) in the parent's group in the step
+        after the parent's final chunk, ahead of the group's other chunks.  A
+        prompt of one token has nothing to copy: a plain add()."""
+        p = self.seqs.get(parent)
+        if p is None:
+            raise ValueError("add_fork: unknown parent")
+        if p.slot >= 0 or p.g >= 0 or p.parent >= 0:
+            raise ValueError("add_fork: the parent is admitted already, or is a fork itself")
+        if sid in self.seqs:
+            raise ValueError("add_fork: the sequence exists already")
+        if p.prompt_len == 1:
+            self.add(sid, 1, want, stop_at_eos)
+            return
+        self.seqs[sid] = _Seq(p.prompt_len, want, stop_at_eos, parent=parent)
+        p.forks.append(sid)
+
+    def forks(self) -> List[tuple]:
+        """(fork sid, source slot) of the fork chunks of the last plan(), in plan order."""
+        return list(self._forks)
 
     def set_join_policy(self, join_min: int, max_wait: int) -> None:
         """lsd_rt::SchedCore::set_join_policy: admit only with room for every
@@ -386,6 +450,7 @@ class PySchedCore:
     def plan(self, step: int):
         admitted: List[int] = []
         out = []
+        self._forks = []
         for rep in range(self.R):
             gs = []
             for g in range(self.M):
@@ -400,14 +465,25 @@ class PySchedCore:
         pool = self.pools[rep]
         out = []
         while self.waiting and room > 0 and pool.available > 0:
-            sid = self.waiting.popleft()
+            sid = self.waiting[0]
             s = self.seqs[sid]
+            k = len(s.forks)
+            if room < 1 + k or pool.available < 1 + k:
+                break  # a family is admitted as a unit
+            self.waiting.popleft()
             s.rep, s.g = rep, g
             s.slot = pool.alloc(1)[0]
             out.append(sid)
             admitted.append(sid)
-            room -= 1
-            self.joins += 1
+            for fid in s.forks:
+                f = self.seqs[fid]
+                f.rep, f.g = rep, g
+                f.slot = pool.alloc(1)[0]
+                f.src_slot, f.prefilled = s.slot, f.prompt_len - 1
+                out.append(fid)
+                admitted.append(fid)
+            room -= 1 + k
+            self.joins += 1 + k
         return out
 
     def _group_plan(self, rep: int, g: int, step: int, admitted: List[int]):
@@ -433,8 +509,25 @@ class PySchedCore:
         # prefill chunks (FIFO, one chunk per sequence per step, token budget)
         budget = self.budget or (1 << 62)
         chunks, finals = [], []
-        for sid in list(gh.prefilling):
+        pf = list(gh.prefilling)
+        # forks whose parent's final chunk was planned in the previous step: one
+        # token each, ahead of every other chunk, whatever the budget has left
+        for sid in pf:
             s = self.seqs[sid]
+            if s.parent < 0 or not s.ready:
+                continue
+            L = s.prompt_len
+            budget -= 1
+            chunks.append((sid, s.slot, L - 1, 1, True))
+            self._forks.append((sid, s.src_slot))
+            s.prefilled = L
+            gh.prefilling.remove(sid)
+            finals.append(sid)
+            s.issued, s.pos, s.sstep = 1, L, 1
+        for sid in pf:
+            s = self.seqs[sid]
+            if s.parent >= 0:
+                continue  # a fork: planned above, or waiting for its parent's final chunk
             L = s.prompt_len
             n = L - s.prefilled if self.chunk <= 0 else min(self.chunk, L - s.prefilled)
             if chunks and n > budget:
@@ -448,6 +541,9 @@ class PySchedCore:
                 gh.prefilling.remove(sid)
                 finals.append(sid)
                 s.issued, s.pos, s.sstep = 1, L, 1
+                for fid in s.forks:  # their chunks: the next step
+                    self.seqs[fid].ready = True
+                s.forks = []
         # decode rows
         n = len(new_rows)
         b = _bucket(n, self.cap)
@@ -558,6 +654,7 @@ class PySchedCore:
         self.seqs.clear()
         self.waiting.clear()
         self.expect.clear()
+        self._forks = []
         self.groups = [[_Group() for _ in range(self.M)] for _ in range(self.R)]
 
 
@@ -626,6 +723,7 @@ class Scheduler(racecheck.Shared):
         self._allowing = 0  # live requests with allowed_token_ids, likewise
         self._badwords = 0  # live requests with bad_words, likewise
         self._guided = 0  # live requests that follow a guide, likewise
+        self._forking = 0  # forks whose chunk is not planned yet: build_step asks the core for forks() only then
 
     # -- admission ---------------------------------------------------------
     def submit(self, prompt_ids: List[int], params: SamplingParams, guide_row: int = -1) -> Request:
@@ -634,8 +732,10 @@ class Scheduler(racecheck.Shared):
         released, or here when the request never gets one."""
         req = Request(list(map(int, prompt_ids)), params)
         req.guide_row = guide_row
+        req.fork_samples()
         if params.max_new_tokens == 0:
-            self.eng.unpin_guide(guide_row)
+            for _ in range(params.n):  # one pin per sample
+                self.eng.unpin_guide(guide_row)
             req.finish([])
             return req
         rid = next(self._ids)
@@ -664,9 +764,12 @@ class Scheduler(racecheck.Shared):
                 req.guide_row = row
         live = []
         for req in reqs:
+            if req.params.n > 1:
+                req.fork_samples()
             if req.params.max_new_tokens == 0:
                 if req.guide_row >= 0:
-                    self.eng.unpin_guide(req.guide_row)
+                    for _ in range(req.params.n):  # one pin per sample
+                        self.eng.unpin_guide(req.guide_row)
                 req.finish([])
             else:
                 live.append((next(self._ids), req))
@@ -693,10 +796,25 @@ class Scheduler(racecheck.Shared):
             racecheck.note(self, "_pending")
             reqs = [self._pending.pop(i) for i in ids]
         meta, rng = self.meta, self._rng
-        lens, wants, stops, asking = [], [], [], []
+        lens, wants, stops, asking, forks = [], [], [], [], []
+        samples = []  # (sid, its Request, seed) of every sample: n per request, sample 0 under the request's id
         for i, req in zip(ids, reqs):
             p = req.params
             seed = p.seed if p.seed is not None else rng.getrandbits(62)
+            samples.append((i, req, seed))
+            lens.append(len(req.prompt_ids))
+            wants.append(p.max_new_tokens)
+            stops.append(bool(p.stop_at_eos))
+            if p.n > 1:
+                # samples 1 .. n - 1: sequences of their own that fork from sample
+                # 0's KV (core.add_fork), sample k drawing with seed + k
+                for k, sub in enumerate(req.samples[1:], 1):
+                    fid = next(self._ids)
+                    sub.guide_row = req.guide_row
+                    samples.append((fid, sub, seed + k))
+                    forks.append((fid, i, p.max_new_tokens, bool(p.stop_at_eos)))
+        for i, req, seed in samples:
+            p = req.params
             meta[i] = _Meta(req, seed, sampler_values(p, seed), -1 if p.logprobs is None else int(p.logprobs))
             if p.has_logit_edits:
                 meta[i].edits = p.logit_edits(self.eng.mcfg.eos_token_id)
@@ -715,10 +833,11 @@ class Scheduler(racecheck.Shared):
                 self._guided += 1
             if p.stop_token_ids or p.stop_sequences:
                 asking.append((i, p))
-            lens.append(len(req.prompt_ids))
-            wants.append(p.max_new_tokens)
-            stops.append(bool(p.stop_at_eos))
         self.core.add_many(ids, lens, wants, stops)
+        for f in forks:  # behind their parents, ahead of any plan: the parents are still waiting
+            self.core.add_fork(*f)
+        # those with a KV copy ahead: a one-token prompt's samples are plain sequences
+        self._forking += sum(1 for f in forks if len(meta[f[0]].req.prompt_ids) > 1)
         for i, p in asking:  # the requests with stop sequences alone: the core matches their last tokens
             st = meta[i].stops = p.stop_list()
             self.core.set_stops(i, [t for w in st for t in w], [len(w) for w in st], p.min_new_tokens)
@@ -743,7 +862,9 @@ class Scheduler(racecheck.Shared):
             now = time.monotonic()
             for sid in admitted:
                 self.meta[sid].req.t_start = now
-        plans = [StepPlan(step=s, groups=[self._group(go, rep) for go in gos], replica=rep,
+        # (fork sid -> source slot) of this step's fork chunks
+        fk = dict(self.core.forks()) if self._forking else None
+        plans = [StepPlan(step=s, groups=[self._group(go, rep, fk) for go in gos], replica=rep,
                           timing=self.timing) for rep, gos in enumerate(per_rep)]
         c = self.core
         self.stats.update(steps=self.stats["steps"] + 1, joins=c.joins, leaves=c.leaves,
@@ -752,15 +873,22 @@ class Scheduler(racecheck.Shared):
             self.step_log.append((s, any(gp.chunks for p in plans for gp in p.groups)))
         return plans
 
-    def _group(self, go, rep: int = 0) -> GroupPlan:
+    def _group(self, go, rep: int = 0, fk: Optional[dict] = None) -> GroupPlan:
         g, ret, n, b, ctxb, changed, chunks, rows = go
         gp = GroupPlan(g, ret=ret, n=n, b=b, ctxb=ctxb)
         meta = self.meta
         for sid, slot, start, _, _ in chunks:
-            if start == 0 and meta[sid].logprobs >= 0:  # where _finish fetches the logprob records
+            # where _finish fetches the logprob records: noted at the chunk that opens the prompt
+            if (start == 0 or (fk and sid in fk)) and meta[sid].logprobs >= 0:
                 meta[sid].rep, meta[sid].slot = rep, slot
         gp.chunks = [Chunk(sid, slot, start, m.req.prompt_ids[start:start + ln], final, *h, *t)
                      for sid, slot, start, ln, final in chunks for m in (meta[sid],) for h, t in (m.values,)]
+        if fk:
+            for c in gp.chunks:
+                src = fk.get(c.seq)
+                if src is not None:
+                    c.fork = src
+                    self._forking -= 1
         if changed:
             gp.rows = [Row(sid, slot, pos, *h, sstep, src, *t)
                        for sid, slot, pos, sstep, src in rows for h, t in (meta[sid].values,)]
@@ -979,7 +1107,7 @@ class Scheduler(racecheck.Shared):
                 m.done = True
                 m.req.finish(error=err)
         self.meta.clear()
-        self._edited = self._contexts = self._allowing = self._badwords = self._guided = 0
+        self._edited = self._contexts = self._allowing = self._badwords = self._guided = self._forking = 0
         self.eng.unpin_guide(None)
         self.core.reset()
         self.readouts.clear()

@@ -7,11 +7,12 @@ otherwise the string "Error: {code} - {text}"; network failures return
 (temperature, top_k, top_p, min_p, presence_penalty, frequency_penalty, logprobs,
 logit_bias, banned_token_ids, min_new_tokens, repetition_penalty,
 no_repeat_ngram_size, allowed_token_ids, bad_words, bad_words_ids, stop,
-stop_token_ids, include_stop_in_output, guided_regex, guided_choice, greedy, seed,
+stop_token_ids, include_stop_in_output, guided_regex, guided_choice, n, greedy, seed,
 stop_at_eos) are sent
 when given; with logprobs the returned dict
 has a "logprobs" object beside "generated", with stop or stop_token_ids a
-"finish_reason" and, after a stop, a "stop_reason".
+"finish_reason" and, after a stop, a "stop_reason"; with n > 1 "generated" is
+sample 0 and "choices" holds one such object per sample.
 """
 from __future__ import annotations
 
@@ -29,7 +30,7 @@ def generate_text(prompt: str, max_new_tokens: int = 20, url: str = None,
                   no_repeat_ngram_size: int = None, allowed_token_ids: list = None, bad_words: list = None,
                   bad_words_ids: list = None, stop=None, stop_token_ids: list = None,
                   include_stop_in_output: bool = None, guided_regex: str = None,
-                  guided_choice: list = None, **sampling) -> Union[dict, str]:
+                  guided_choice: list = None, n: int = None, **sampling) -> Union[dict, str]:
     import requests
 
     payload = {"prompt": prompt, "max_new_tokens": max_new_tokens}
@@ -39,7 +40,7 @@ def generate_text(prompt: str, max_new_tokens: int = 20, url: str = None,
                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                     allowed_token_ids=allowed_token_ids, bad_words=bad_words, bad_words_ids=bad_words_ids,
                     stop=stop, stop_token_ids=stop_token_ids, include_stop_in_output=include_stop_in_output,
-                    guided_regex=guided_regex, guided_choice=guided_choice)
+                    guided_regex=guided_regex, guided_choice=guided_choice, n=n)
     payload.update({k: v for k, v in sampling.items() if v is not None})
     try:
         r = requests.post(url or COORDINATOR_URL, json=payload, timeout=timeout)

@@ -33,6 +33,7 @@ pipeline into 503s instead of hanging requests.
 from __future__ import annotations
 
 import logging
+import os
 import time
 from typing import Dict, List, Optional, Union
 
@@ -96,6 +97,10 @@ class GenerateReq(BaseModel):
     # server's tokenizer; EOS is allowed exactly where the match is complete, so set stop_at_eos
     guided_regex: Optional[str] = None
     guided_choice: Optional[List[str]] = None
+    # samples of the prompt (at most MAX_SAMPLES, the microbatch capacity and the KV slots):
+    # sample i draws with seed + i; with n > 1 the response keeps "generated" for sample 0
+    # and adds "choices", one object per sample
+    n: int = 1
 
 
 class GuideCache:
@@ -267,8 +272,8 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                             no_repeat_ngram_size=req.no_repeat_ngram_size,
                             allowed_token_ids=req.allowed_token_ids, bad_words=bad,
                             stop_token_ids=req.stop_token_ids, stop_sequences=stops,
-                            include_stop_in_output=req.include_stop_in_output, guide=guide)
-        if req.max_new_tokens == 0 and req.logprobs is None:
+                            include_stop_in_output=req.include_stop_in_output, guide=guide, n=req.n)
+        if req.max_new_tokens == 0 and req.logprobs is None and req.n == 1:
             return {"generated": tok.decode(ids, skip_special_tokens=True)}
         if not ids:
             raise HTTPException(422, "prompt must encode to at least one token")
@@ -277,14 +282,18 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
 
         lp = None
         reason = ("length", None)
+        each = None  # n > 1: (tokens, logprob records, reasons) of every sample
         try:
             sp.validate(cfg.max_logprobs, cfg.max_logit_edits, cfg.max_bad_words, cfg.max_bad_word_tokens,
                         cfg.max_stop_sequences, max_guide_classes=cfg.max_guide_classes,
                         max_guide_cells=cfg.max_guide_cells)
+            if sp.n > cfg.max_samples:
+                raise ValueError(f"n = {sp.n} exceeds max_samples = {cfg.max_samples}")
             if req.max_new_tokens == 0:
                 from ..runtime.scheduler import Logprobs
 
-                out, lp = [], Logprobs([], [], [])
+                out, lp = [], Logprobs([], [], []) if req.logprobs is not None else None
+                each = [(out, lp, reason)] * sp.n
             elif engine is not None:
                 if len(ids) + sp.max_new_tokens > engine.max_seq:
                     raise ValueError(f"prompt ({len(ids)}) + max_new_tokens ({sp.max_new_tokens}) "
@@ -292,11 +301,20 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                 req_ = engine.submit(ids, sp)
                 out = req_.wait(timeout=cfg.request_timeout_s)
                 lp, reason = req_.logprobs, (req_.finish_reason, req_.stop_reason)
-                metrics.observe_request(len(out), time.perf_counter() - t0,
+                each = [(s.wait(0), s.logprobs, (s.finish_reason, s.stop_reason)) for s in req_.samples]
+                metrics.observe_request(sum(len(e[0]) for e in each), time.perf_counter() - t0,
                                         ttft_s=(req_.t_first - req_.t_submit) if req_.t_first else None)
             else:
-                out, lp, reason = http_generate(cfg, ids, sp, records=True, reasons=True)
-                metrics.observe_request(len(out), time.perf_counter() - t0)
+                # the relay has no engine: the samples one after another, sample i with seed + i
+                import dataclasses
+
+                base = sp.seed
+                if base is None and sp.n > 1:
+                    base = int.from_bytes(os.urandom(7), "little")
+                each = [http_generate(cfg, ids, dataclasses.replace(sp, n=1, seed=None if base is None else base + i),
+                                      records=True, reasons=True) for i in range(sp.n)]
+                out, lp, reason = each[0]
+                metrics.observe_request(sum(len(e[0]) for e in each), time.perf_counter() - t0)
         except ValueError as e:
             raise HTTPException(422, str(e))
         except RequestTimeout as e:
@@ -305,13 +323,19 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
             if engine is not None and not engine.healthy:
                 raise HTTPException(503, f"engine unhealthy: {engine.last_error}")
             raise
-        body = {"generated": tok.decode(ids + out, skip_special_tokens=True)}
-        if lp is not None:
-            body["logprobs"] = logprobs_json(lp)
-        if asked_stop:
-            body["finish_reason"] = reason[0]
-            if reason[1] is not None:
-                body["stop_reason"] = reason[1]
+        def sample_json(out, lp, reason):
+            b = {"generated": tok.decode(ids + out, skip_special_tokens=True)}
+            if lp is not None:
+                b["logprobs"] = logprobs_json(lp)
+            if asked_stop:
+                b["finish_reason"] = reason[0]
+                if reason[1] is not None:
+                    b["stop_reason"] = reason[1]
+            return b
+
+        body = sample_json(out, lp, reason)
+        if sp.n > 1:
+            body["choices"] = [sample_json(*e) for e in each]
         return body
 
     @app.get("/health")
