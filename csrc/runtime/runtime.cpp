@@ -112,6 +112,12 @@ PYBIND11_MODULE(_runtime, m) {
       .def("add_fork", &SchedCore::add_fork, py::arg("sid"), py::arg("parent"), py::arg("want"),
            py::arg("stop_at_eos"))
       .def("forks", [](const SchedCore& c) { return c.forks(); })
+      .def("set_prefix_cache", &SchedCore::set_prefix_cache, py::arg("max_entries"), py::arg("min_tokens"))
+      .def("set_prompt", &SchedCore::set_prompt, py::arg("sid"), py::arg("tokens"), py::arg("lookup") = true)
+      .def("hits", [](const SchedCore& c) { return c.hits(); })
+      .def("prefix_cache_stats", &SchedCore::prefix_cache_stats)
+      .def("prefix_entries", &SchedCore::prefix_entries, py::arg("rep"))
+      .def("clear_prefix_cache", &SchedCore::clear_prefix_cache)
       .def("has_work", &SchedCore::has_work)
       .def("plan", [](SchedCore& c, int64_t step) {
              std::vector<int64_t> admitted;

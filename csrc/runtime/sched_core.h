@@ -15,7 +15,9 @@
 //   * readout assignment: sampled ids -> per-sequence events, EOS stop,
 //     per-request stop sequences, and slot release at a sequence's last item;
 //   * families (add_fork): further samples of one prompt, admitted with their
-//     parent and started from a copy of its KV instead of a prefill.
+//     parent and started from a copy of its KV instead of a prefill;
+//   * the prefix cache (set_prefix_cache): slots that finished requests left,
+//     keyed by their prompts, which later prompts start their prefill behind.
 // The reference has no scheduler at all. Its coordinator runs one request's
 // token loop per HTTP call (`server.py:154-206`); see SURVEY.md §5.2.
 //
@@ -95,7 +97,7 @@ class SchedCore {
             std::vector<SlotAllocator*> pools)
       : R_(replicas), M_(groups), cap_(cap), budget_(prefill_budget), chunk_(chunk),
         max_seq_(max_seq), pools_(std::move(pools)),
-        groups_(replicas, std::vector<Group>(groups)) {
+        groups_(replicas, std::vector<Group>(groups)), caches_(replicas) {
     if ((int)pools_.size() != R_) throw std::invalid_argument("one slot pool per replica");
   }
 
@@ -146,6 +148,7 @@ class SchedCore {
     const int L = it->second.prompt_len;
     if (L == 1) {
       add(sid, 1, want, stop_at_eos);
+      seqs_.at(sid).prompt = seqs_.at(parent).prompt;
       return;
     }
     Seq s;
@@ -153,12 +156,95 @@ class SchedCore {
     s.want = want;
     s.stop_at_eos = stop_at_eos;
     s.parent = parent;
+    s.prompt = it->second.prompt;
     seqs_[sid] = s;
     seqs_.at(parent).forks.push_back(sid);
   }
 
-  // (fork sid, source slot) of the fork chunks of the last plan(), in plan order
+  // (sid, source slot) of the chunks of the last plan() that start behind a
+  // copy of another slot's KV, in plan order: the families' fork chunks, and
+  // the first chunk of every sequence that hit the prefix cache
   const std::vector<std::pair<int64_t, int>>& forks() const { return forks_; }
+
+  // The prefix cache.  An *entry* is a KV slot that a finished sequence left,
+  // valid for positions [0, L) of that sequence's prompt -- its key; the slot
+  // stays taken from the pool.  Off (max_entries 0) nothing below happens.
+  //   insert: when a sequence with a prompt (set_prompt) gives its slot back
+  //     (release) the slot becomes an entry instead, at no copy.  A prompt
+  //     shorter than min_tokens can never be matched: its slot is freed.  If an
+  //     entry's key starts with the new key the new slot is freed (and the
+  //     entry counts as used now); every unpinned entry whose key the new key
+  //     starts with is freed.  At most max_entries per replica: the least
+  //     recently used unpinned entry goes first (with every entry pinned the
+  //     new slot is freed instead);
+  //   lookup: at admission, for a sequence whose set_prompt asked for it, over
+  //     the entries of the admitting replica that share the prompt's first
+  //     min_tokens tokens (one hash lookup finds them).  c = the longest
+  //     common prefix with an entry's key, m = min(c, L - 1) -- one token is
+  //     always forwarded, to take draw 0 -- the largest m wins, ties go to the
+  //     most recently used entry, and m >= min_tokens is a hit;
+  //   hit: the sequence starts with prefilled = m; its first chunk
+  //     (sid, slot, m, len, final?) is reported by forks() with the entry's
+  //     slot, and by hits() with m; chunk length and budget apply to the tail;
+  //   pin: the entry is pinned from the admission until the hitting
+  //     sequence's first token has been read back (EV_FIRST): the item that
+  //     drew it ran behind the copy on the same lane.  A pinned entry is never
+  //     evicted and never handed out;
+  //   evict: an admission that needs 1 + k slots while the pool is short gives
+  //     least recently used unpinned entries back to the pool, never the one
+  //     just matched -- unless the family cannot fit beside it: then the match
+  //     is dropped (a miss) and that entry may go too.  Nothing is evicted for
+  //     a family that would not fit even so.
+  // free slots + entries + slots held by sequences = the pool's capacity.
+  void set_prefix_cache(int max_entries, int min_tokens) {
+    if (max_entries < 0 || min_tokens < 1) throw std::invalid_argument("set_prefix_cache: max_entries >= 0, min_tokens >= 1");
+    clear_prefix_cache();
+    for (const auto& c : caches_)
+      if (!c.entries.empty()) throw std::runtime_error("set_prefix_cache: entries are pinned by sequences in flight");
+    pc_max_ = max_entries;
+    pc_min_ = min_tokens;
+  }
+
+  // The prompt of a sequence that was added and is not admitted yet (its forks
+  // share it): the sequence leaves an entry behind, and with `lookup` it may
+  // start from one.  The core holds no token ids otherwise.
+  void set_prompt(int64_t sid, const std::vector<int>& tokens, bool lookup = true) {
+    auto it = seqs_.find(sid);
+    if (it == seqs_.end()) throw std::invalid_argument("set_prompt: unknown sequence");
+    Seq& s = it->second;
+    if (s.slot >= 0 || s.g >= 0) throw std::invalid_argument("set_prompt: the sequence is admitted already");
+    if ((int)tokens.size() != s.prompt_len) throw std::invalid_argument("set_prompt: not prompt_len tokens");
+    s.prompt = std::make_shared<const std::vector<int>>(tokens);
+    s.lookup = lookup;
+    for (int64_t fid : s.forks) seqs_.at(fid).prompt = s.prompt;
+  }
+
+  // (sid, m) of the prefix-cache hits among forks(), in plan order
+  const std::vector<std::pair<int64_t, int>>& hits() const { return hits_; }
+
+  // (entries, hits, misses, tokens reused, evictions)
+  std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t> prefix_cache_stats() const {
+    int64_t n = 0;
+    for (const auto& c : caches_) n += (int64_t)c.entries.size();
+    return {n, pc_hits_, pc_misses_, pc_tokens_, pc_evictions_};
+  }
+
+  // (slot, pins, key) of replica rep's entries, by slot (tests, debugging)
+  std::vector<std::tuple<int, int, std::vector<int>>> prefix_entries(int rep) const {
+    std::vector<std::tuple<int, int, std::vector<int>>> out;
+    for (const auto& kv : caches_.at(rep).entries) out.emplace_back(kv.first, kv.second.pins, kv.second.toks);
+    return out;
+  }
+
+  // Free the unpinned entries.
+  void clear_prefix_cache() {
+    for (int rep = 0; rep < R_; ++rep) {
+      std::vector<int> go;
+      for (const auto& kv : caches_[rep].entries)
+        if (kv.second.pins == 0) go.push_back(kv.first);
+      for (int slot : go) drop_entry(rep, slot);
+    }
+  }
 
   // Stop sequences of a sequence that was added and has no token yet:
   // lengths[e] tokens of flat_tokens each, tried in this order.  After its
@@ -202,6 +288,7 @@ class SchedCore {
   std::vector<std::vector<GroupOut>> plan(int64_t step, std::vector<int64_t>* admitted) {
     std::vector<std::vector<GroupOut>> out(R_);
     forks_.clear();
+    hits_.clear();
     for (int rep = 0; rep < R_; ++rep)
       for (int g = 0; g < M_; ++g) {
         GroupOut go;
@@ -258,11 +345,16 @@ class SchedCore {
   void reset() {
     for (auto& kv : seqs_)
       if (kv.second.slot >= 0) pools_[kv.second.rep]->free({kv.second.slot});
+    for (int rep = 0; rep < R_; ++rep) {  // every entry, the pinned ones too: their sequences are gone
+      for (const auto& kv : caches_[rep].entries) pools_[rep]->free({kv.first});
+      caches_[rep] = Cache();
+    }
     seqs_.clear();
     waiting_.clear();
     expect_.clear();
     produced_.clear();
     forks_.clear();
+    hits_.clear();
     groups_.assign(R_, std::vector<Group>(M_));
   }
 
@@ -309,6 +401,24 @@ class SchedCore {
     int src_slot = -1;
     bool ready = false;
     std::vector<int64_t> forks;
+    // prefix cache: the prompt's ids (null: the sequence opted out), whether it
+    // looks an entry up at admission, and of a hit the entry's slot (pinned
+    // until this sequence's first token) and whether its first chunk is still
+    // to be planned
+    std::shared_ptr<const std::vector<int>> prompt;
+    bool lookup = false, hit_new = false;
+    int hit_slot = -1;
+  };
+  struct Entry {
+    std::vector<int> toks;
+    int pins = 0;
+    int64_t used = 0;  // tick of the insert or of the last hit
+  };
+  // one replica's entries by slot, and the slots by the hash of their keys'
+  // first min_tokens tokens
+  struct Cache {
+    std::map<int, Entry> entries;
+    std::unordered_map<uint64_t, std::vector<int>> index;
   };
   struct Produced {
     int b = 0;
@@ -350,11 +460,43 @@ class SchedCore {
   std::vector<int64_t> admit(int rep, int g, int room, std::vector<int64_t>* admitted) {
     SlotAllocator* pool = pools_[rep];
     std::vector<int64_t> out;
-    while (!waiting_.empty() && room > 0 && pool->available() > 0) {
+    while (!waiting_.empty() && room > 0 && pool->available() + (int)caches_[rep].entries.size() > 0) {
       const int64_t sid = waiting_.front();
       Seq& s = seqs_.at(sid);
       const int k = (int)s.forks.size();
-      if (room < 1 + k || pool->available() < 1 + k) break;  // a family is admitted as a unit
+      if (room < 1 + k) break;  // a family is admitted as a unit
+      int src = -1, m = 0;
+      if (pc_max_ > 0) {
+        if (s.lookup && s.prompt) m = lookup(rep, *s.prompt, &src);
+        if (pool->available() < 1 + k) {
+          // the slots that evictions could add: every unpinned entry but the match
+          int spare = 0;
+          for (const auto& kv : caches_[rep].entries) spare += kv.second.pins == 0 && kv.first != src;
+          if (src >= 0 && pool->available() + spare < 1 + k && caches_[rep].entries.at(src).pins == 0) {
+            src = -1;  // the family does not fit beside the entry it matched: a miss
+            m = 0;
+            spare += 1;
+          }
+          if (pool->available() + spare < 1 + k) break;
+          while (pool->available() < 1 + k) evict_lru(rep, src);
+        }
+        if (s.lookup && s.prompt) {
+          if (src >= 0) {
+            Entry& e = caches_[rep].entries.at(src);
+            e.pins += 1;
+            e.used = ++pc_tick_;
+            s.hit_slot = src;
+            s.hit_new = true;
+            s.prefilled = m;
+            pc_hits_ += 1;
+            pc_tokens_ += m;
+          } else {
+            pc_misses_ += 1;
+          }
+        }
+      } else if (pool->available() < 1 + k) {
+        break;
+      }
       waiting_.pop_front();
       s.rep = rep;
       s.g = g;
@@ -375,6 +517,116 @@ class SchedCore {
       joins_ += 1 + k;
     }
     return out;
+  }
+
+  // FNV-1a over the first pc_min_ tokens (the caller made sure they exist)
+  uint64_t head_hash(const std::vector<int>& toks) const {
+    uint64_t h = 1469598103934665603ull;
+    for (int i = 0; i < pc_min_; ++i) {
+      h ^= (uint64_t)(uint32_t)toks[i];
+      h *= 1099511628211ull;
+    }
+    return h;
+  }
+
+  // The best entry of replica rep for `toks`: -> m (0: none), *src its slot.
+  int lookup(int rep, const std::vector<int>& toks, int* src) const {
+    const int L = (int)toks.size();
+    *src = -1;
+    if (L - 1 < pc_min_) return 0;
+    const Cache& c = caches_[rep];
+    const auto b = c.index.find(head_hash(toks));
+    if (b == c.index.end()) return 0;
+    int best = 0;
+    int64_t best_used = -1;
+    for (int slot : b->second) {
+      const Entry& e = c.entries.at(slot);
+      const int n = std::min(L, (int)e.toks.size());
+      int cp = 0;
+      while (cp < n && e.toks[cp] == toks[cp]) ++cp;
+      const int m = std::min(cp, L - 1);
+      if (m < pc_min_) continue;
+      if (m > best || (m == best && e.used > best_used)) {
+        best = m;
+        best_used = e.used;
+        *src = slot;
+      }
+    }
+    return best;
+  }
+
+  void drop_entry(int rep, int slot) {
+    Cache& c = caches_[rep];
+    const auto it = c.entries.find(slot);
+    const uint64_t h = head_hash(it->second.toks);
+    auto& b = c.index.at(h);
+    b.erase(std::find(b.begin(), b.end(), slot));
+    if (b.empty()) c.index.erase(h);
+    c.entries.erase(it);
+    pools_[rep]->free({slot});
+  }
+
+  // Give the least recently used unpinned entry other than `keep` back to the
+  // pool (the caller made sure there is one).
+  void evict_lru(int rep, int keep) {
+    int slot = -1;
+    int64_t used = 0;
+    for (const auto& kv : caches_[rep].entries)
+      if (kv.second.pins == 0 && kv.first != keep && (slot < 0 || kv.second.used < used)) {
+        slot = kv.first;
+        used = kv.second.used;
+      }
+    if (slot < 0) throw std::logic_error("prefix cache: no entry to evict");
+    drop_entry(rep, slot);
+    pc_evictions_ += 1;
+  }
+
+  // A released slot whose sequence had a prompt: an entry, or back to the pool.
+  void insert_entry(int rep, int slot, const std::vector<int>& toks) {
+    Cache& c = caches_[rep];
+    const int L = (int)toks.size();
+    if (L < pc_min_) {
+      pools_[rep]->free({slot});
+      return;
+    }
+    const uint64_t h = head_hash(toks);
+    const auto b = c.index.find(h);
+    if (b != c.index.end()) {
+      std::vector<int> covered;
+      for (int other : b->second) {
+        Entry& e = c.entries.at(other);
+        const int n = (int)e.toks.size();
+        if (n >= L && std::equal(toks.begin(), toks.end(), e.toks.begin())) {
+          e.used = ++pc_tick_;  // the entry covers the new key
+          pools_[rep]->free({slot});
+          return;
+        }
+        if (n < L && e.pins == 0 && std::equal(e.toks.begin(), e.toks.end(), toks.begin())) covered.push_back(other);
+      }
+      for (int other : covered) drop_entry(rep, other);
+    }
+    if ((int)c.entries.size() >= pc_max_) {
+      bool any = false;
+      for (const auto& kv : c.entries) any = any || kv.second.pins == 0;
+      if (!any) {
+        pools_[rep]->free({slot});
+        return;
+      }
+      evict_lru(rep, -1);
+    }
+    Entry e;
+    e.toks = toks;
+    e.used = ++pc_tick_;
+    c.entries.emplace(slot, std::move(e));
+    c.index[h].push_back(slot);
+  }
+
+  // The sequence's first token is back: the copy from the entry it hit is done.
+  void unpin(Seq& s) {
+    if (s.hit_slot < 0) return;
+    const auto it = caches_[s.rep].entries.find(s.hit_slot);
+    if (it != caches_[s.rep].entries.end() && it->second.pins > 0) it->second.pins -= 1;
+    s.hit_slot = -1;
   }
 
   bool group_plan(int rep, int g, int64_t step, GroupOut* go, std::vector<int64_t>* admitted) {
@@ -456,6 +708,11 @@ class SchedCore {
       const int a = s.prefilled;
       const bool final = a + take == L;
       chunks.emplace_back(sid, s.slot, a, take, final);
+      if (s.hit_new) {  // the first chunk of a prefix-cache hit: behind a copy of [0, a)
+        forks_.emplace_back(sid, s.hit_slot);
+        hits_.emplace_back(sid, a);
+        s.hit_new = false;
+      }
       s.prefilled += take;
       if (final) {
         gh.prefilling.erase(std::find(gh.prefilling.begin(), gh.prefilling.end(), sid));
@@ -547,6 +804,7 @@ class SchedCore {
     Seq& s = it->second;
     if (s.finished || s.ntok >= s.want) return;
     int flags = s.ntok == 0 ? EV_FIRST : 0;
+    if (flags) unpin(s);
     s.ntok += 1;
     const bool hit = s.stops && stop_match(*s.stops, tok, s.ntok);
     if (s.stop_at_eos && tok == eos) {
@@ -568,6 +826,7 @@ class SchedCore {
     Seq& s = it->second;
     if (s.finished || s.ntok >= s.want) return;
     int flags = s.ntok == 0 ? EV_FIRST : 0;
+    if (flags) unpin(s);
     s.ntok += 1;
     s.toks.push_back(tok);
     const bool hit = s.stops && stop_match(*s.stops, tok, s.ntok);
@@ -588,9 +847,15 @@ class SchedCore {
   void release(int64_t sid, std::vector<Event>* ev) {
     auto it = seqs_.find(sid);
     if (it == seqs_.end()) return;
-    const Seq s = it->second;
+    Seq s = it->second;
     seqs_.erase(it);
-    if (s.slot >= 0) pools_[s.rep]->free({s.slot});
+    unpin(s);
+    if (s.slot >= 0) {
+      if (pc_max_ > 0 && s.prompt)
+        insert_entry(s.rep, s.slot, *s.prompt);
+      else
+        pools_[s.rep]->free({s.slot});
+    }
     ev->emplace_back(sid, -1, EV_RELEASE | (s.finished ? 0 : EV_FINISH));
   }
 
@@ -606,7 +871,10 @@ class SchedCore {
   int64_t next_id_ = 0, joins_ = 0, leaves_ = 0, steps_ = 0, deferred_ = 0;
   int join_min_ = 1, max_wait_ = 0;
   int max_rows_ = 0;
-  std::vector<std::pair<int64_t, int>> forks_;
+  std::vector<std::pair<int64_t, int>> forks_, hits_;
+  std::vector<Cache> caches_;
+  int pc_max_ = 0, pc_min_ = 8;
+  int64_t pc_tick_ = 0, pc_hits_ = 0, pc_misses_ = 0, pc_tokens_ = 0, pc_evictions_ = 0;
 };
 
 }  // namespace lsd_rt

@@ -413,6 +413,14 @@ class SamplingParams:
     # (csrc/kernels/kv_fork.hip).  At most EngineConfig.max_samples, the
     # microbatch capacity and the KV slot count.  greedy gives n equal samples
     n: int = 1
+    # The per-request opt-out of the engine's prefix cache
+    # (EngineConfig.prefix_cache): False and the request neither starts from a
+    # cached prompt's KV nor leaves its own behind, so its tokens are exactly
+    # those of an engine without the cache.  Nothing while the cache is off.
+    # A request that reads its prompt on the last stage (repetition_penalty,
+    # no_repeat_ngram_size, bad_words) never starts from an entry -- the
+    # entry's prompt ids are not kept there -- but still leaves one
+    prefix_cache: bool = True
 
     @property
     def has_stops(self) -> bool:
@@ -572,6 +580,8 @@ class SamplingParams:
                                  "itself, and no static check shows that a token stays drawable in every state")
         if not isinstance(self.include_stop_in_output, bool):
             raise ValueError("include_stop_in_output must be a bool")
+        if not isinstance(self.prefix_cache, bool):
+            raise ValueError("prefix_cache must be a bool")
         if self.stop_token_ids is not None or self.stop_sequences is not None:
             st = self.stop_list()
             if any(not 1 <= len(w) <= MAX_STOP_LEN for w in st):
@@ -747,8 +757,23 @@ class EngineConfig:
     # samples are admitted together, so n is also bounded by the microbatch
     # capacity and the KV slot count.  At most 64.
     max_samples: int = 8
+    # Prefix cache (runtime/sched_core.h set_prefix_cache): a finished
+    # request's KV slot stays behind as an entry keyed by its prompt, at most
+    # this many per replica (0 = off), and a later prompt that shares at least
+    # prefix_cache_min_tokens leading tokens with one starts its prefill
+    # behind a copy of them (csrc/kernels/kv_fork.hip).  Entries are slots of
+    # the replica's pool: they go back to it, least recently used first, when
+    # an admission needs them.  8: a lone hit's first token on GPT-2 XL was no
+    # later than the miss's from 8 reused tokens on (tools/prefix_cache_ab.py
+    # --cases lone, profiles/prefix_cache_ab.log), by less than the runs' spread.
+    prefix_cache: int = 0
+    prefix_cache_min_tokens: int = 8
 
     def __post_init__(self):
+        if not (0 <= self.prefix_cache <= self.max_batch):
+            raise ValueError("prefix_cache must be in [0, max_batch]: an entry is one of the replica's KV slots")
+        if self.prefix_cache_min_tokens < 1:
+            raise ValueError("prefix_cache_min_tokens must be at least 1")
         if not (1 <= self.max_samples <= MAX_SAMPLES_CEILING):
             raise ValueError(f"max_samples must be in [1, {MAX_SAMPLES_CEILING}]")
         if not (1 <= self.max_guides <= MAX_GUIDES_CEILING):
@@ -809,6 +834,8 @@ class EngineConfig:
             max_guide_classes=int(_env("MAX_GUIDE_CLASSES", "1024")),
             max_guide_cells=int(_env("MAX_GUIDE_CELLS", str(1 << 18))),
             max_samples=int(_env("MAX_SAMPLES", "8")),
+            prefix_cache=int(_env("PREFIX_CACHE", "0")),
+            prefix_cache_min_tokens=int(_env("PREFIX_CACHE_MIN_TOKENS", "8")),
         )
         if cfg.split_points and cfg.num_stages == 1:
             cfg.num_stages = len(cfg.split_points) + 1

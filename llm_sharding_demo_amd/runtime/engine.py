@@ -638,6 +638,24 @@ class Engine(racecheck.Shared):
         reqs = self.generate_requests(prompts, params, microbatches, record_timing)
         return [[s.wait(0) for s in r.samples] for r in reqs]
 
+    def prefix_cache_stats(self) -> dict:
+        """The prefix cache's counters (EngineConfig.prefix_cache): the entries
+        held now over every replica, and since the engine started the hits, the
+        misses (lookups that found nothing long enough), the prompt tokens
+        whose prefill a hit skipped, and the entries evicted for their slots.
+        All zero while the cache is off."""
+        names = ("entries", "hits", "misses", "tokens_reused", "evictions")
+        if self.cfg.prefix_cache <= 0:
+            return dict.fromkeys(names, 0)
+        return dict(zip(names, map(int, self.scheduler.core.prefix_cache_stats())))
+
+    def prefix_cache_clear(self) -> None:
+        """Give every entry's KV slot back to its pool.  Waits for the running
+        session to go idle, so no request in flight still copies from one."""
+        if self.cfg.prefix_cache > 0:
+            with self._lock:
+                self.scheduler.core.clear_prefix_cache()
+
     def fetch_logprobs(self, replica: int, slot: int, n: int) -> tuple:
         """Logprob records [0, n) of KV slot `slot` from the replica's last
         stage, which lives in this process (local mode; _validate refuses the
@@ -661,6 +679,8 @@ class Engine(racecheck.Shared):
                 raise RuntimeError("regrouping needs every rank: set num_microbatches instead")
             self.M = max(1, M)
             self.group_cap = -(-self.cfg.max_batch // self.M)
+            if self.cfg.prefix_cache > 0:
+                self.scheduler.core.clear_prefix_cache()  # the entries' slots: the new core starts without them
             self.scheduler = Scheduler(self, self.M, self.group_cap)
             self.workers[0].readout = self.scheduler.on_readout
             self.workers[0].readout_native = self.scheduler.on_readout_native

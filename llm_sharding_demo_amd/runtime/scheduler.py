@@ -83,6 +83,7 @@ class Request:
     finish_reason: Optional[str] = None  # "length" | "eos" | "stop", once finished without an error
     stop_reason: Optional[int] = None    # the matched stop sequence's index in params.stop_list(), with "stop"
     guide_row: int = -1  # the row of the last stage's guide table the engine pinned for params.guide (-1: none)
+    cached_tokens: int = 0  # leading prompt tokens whose KV came from a prefix-cache entry (0: a miss, or no cache)
     _flag: bool = False
     _ev: Optional[threading.Event] = None
     # params.n > 1: the n samples in sample order, this request (sample 0) first;
@@ -291,6 +292,31 @@ class _Seq:
     src_slot: int = -1
     ready: bool = False
     forks: List[int] = field(default_factory=list)
+    # prefix cache: the prompt's ids (None: the sequence opted out), whether it
+    # looks an entry up at admission, and of a hit the entry's slot (pinned
+    # until this sequence's first token) and whether its first chunk is still
+    # to be planned
+    prompt: Optional[tuple] = None
+    lookup: bool = False
+    hit_new: bool = False
+    hit_slot: int = -1
+
+
+@dataclass
+class _Entry:
+    """A prefix-cache entry: the slot's key (a finished sequence's prompt), the
+    hits that pin it, and the tick of its insert or last hit."""
+    toks: tuple
+    pins: int = 0
+    used: int = 0
+
+
+@dataclass
+class _Cache:
+    """One replica's entries by slot, and the slots by their keys' first
+    min_tokens tokens."""
+    entries: Dict[int, _Entry] = field(default_factory=dict)
+    index: Dict[tuple, List[int]] = field(default_factory=dict)
 
 
 @dataclass
@@ -338,6 +364,130 @@ class PySchedCore:
         self.joins = self.leaves = self.max_rows = self.steps = 0
         self.join_min, self.max_wait, self.deferred = 1, 0, 0
         self._forks: List[tuple] = []
+        self._hits: List[tuple] = []
+        self.caches = [_Cache() for _ in range(replicas)]
+        self.pc_max, self.pc_min, self.pc_tick = 0, 8, 0
+        self.pc_hits = self.pc_misses = self.pc_tokens = self.pc_evictions = 0
+
+    # -- the prefix cache (lsd_rt::SchedCore::set_prefix_cache has the rules) --
+    def set_prefix_cache(self, max_entries: int, min_tokens: int) -> None:
+        if max_entries < 0 or min_tokens < 1:
+            raise ValueError("set_prefix_cache: max_entries >= 0, min_tokens >= 1")
+        self.clear_prefix_cache()
+        if any(c.entries for c in self.caches):
+            raise RuntimeError("set_prefix_cache: entries are pinned by sequences in flight")
+        self.pc_max, self.pc_min = max_entries, min_tokens
+
+    def set_prompt(self, sid: int, tokens, lookup: bool = True) -> None:
+        """lsd_rt::SchedCore::set_prompt: the prompt of a sequence that is not
+        admitted yet (its forks share it); it leaves an entry behind, and with
+        `lookup` it may start from one."""
+        s = self.seqs.get(sid)
+        if s is None:
+            raise ValueError("set_prompt: unknown sequence")
+        if s.slot >= 0 or s.g >= 0:
+            raise ValueError("set_prompt: the sequence is admitted already")
+        if len(tokens) != s.prompt_len:
+            raise ValueError("set_prompt: not prompt_len tokens")
+        s.prompt, s.lookup = tuple(tokens), bool(lookup)
+        for fid in s.forks:
+            self.seqs[fid].prompt = s.prompt
+
+    def hits(self) -> List[tuple]:
+        """(sid, m) of the prefix-cache hits among forks(), in plan order."""
+        return list(self._hits)
+
+    def prefix_cache_stats(self) -> tuple:
+        """(entries, hits, misses, tokens reused, evictions)."""
+        return (sum(len(c.entries) for c in self.caches), self.pc_hits, self.pc_misses, self.pc_tokens,
+                self.pc_evictions)
+
+    def prefix_entries(self, rep: int) -> List[tuple]:
+        """(slot, pins, key) of replica rep's entries, by slot."""
+        return [(slot, e.pins, list(e.toks)) for slot, e in sorted(self.caches[rep].entries.items())]
+
+    def clear_prefix_cache(self) -> None:
+        for rep, c in enumerate(self.caches):
+            for slot in [slot for slot, e in c.entries.items() if e.pins == 0]:
+                self._drop_entry(rep, slot)
+
+    def _lookup(self, rep: int, toks: tuple) -> tuple:
+        """The best entry of replica rep for `toks`: (m, slot), (0, -1) without."""
+        L = len(toks)
+        if L - 1 < self.pc_min:
+            return 0, -1
+        c = self.caches[rep]
+        best, best_used, src = 0, -1, -1
+        for slot in c.index.get(toks[: self.pc_min], ()):
+            e = c.entries[slot]
+            cp = 0
+            for a, b in zip(e.toks, toks):
+                if a != b:
+                    break
+                cp += 1
+            m = min(cp, L - 1)
+            if m >= self.pc_min and (m > best or (m == best and e.used > best_used)):
+                best, best_used, src = m, e.used, slot
+        return best, src
+
+    def _drop_entry(self, rep: int, slot: int) -> None:
+        c = self.caches[rep]
+        e = c.entries.pop(slot)
+        b = c.index[e.toks[: self.pc_min]]
+        b.remove(slot)
+        if not b:
+            del c.index[e.toks[: self.pc_min]]
+        self.pools[rep].free([slot])
+
+    def _evict_lru(self, rep: int, keep: int) -> None:
+        slot = min((e.used, slot) for slot, e in self.caches[rep].entries.items() if e.pins == 0 and slot != keep)[1]
+        self._drop_entry(rep, slot)
+        self.pc_evictions += 1
+
+    def _insert_entry(self, rep: int, slot: int, toks: tuple) -> None:
+        c, L = self.caches[rep], len(toks)
+        if L < self.pc_min:
+            self.pools[rep].free([slot])
+            return
+        covered = []
+        for other in c.index.get(toks[: self.pc_min], ()):
+            e = c.entries[other]
+            n = len(e.toks)
+            if n >= L and e.toks[:L] == toks:
+                self.pc_tick += 1
+                e.used = self.pc_tick  # the entry covers the new key
+                self.pools[rep].free([slot])
+                return
+            if n < L and e.pins == 0 and toks[:n] == e.toks:
+                covered.append(other)
+        for other in covered:
+            self._drop_entry(rep, other)
+        if len(c.entries) >= self.pc_max:
+            if all(e.pins for e in c.entries.values()):
+                self.pools[rep].free([slot])
+                return
+            self._evict_lru(rep, -1)
+        self.pc_tick += 1
+        c.entries[slot] = _Entry(toks, 0, self.pc_tick)
+        c.index.setdefault(toks[: self.pc_min], []).append(slot)
+
+    def _unpin(self, s: "_Seq") -> None:
+        if s.hit_slot < 0:
+            return
+        e = self.caches[s.rep].entries.get(s.hit_slot)
+        if e is not None and e.pins > 0:
+            e.pins -= 1
+        s.hit_slot = -1
+
+    def _release_slot(self, s: "_Seq") -> None:
+        """A leaving sequence's slot: an entry when it has a prompt and the
+        cache is on, else back to the pool."""
+        self._unpin(s)
+        if s.slot >= 0:
+            if self.pc_max > 0 and s.prompt is not None:
+                self._insert_entry(s.rep, s.slot, s.prompt)
+            else:
+                self.pools[s.rep].free([s.slot])
 
     def add_fork(self, sid: int, parent: int, want: int, stop_at_eos: bool) -> None:
         """lsd_rt::SchedCore::add_fork: a further sample of `parent`'s prompt.
@@ -355,12 +505,15 @@ class PySchedCore:
             raise ValueError("add_fork: the sequence exists already")
         if p.prompt_len == 1:
             self.add(sid, 1, want, stop_at_eos)
+            self.seqs[sid].prompt = p.prompt
             return
-        self.seqs[sid] = _Seq(p.prompt_len, want, stop_at_eos, parent=parent)
+        self.seqs[sid] = _Seq(p.prompt_len, want, stop_at_eos, parent=parent, prompt=p.prompt)
         p.forks.append(sid)
 
     def forks(self) -> List[tuple]:
-        """(fork sid, source slot) of the fork chunks of the last plan(), in plan order."""
+        """(sid, source slot) of the chunks of the last plan() that start behind a
+        copy of another slot's KV, in plan order: the families' fork chunks and
+        the first chunk of every prefix-cache hit."""
         return list(self._forks)
 
     def set_join_policy(self, join_min: int, max_wait: int) -> None:
@@ -451,6 +604,7 @@ class PySchedCore:
         admitted: List[int] = []
         out = []
         self._forks = []
+        self._hits = []
         for rep in range(self.R):
             gs = []
             for g in range(self.M):
@@ -464,12 +618,38 @@ class PySchedCore:
     def _admit(self, rep: int, g: int, room: int, admitted: List[int]) -> List[int]:
         pool = self.pools[rep]
         out = []
-        while self.waiting and room > 0 and pool.available > 0:
+        cache = self.caches[rep]
+        while self.waiting and room > 0 and pool.available + len(cache.entries) > 0:
             sid = self.waiting[0]
             s = self.seqs[sid]
             k = len(s.forks)
-            if room < 1 + k or pool.available < 1 + k:
+            if room < 1 + k:
                 break  # a family is admitted as a unit
+            if self.pc_max > 0:
+                looks = s.lookup and s.prompt is not None
+                m, src = self._lookup(rep, s.prompt) if looks else (0, -1)
+                if pool.available < 1 + k:
+                    # the slots that evictions could add: every unpinned entry but the match
+                    spare = sum(1 for slot, e in cache.entries.items() if e.pins == 0 and slot != src)
+                    if src >= 0 and pool.available + spare < 1 + k and cache.entries[src].pins == 0:
+                        m, src = 0, -1  # the family does not fit beside the entry it matched: a miss
+                        spare += 1
+                    if pool.available + spare < 1 + k:
+                        break
+                    while pool.available < 1 + k:
+                        self._evict_lru(rep, src)
+                if looks and src >= 0:
+                    e = cache.entries[src]
+                    e.pins += 1
+                    self.pc_tick += 1
+                    e.used = self.pc_tick
+                    s.hit_slot, s.hit_new, s.prefilled = src, True, m
+                    self.pc_hits += 1
+                    self.pc_tokens += m
+                elif looks:
+                    self.pc_misses += 1
+            elif pool.available < 1 + k:
+                break
             self.waiting.popleft()
             s.rep, s.g = rep, g
             s.slot = pool.alloc(1)[0]
@@ -536,6 +716,10 @@ class PySchedCore:
             a = s.prefilled
             final = a + n == L
             chunks.append((sid, s.slot, a, n, final))
+            if s.hit_new:  # the first chunk of a prefix-cache hit: behind a copy of [0, a)
+                self._forks.append((sid, s.hit_slot))
+                self._hits.append((sid, a))
+                s.hit_new = False
             s.prefilled += n
             if final:
                 gh.prefilling.remove(sid)
@@ -584,8 +768,7 @@ class PySchedCore:
             s = self.seqs.pop(sid, None)
             if s is None:
                 continue
-            if s.slot >= 0:
-                self.pools[s.rep].free([s.slot])
+            self._release_slot(s)
             ev.append((sid, -1, EV_RELEASE | (0 if s.finished else EV_FINISH)))
         return ev
 
@@ -605,8 +788,7 @@ class PySchedCore:
                 continue
             if not s.finished:
                 done.append((sid, list(s.toks)))
-            if s.slot >= 0:
-                self.pools[s.rep].free([s.slot])
+            self._release_slot(s)
             ev.append((sid, -1, EV_RELEASE | (0 if s.finished else EV_FINISH)))
         return ev, done
 
@@ -615,6 +797,8 @@ class PySchedCore:
         if s is None or s.finished or s.ntok >= s.want:
             return
         flags = EV_FIRST if s.ntok == 0 else 0
+        if flags:
+            self._unpin(s)
         s.ntok += 1
         s.toks.append(tok)
         hit = s.stops is not None and self._stop_match(s, tok)
@@ -635,6 +819,8 @@ class PySchedCore:
         if s is None or s.finished or s.ntok >= s.want:
             return
         flags = EV_FIRST if s.ntok == 0 else 0
+        if flags:
+            self._unpin(s)
         s.ntok += 1
         hit = s.stops is not None and self._stop_match(s, tok)
         if s.stop_at_eos and tok == eos:
@@ -651,10 +837,14 @@ class PySchedCore:
         for s in self.seqs.values():
             if s.slot >= 0:
                 self.pools[s.rep].free([s.slot])
+        for rep, c in enumerate(self.caches):  # every entry, the pinned ones too: their sequences are gone
+            self.pools[rep].free(list(c.entries))
+        self.caches = [_Cache() for _ in range(self.R)]
         self.seqs.clear()
         self.waiting.clear()
         self.expect.clear()
         self._forks = []
+        self._hits = []
         self.groups = [[_Group() for _ in range(self.M)] for _ in range(self.R)]
 
 
@@ -724,6 +914,15 @@ class Scheduler(racecheck.Shared):
         self._badwords = 0  # live requests with bad_words, likewise
         self._guided = 0  # live requests that follow a guide, likewise
         self._forking = 0  # forks whose chunk is not planned yet: build_step asks the core for forks() only then
+        # the prefix cache (EngineConfig.prefix_cache entries per replica): on, every
+        # step asks the core for forks() and hits(), and opted-in requests hand
+        # it their prompts.  A request that reads its prompt on the last stage
+        # (repetition_penalty, no_repeat_ngram_size, bad_words) never starts
+        # from an entry -- DrawStage clones a source slot's prompt ids only for
+        # family forks, an entry's row is not kept valid -- but leaves one
+        self._caching = engine.cfg.prefix_cache > 0
+        if self._caching:
+            self.core.set_prefix_cache(engine.cfg.prefix_cache, engine.cfg.prefix_cache_min_tokens)
 
     # -- admission ---------------------------------------------------------
     def submit(self, prompt_ids: List[int], params: SamplingParams, guide_row: int = -1) -> Request:
@@ -838,6 +1037,11 @@ class Scheduler(racecheck.Shared):
             self.core.add_fork(*f)
         # those with a KV copy ahead: a one-token prompt's samples are plain sequences
         self._forking += sum(1 for f in forks if len(meta[f[0]].req.prompt_ids) > 1)
+        if self._caching:  # the prompts of the requests that did not opt out (their forks share them)
+            for i, req in zip(ids, reqs):
+                p = req.params
+                if p.prefix_cache:
+                    self.core.set_prompt(i, req.prompt_ids, meta[i].context is None and meta[i].bad is None)
         for i, p in asking:  # the requests with stop sequences alone: the core matches their last tokens
             st = meta[i].stops = p.stop_list()
             self.core.set_stops(i, [t for w in st for t in w], [len(w) for w in st], p.min_new_tokens)
@@ -863,7 +1067,12 @@ class Scheduler(racecheck.Shared):
             for sid in admitted:
                 self.meta[sid].req.t_start = now
         # (fork sid -> source slot) of this step's fork chunks
-        fk = dict(self.core.forks()) if self._forking else None
+        fk = dict(self.core.forks()) if self._forking or self._caching else None
+        if self._caching and fk:
+            # the prefix-cache hits among them: no family fork, and the request learns its m
+            for sid, m in self.core.hits():
+                self.meta[sid].req.cached_tokens = m
+                self._forking += 1  # _group counts every chunk it finds in fk down
         plans = [StepPlan(step=s, groups=[self._group(go, rep, fk) for go in gos], replica=rep,
                           timing=self.timing) for rep, gos in enumerate(per_rep)]
         c = self.core

@@ -18,7 +18,7 @@ Additions: optional sampling fields on /generate (temperature, top_k, top_p,
 min_p, presence_penalty, frequency_penalty, logprobs, logit_bias, banned_token_ids,
 min_new_tokens, repetition_penalty, no_repeat_ngram_size, allowed_token_ids, bad_words,
 bad_words_ids, stop, stop_token_ids, include_stop_in_output, guided_regex, guided_choice,
-greedy, seed, stop_at_eos;
+greedy, seed, stop_at_eos, prefix_cache;
 defaults = reference sampler; with logprobs the response gains a "logprobs" object
 beside "generated"; with stop / stop_token_ids it gains "finish_reason" and, after
 a stop, "stop_reason"; a stop string is tokenised with the server's tokenizer as
@@ -38,7 +38,7 @@ import time
 from typing import Dict, List, Optional, Union
 
 import torch
-from pydantic import BaseModel
+from pydantic import BaseModel, StrictBool
 
 from ..config import EngineConfig, SamplingParams
 from ..utils import racecheck
@@ -101,6 +101,10 @@ class GenerateReq(BaseModel):
     # sample i draws with seed + i; with n > 1 the response keeps "generated" for sample 0
     # and adds "choices", one object per sample
     n: int = 1
+    # false: the request neither starts from the engine's prefix cache (PREFIX_CACHE entries)
+    # nor leaves an entry behind; a JSON bool.  While the cache is on the response gains
+    # "cached_tokens", the leading prompt tokens whose prefill an entry's KV replaced
+    prefix_cache: StrictBool = True
 
 
 class GuideCache:
@@ -272,7 +276,8 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                             no_repeat_ngram_size=req.no_repeat_ngram_size,
                             allowed_token_ids=req.allowed_token_ids, bad_words=bad,
                             stop_token_ids=req.stop_token_ids, stop_sequences=stops,
-                            include_stop_in_output=req.include_stop_in_output, guide=guide, n=req.n)
+                            include_stop_in_output=req.include_stop_in_output, guide=guide, n=req.n,
+                            prefix_cache=req.prefix_cache)
         if req.max_new_tokens == 0 and req.logprobs is None and req.n == 1:
             return {"generated": tok.decode(ids, skip_special_tokens=True)}
         if not ids:
@@ -282,6 +287,7 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
 
         lp = None
         reason = ("length", None)
+        cached = 0  # Request.cached_tokens
         each = None  # n > 1: (tokens, logprob records, reasons) of every sample
         try:
             sp.validate(cfg.max_logprobs, cfg.max_logit_edits, cfg.max_bad_words, cfg.max_bad_word_tokens,
@@ -300,8 +306,8 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                                      f"exceeds the context limit {engine.max_seq}")
                 req_ = engine.submit(ids, sp)
                 out = req_.wait(timeout=cfg.request_timeout_s)
-                lp, reason = req_.logprobs, (req_.finish_reason, req_.stop_reason)
-                each = [(s.wait(0), s.logprobs, (s.finish_reason, s.stop_reason)) for s in req_.samples]
+                lp, reason, cached = req_.logprobs, (req_.finish_reason, req_.stop_reason), req_.cached_tokens
+                each =[(s.wait(0), s.logprobs, (s.finish_reason, s.stop_reason)) for s in req_.samples]
                 metrics.observe_request(sum(len(e[0]) for e in each), time.perf_counter() - t0,
                                         ttft_s=(req_.t_first - req_.t_submit) if req_.t_first else None)
             else:
@@ -336,6 +342,8 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         body = sample_json(out, lp, reason)
         if sp.n > 1:
             body["choices"] = [sample_json(*e) for e in each]
+        if engine is not None and engine.cfg.prefix_cache > 0:
+            body["cached_tokens"] = cached
         return body
 
     @app.get("/health")
@@ -345,6 +353,8 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         if engine is not None:
             body.update(stages=engine.P, plan=engine.plan, unit_plan=engine.unit_plan, mode=engine.mode,
                         devices=[str(d) for d in engine.devices], **engine.kv_info())
+            if engine.cfg.prefix_cache > 0:
+                body["prefix_cache"] = engine.prefix_cache_stats()
             if not ok:
                 body["error"] = engine.last_error
         if shard is not None:
@@ -369,6 +379,12 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                         "sequence_joins_total": sch.stats["joins"],
                         "sequence_leaves_total": sch.stats["leaves"],
                         "hipgraph_captures_total": sum(w.captures for w in engine.workers)}
+            if engine.cfg.prefix_cache > 0:
+                pc = engine.prefix_cache_stats()
+                gauges["prefix_cache_entries"] = pc["entries"]
+                counters.update(prefix_cache_hits_total=pc["hits"], prefix_cache_misses_total=pc["misses"],
+                                prefix_cache_tokens_reused_total=pc["tokens_reused"],
+                                prefix_cache_evictions_total=pc["evictions"])
             ls = engine.last_session
             if ls is not None:
                 if ls.step_times_ms:
