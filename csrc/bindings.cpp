@@ -57,11 +57,11 @@ hipError_t lsd_norm(float* x, const void* slab, int slab_bf16, int splits, const
 hipError_t lsd_attn_decode(const bf16* q, long ldq, const bf16* kc, const bf16* vc,
                            const int* seq_slots, const int* qpos, bf16* out, long ldo,
                            float* part_o, float* part_ml, int B, int nh, int n_kv, int hd,
-                           int max_seq, int splits, float scale_log2, hipStream_t st);
+                           int max_seq, int splits, float scale_log2, int kv_elt, hipStream_t st);
 hipError_t lsd_attn_prefill(const bf16* q, long ldq, const bf16* kc, const bf16* vc,
                             const int* tiles, int n_tiles, const int* seq_slots,
                             const int* q_start, const int* cu_q, bf16* out, long ldo, int nh,
-                            int n_kv, int hd, int max_seq, float scale_log2, hipStream_t st);
+                            int n_kv, int hd, int max_seq, float scale_log2, int kv_elt, hipStream_t st);
 hipError_t lsd_attn_oproj(const bf16* q, long ldq, const bf16* kc, const bf16* vc,
                           const int* seq_slots, const int* qpos, int B, int nh, int n_kv, int hd,
                           int max_seq, float scale_log2, const bf16* W, long ldw, const bf16* bias,
@@ -73,7 +73,7 @@ hipError_t lsd_apply_rows(const int64_t* args, int nargs, int b, hipStream_t st)
 hipError_t lsd_silu_mul(const lsd_bf16_t* y, long ldy, lsd_bf16_t* out, long ldo, int M, int F, hipStream_t st);
 hipError_t lsd_qkv_post(const float* y, long ldy, const lsd_bf16_t* bias, const int* tslot, const int* tpos,
                         const float* rope, lsd_bf16_t* q, lsd_bf16_t* kc, lsd_bf16_t* vc, int M, int q_size,
-                        int kv_size, int hd, int n_kv, int max_seq, hipStream_t st);
+                        int kv_size, int hd, int n_kv, int max_seq, int kv_fp8, hipStream_t st);
 hipError_t lsd_sample(const float* logits, long ld, int B, int V, const float* temp,
                       const int* topk, const int* greedy, const long long* seeds,
                       long long* step, int* out, int advance, const int* active, int* pos,
@@ -123,6 +123,17 @@ void check_hip(hipError_t e, const char* what) {
 void need(const torch::Tensor& t, c10::ScalarType dt, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
   TORCH_CHECK(t.scalar_type() == dt, name, " has dtype ", t.scalar_type(), ", expected ", dt);
+}
+
+// KV caches are bf16 or FP8 E4M3 (one byte per element; the kernels take the
+// element type from here), K and V alike.  Returns 1 for FP8.
+int need_kv(const torch::Tensor& kc, const torch::Tensor& vc) {
+  TORCH_CHECK(kc.is_cuda() && vc.is_cuda(), "k_cache / v_cache must be GPU tensors");
+  const auto dt = kc.scalar_type();
+  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kFloat8_e4m3fn, "k_cache has dtype ", dt,
+              ", expected BFloat16 or Float8_e4m3fn");
+  TORCH_CHECK(vc.scalar_type() == dt, "v_cache has dtype ", vc.scalar_type(), ", k_cache has ", dt);
+  return dt == torch::kFloat8_e4m3fn ? 1 : 0;
 }
 
 long long* g_stamps = nullptr;  // diagnostic phase stamps (tools/microbench.py "stamps")
@@ -301,8 +312,7 @@ torch::Tensor linear_qkv(torch::Tensor a, torch::Tensor w, c10::optional<torch::
                          c10::optional<torch::Tensor> counters) {
   GemmParams p = base_params(a, w, tiled);
   p.bias = opt_bias(bias, p.N);
-  need(kc, torch::kBFloat16, "k_cache");
-  need(vc, torch::kBFloat16, "v_cache");
+  p.kv_fp8 = need_kv(kc, vc);
   TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.sizes() == kc.sizes() && vc.is_contiguous(),
               "caches must be contiguous [slots, n_kv, max_seq, hd]");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(kc.data_ptr()) % 16 == 0 &&
@@ -407,8 +417,7 @@ c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optiona
   } else if (epi == EPI_QKV) {
     TORCH_CHECK(kc.has_value() && vc.has_value() && tslot.has_value() && tpos.has_value(),
                 "qkv needs caches and token slots/positions");
-    need(*kc, torch::kBFloat16, "k_cache");
-    need(*vc, torch::kBFloat16, "v_cache");
+    p.kv_fp8 = need_kv(*kc, *vc);
     TORCH_CHECK(kc->dim() == 4 && kc->is_contiguous() && vc->sizes() == kc->sizes() && vc->is_contiguous(),
                 "caches must be contiguous [slots, n_kv, max_seq, hd]");
     TORCH_CHECK(kc->size(3) == hd && kc->size(1) * hd == kv_size, "cache shape mismatch");
@@ -515,13 +524,13 @@ c10::optional<torch::Tensor> norm(torch::Tensor x, c10::optional<torch::Tensor> 
   return out;
 }
 
-void check_cache(const torch::Tensor& kc, const torch::Tensor& vc) {
-  need(kc, torch::kBFloat16, "k_cache");
-  need(vc, torch::kBFloat16, "v_cache");
+int check_cache(const torch::Tensor& kc, const torch::Tensor& vc) {
+  const int fp8 = need_kv(kc, vc);
   TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() && kc.sizes() == vc.sizes(),
               "caches must be contiguous [slots, n_kv, max_seq, hd]");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(kc.data_ptr()) % 16 == 0 &&
               reinterpret_cast<uintptr_t>(vc.data_ptr()) % 16 == 0, "caches must be 16-byte aligned");
+  return fp8;
 }
 
 torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
@@ -529,7 +538,7 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
                           int64_t splits) {
   need(q, torch::kBFloat16, "q");
   need_rows(q, "q");
-  check_cache(kc, vc);
+  const int kv_elt = check_cache(kc, vc) ? 1 : 2;
   const int B = q.size(0), n_kv = kc.size(1), hd = kc.size(3);
   TORCH_CHECK(q.size(1) == nh * hd && nh % n_kv == 0, "q must be [B, nh*hd]");
   TORCH_CHECK(hd == 64 || hd == 128, "head_dim must be 64 or 128");
@@ -550,7 +559,7 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
   const float sl2 = 1.4426950408889634f / std::sqrt((float)hd);
   check_hip(lsd_attn_decode(bptr(q), q.stride(0), bptr(kc), bptr(vc), seq_slots.data_ptr<int>(),
                             qpos.data_ptr<int>(), bptr_mut(out), out.stride(0), pop, pmlp, B, nh,
-                            n_kv, hd, kc.size(2), splits, sl2, cur_stream()), "attn_decode");
+                            n_kv, hd, kc.size(2), splits, sl2, kv_elt, cur_stream()), "attn_decode");
   return out;
 }
 
@@ -561,7 +570,7 @@ void attn_oproj(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tens
                 torch::Tensor x, int64_t nc, torch::Tensor counters) {
   need(q, torch::kBFloat16, "q");
   need_rows(q, "q");
-  check_cache(kc, vc);
+  TORCH_CHECK(check_cache(kc, vc) == 0, "attn_oproj: bf16 caches only");
   const int B = q.size(0), n_kv = kc.size(1), hd = kc.size(3);
   TORCH_CHECK(B >= 1 && B <= 4, "attn_oproj: 1 <= B <= 4 rows, got ", B);
   TORCH_CHECK(q.size(1) == nh * hd && nh % n_kv == 0, "q must be [B, nh*hd]");
@@ -596,7 +605,7 @@ torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
                            torch::Tensor cu_q, int64_t nh) {
   need(q, torch::kBFloat16, "q");
   need_rows(q, "q");
-  check_cache(kc, vc);
+  const int kv_elt = check_cache(kc, vc) ? 1 : 2;
   const int n_kv = kc.size(1), hd = kc.size(3);
   TORCH_CHECK(q.size(1) == nh * hd && nh % n_kv == 0, "q must be [T, nh*hd]");
   TORCH_CHECK(hd == 64 || hd == 128, "head_dim must be 64 or 128");
@@ -611,7 +620,7 @@ torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
   check_hip(lsd_attn_prefill(bptr(q), q.stride(0), bptr(kc), bptr(vc), tiles.data_ptr<int>(),
                              tiles.size(0), seq_slots.data_ptr<int>(), q_start.data_ptr<int>(),
                              cu_q.data_ptr<int>(), bptr_mut(out), out.stride(0), nh, n_kv, hd,
-                             kc.size(2), sl2, cur_stream()), "attn_prefill");
+                             kc.size(2), sl2, kv_elt, cur_stream()), "attn_prefill");
   return out;
 }
 
@@ -692,8 +701,7 @@ torch::Tensor qkv_post(torch::Tensor y, c10::optional<torch::Tensor> bias, torch
   TORCH_CHECK(N == q_size + 2 * kv_size && hd % 8 == 0 && q_size % hd == 0 && kv_size % hd == 0,
               "qkv_post: N must be q_size + 2 kv_size, head dims multiples of 8");
   const lsd_bf16_t* b = opt_bias(bias, N);
-  need(kc, torch::kBFloat16, "k_cache");
-  need(vc, torch::kBFloat16, "v_cache");
+  const int kv_fp8 = need_kv(kc, vc);
   TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.sizes() == kc.sizes() && vc.is_contiguous(),
               "caches must be contiguous [slots, n_kv, max_seq, hd]");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(kc.data_ptr()) % 16 == 0 &&
@@ -713,7 +721,7 @@ torch::Tensor qkv_post(torch::Tensor y, c10::optional<torch::Tensor> bias, torch
   auto q = torch::empty({M, q_size}, y.options().dtype(torch::kBFloat16));
   check_hip(lsd_qkv_post(y.data_ptr<float>(), y.stride(0), b, tslot.data_ptr<int>(), tpos.data_ptr<int>(), rp,
                          reinterpret_cast<lsd_bf16_t*>(q.data_ptr()), bptr_mut(kc), bptr_mut(vc), (int)M,
-                         (int)q_size, (int)kv_size, (int)hd, (int)kc.size(1), (int)kc.size(2), cur_stream()),
+                         (int)q_size, (int)kv_size, (int)hd, (int)kc.size(1), (int)kc.size(2), kv_fp8, cur_stream()),
             "qkv_post");
   return q;
 }

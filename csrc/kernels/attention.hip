@@ -5,7 +5,7 @@
 // over the whole sequence every step and gets causality only implicitly
 // (quirk Q3); here the mask is explicit and K/V come from the cache.
 //
-// Cache layout [slot][kv_head][position][hd] (bf16): one (slot, head) is a
+// Cache layout [slot][kv_head][position][hd] (bf16, or FP8 E4M3 bytes): one (slot, head) is a
 // contiguous run of positions, so every key/value row read is part of one
 // linear stream.
 //
@@ -196,6 +196,221 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_kernel(
       }
     }
     __syncthreads();  // sm is reused by this block's next item
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Decode over an FP8 (E4M3) KV cache: one byte per element, no scales
+// ---------------------------------------------------------------------------
+// The bf16 kernel above runs at the HBM roofline, so the only way down is
+// fewer bytes.  The lane map here is built for bytes: a lane's 16-byte load is
+// EPL = 16 ELEMENTS of a key row, so a row takes LPK = HD/16 lanes (4 at HD 64,
+// 8 at HD 128), a wave-instruction still streams 1 KiB of contiguous K (KPI =
+// 16 / 8 keys), every byte costs half the load instructions, and a score is
+// reduced in log2(LPK) exchanges.  The 16 bytes are dequantised by eight packed
+// converts (v_cvt_pk_f32_fp8, both halves of each dword through the word-select
+// operand) whose results feed the FMA chains directly -- exact, so the math sees
+// what a reference over the dequantised cache sees.  qf[G][EPL] and o[G][EPL]
+// stay in registers; G >= 4 takes EPL = 8 (8-byte loads, the bf16 kernel's lane
+// map): 2 x G x 16 floats would halve the occupancy.  Wave merge, LDS merge and
+// split outputs are attn_decode_kernel's.  NWV = 4 requests V after the scores,
+// NWV = 8 (small grids) together with K.
+template <int EPL>
+struct Fp8Row {
+  unsigned w[EPL / 4];
+};
+template <int EPL>
+__device__ __forceinline__ Fp8Row<EPL> ld_fp8_row(const unsigned char* p) {
+  Fp8Row<EPL> r;
+  if constexpr (EPL == 16) {
+#ifdef LSD_KV_TEMPORAL
+    const u32x4 v = *reinterpret_cast<const u32x4*>(p);
+#else
+    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+#endif
+    r.w[0] = v[0]; r.w[1] = v[1]; r.w[2] = v[2]; r.w[3] = v[3];
+  } else {
+#ifdef LSD_KV_TEMPORAL
+    const u32x2 v = *reinterpret_cast<const u32x2*>(p);
+#else
+    const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+#endif
+    r.w[0] = v[0]; r.w[1] = v[1];
+  }
+  return r;
+}
+template <int EPL>
+__device__ __forceinline__ void fp8_row_f32(const Fp8Row<EPL>& r, float (&f)[EPL]) {
+#pragma unroll
+  for (int i = 0; i < EPL / 4; ++i) {
+    const f32x2 lo = fp8_dec2<false>(r.w[i]), hi = fp8_dec2<true>(r.w[i]);
+    f[4 * i] = lo[0]; f[4 * i + 1] = lo[1]; f[4 * i + 2] = hi[0]; f[4 * i + 3] = hi[1];
+  }
+}
+
+template <int HD, int G, int EPL, int U, int NWV>
+__global__ LSD_NO_PK_F32 __launch_bounds__(NWV * 64) void attn_decode_fp8_kernel(
+    const bf16* __restrict__ q, long ldq, const unsigned char* __restrict__ kc,
+    const unsigned char* __restrict__ vc, const int* __restrict__ seq_slots,
+    const int* __restrict__ qpos, bf16* out, long ldo, float* part_o, float* part_ml, int n_kv,
+    int max_seq, int splits, float scale_log2, int n_items) {
+  static_assert(EPL == 8 || EPL == 16, "a lane loads 8 or 16 bytes of a row");
+  constexpr int LPK = HD / EPL;  // lanes per key row
+  constexpr int KPI = 64 / LPK;  // keys per wave-instruction
+  __shared__ float sm[NWV][G][LPK][EPL + 2];
+  for (int item = blockIdx.x; item < n_items; item += gridDim.x) {  // capped grid: lsd_attn_set_max_wg
+    const int b = item / n_kv, kvh = item % n_kv, split = blockIdx.y;
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const int ds = lane % LPK, kg = lane / LPK;
+    const int ctx = qpos[b] + 1;
+    const int per = (ctx + splits - 1) / splits;
+    const int k_lo = split * per, k_hi = min(ctx, k_lo + per);
+    const long base = ((long)seq_slots[b] * n_kv + kvh) * (long)max_seq * HD + ds * EPL;  // bytes
+
+    float qf[G][EPL];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int c = 0; c < EPL / 8; ++c) {
+        const bf16x8 qq = ld8(q + (long)b * ldq + (long)(kvh * G + g) * HD + ds * EPL + c * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[g][c * 8 + j] = bf2f(qq[j]) * scale_log2;
+      }
+    float m[G], l[G], o[G][EPL];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      m[g] = NEG;
+      l[g] = 0.f;
+#pragma unroll
+      for (int j = 0; j < EPL; ++j) o[g][j] = 0.f;
+    }
+
+    for (int c0 = k_lo + w * KPI; c0 < k_hi; c0 += NWV * KPI * U) {
+      Fp8Row<EPL> kv[U], vv[U];
+      int key[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        key[u] = c0 + u * NWV * KPI + kg;
+        kv[u] = ld_fp8_row<EPL>(kc + base + (long)min(key[u], k_hi - 1) * HD);
+      }
+      if constexpr (NWV > 4) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) vv[u] = ld_fp8_row<EPL>(vc + base + (long)min(key[u], k_hi - 1) * HD);
+      }
+      float s[G][U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        float kf[EPL];  // dequantised once, used by the G query heads
+        fp8_row_f32<EPL>(kv[u], kf);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          float acc = 0.f;
+#pragma unroll
+          for (int j = 0; j < EPL; ++j) acc += qf[g][j] * kf[j];
+#pragma unroll
+          for (int msk = 1; msk < LPK; msk <<= 1) acc += wave_xchg_n(acc, msk);
+          s[g][u] = key[u] < k_hi ? acc : NEG;
+        }
+      }
+      if constexpr (NWV <= 4) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) vv[u] = ld_fp8_row<EPL>(vc + base + (long)min(key[u], k_hi - 1) * HD);
+      }
+      float p[G][U];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float mx = s[g][0];
+#pragma unroll
+        for (int u = 1; u < U; ++u) mx = fmaxf(mx, s[g][u]);
+        const float mn = fmaxf(m[g], mx);
+        const float alpha = exp2f(m[g] - mn);
+        float ps = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          p[g][u] = exp2f(s[g][u] - mn);
+          ps += p[g][u];
+        }
+        l[g] = l[g] * alpha + ps;
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) o[g][j] *= alpha;
+        m[g] = mn;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        float vf[EPL];
+        fp8_row_f32<EPL>(vv[u], vf);
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+          for (int j = 0; j < EPL; ++j) o[g][j] += p[g][u] * vf[j];
+      }
+    }
+
+    // merge the key groups of this wave (lanes with equal ds: exact xor partners)
+#pragma unroll
+    for (int msk = LPK; msk < 64; msk <<= 1) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const float mo = wave_xor_n(m[g], msk), lo = wave_xor_n(l[g], msk);
+        const float mn = fmaxf(m[g], mo);
+        const float a = exp2f(m[g] - mn), bb = exp2f(mo - mn);
+        l[g] = l[g] * a + lo * bb;
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) o[g][j] = o[g][j] * a + wave_xor_n(o[g][j], msk) * bb;
+        m[g] = mn;
+      }
+    }
+    // merge the waves through LDS
+    if (kg == 0) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        sm[w][g][ds][0] = m[g];
+        sm[w][g][ds][1] = l[g];
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) sm[w][g][ds][2 + j] = o[g][j];
+      }
+    }
+    block_sync();
+    if (w == 0 && kg == 0) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float mm = NEG;
+#pragma unroll
+        for (int ww = 0; ww < NWV; ++ww) mm = fmaxf(mm, sm[ww][g][ds][0]);
+        float ll = 0.f, oo[EPL];
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) oo[j] = 0.f;
+#pragma unroll
+        for (int ww = 0; ww < NWV; ++ww) {
+          const float f = exp2f(sm[ww][g][ds][0] - mm);
+          ll += sm[ww][g][ds][1] * f;
+#pragma unroll
+          for (int j = 0; j < EPL; ++j) oo[j] += sm[ww][g][ds][2 + j] * f;
+        }
+        const int h = kvh * G + g;
+        if (splits == 1) {
+          const float inv = ll > 0.f ? 1.f / ll : 0.f;
+#pragma unroll
+          for (int c = 0; c < EPL / 8; ++c) {
+            bf16x8 r;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] = f2bf(oo[c * 8 + j] * inv);
+            st8(out + (long)b * ldo + (long)h * HD + ds * EPL + c * 8, r);
+          }
+        } else {
+          const int nh = n_kv * G;
+          const long pi = ((long)b * nh + h) * splits + split;
+          float* po = part_o + pi * HD + ds * EPL;
+#pragma unroll
+          for (int j = 0; j < EPL; ++j) po[j] = oo[j];
+          if (ds == 0) {
+            part_ml[pi * 2] = mm;
+            part_ml[pi * 2 + 1] = ll;
+          }
+        }
+      }
+    }
+    block_sync();  // sm is reused by this block's next item
   }
 }
 
@@ -426,8 +641,27 @@ __device__ __forceinline__ bf16x4 ds_read_tr(const bf16* lds_ptr) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(lds_ptr));
 }
 
-template <int HD>
-__global__ __launch_bounds__(256) void attn_prefill_kernel(
+// The cache element is a template parameter of the body: the FP8 (E4M3)
+// instance (attn_prefill_fp8_kernel) loads a chunk's 8 elements as 8 bytes and
+// dequantises them (exactly) at the st8 into ks / vs; everything behind the
+// barrier is shared.
+template <bool FP8>
+struct KvChunk8 {
+  typedef bf16x8 T;
+  static __device__ __forceinline__ T ld(const bf16* c, long off) { return ld8(c + off); }
+  static __device__ __forceinline__ bf16x8 bf(T v) { return v; }
+};
+template <>
+struct KvChunk8<true> {
+  typedef u32x2 T;
+  static __device__ __forceinline__ T ld(const bf16* c, long off) {
+    return *reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned char*>(c) + off);
+  }
+  static __device__ __forceinline__ bf16x8 bf(T v) { return fp8x8_to_bf16(v); }
+};
+
+template <int HD, bool FP8>
+__device__ __forceinline__ void attn_prefill_body(
     const bf16* __restrict__ q, long ldq, const bf16* __restrict__ kc,
     const bf16* __restrict__ vc, const int* __restrict__ tiles,
     const int* __restrict__ seq_slots, const int* __restrict__ q_start,
@@ -435,7 +669,7 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(
     float scale_log2) {
   constexpr int KT = 64;              // keys per tile
   constexpr int LDR = HD + 8;         // padded LDS row (elements): +16 B
-  constexpr int CPR = HD / 8;         // 16-B chunks per row
+  constexpr int CPR = HD / 8;         // 8-element chunks per row (16 B of bf16, 8 B of FP8)
   constexpr int CH = KT * CPR / 256;  // chunks per thread per tile
   __shared__ __attribute__((aligned(16))) bf16 ks[KT * LDR];
   __shared__ __attribute__((aligned(16))) bf16 vs[KT * LDR];
@@ -463,15 +697,16 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(
   for (int di = 0; di < HD / 16; ++di) o[di] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = NEG, lsum = 0.f;
 
-  bf16x8 kreg[CH], vreg[CH];
-  auto load_tile = [&](int kt) {
+  typedef KvChunk8<FP8> KV;  // base / off count elements: bytes of an FP8 cache
+  typename KV::T kreg[CH], vreg[CH];
+  auto load_tile = [&](int kt) __attribute__((always_inline)) {  // also into the FP8 kernel's other target features
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       const int idx = threadIdx.x + c * 256;
       const int key = min(kt * KT + idx / CPR, kmax - 1);
       const long off = base + (long)key * HD + (idx % CPR) * 8;
-      kreg[c] = ld8(kc + off);
-      vreg[c] = ld8(vc + off);
+      kreg[c] = KV::ld(kc, off);
+      vreg[c] = KV::ld(vc, off);
     }
   };
   load_tile(0);
@@ -479,10 +714,10 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       const int idx = threadIdx.x + c * 256;
-      st8(ks + (idx / CPR) * LDR + (idx % CPR) * 8, kreg[c]);
-      st8(vs + (idx / CPR) * LDR + (idx % CPR) * 8, vreg[c]);
+      st8(ks + (idx / CPR) * LDR + (idx % CPR) * 8, KV::bf(kreg[c]));
+      st8(vs + (idx / CPR) * LDR + (idx % CPR) * 8, KV::bf(vreg[c]));
     }
-    __syncthreads();
+    block_sync();
     if (kt + 1 < ntile) load_tile(kt + 1);  // in flight under this tile's math
 
     // S^T[key][q] for 4 subtiles of 16 keys
@@ -545,7 +780,7 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(
         o[di] = mfma16(vf, pf, o[di]);
       }
     }
-    __syncthreads();
+    block_sync();
   }
   lsum += wave_xchg<16>(lsum);
   lsum += wave_xchg<32>(lsum);
@@ -560,6 +795,27 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(
       st4(op + di * 16 + 4 * g, rr);
     }
   }
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void attn_prefill_kernel(
+    const bf16* __restrict__ q, long ldq, const bf16* __restrict__ kc,
+    const bf16* __restrict__ vc, const int* __restrict__ tiles,
+    const int* __restrict__ seq_slots, const int* __restrict__ q_start,
+    const int* __restrict__ cu_q, bf16* out, long ldo, int nh, int n_kv, int max_seq,
+    float scale_log2) {
+  attn_prefill_body<HD, false>(q, ldq, kc, vc, tiles, seq_slots, q_start, cu_q, out, ldo, nh, n_kv, max_seq,
+                               scale_log2);
+}
+template <int HD>
+__global__ LSD_NO_PK_F32 __launch_bounds__(256) void attn_prefill_fp8_kernel(
+    const bf16* __restrict__ q, long ldq, const bf16* __restrict__ kc,
+    const bf16* __restrict__ vc, const int* __restrict__ tiles,
+    const int* __restrict__ seq_slots, const int* __restrict__ q_start,
+    const int* __restrict__ cu_q, bf16* out, long ldo, int nh, int n_kv, int max_seq,
+    float scale_log2) {
+  attn_prefill_body<HD, true>(q, ldq, kc, vc, tiles, seq_slots, q_start, cu_q, out, ldo, nh, n_kv, max_seq,
+                              scale_log2);
 }
 
 // ---------------------------------------------------------------------------
@@ -579,6 +835,101 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(
 // then staged through this wave's own LDS region for the fragment reads.
 // Waves are independent: no block barrier.  The math is ~2% of the HBM time
 // of the KV stream, so the kernel runs at the KV roofline.
+
+// One 32-key tile of the MFMA decode kernels, from this wave's LDS image (ks,
+// vs: bf16 rows of LDR elements; key0 = the tile's first key): scores, online
+// softmax, O^T += V^T . P^T.
+template <int HD>
+__device__ __forceinline__ void mfma_decode_tile(const bf16* ks, const bf16* vs, const bf16x8 (&qf)[HD / 32],
+                                                 f32x4 (&o)[HD / 16], float& m, float& lsum, int key0, int k_hi,
+                                                 float scale_log2, int r, int g) {
+  constexpr int LDR = HD + 8;
+  f32x4 sacc[2];
+#pragma unroll
+  for (int ni = 0; ni < 2; ++ni) {
+    sacc[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < HD / 32; ++kk) {
+      const bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + (ni * 16 + r) * LDR + kk * 32 + g * 8);
+      sacc[ni] = mfma16(kf, qf[kk], sacc[ni]);
+    }
+  }
+  float tmax = NEG;
+#pragma unroll
+  for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int key = key0 + ni * 16 + 4 * g + i;
+      const float sv = key < k_hi ? sacc[ni][i] * scale_log2 : NEG;
+      sacc[ni][i] = sv;
+      tmax = fmaxf(tmax, sv);
+    }
+  tmax = fmaxf(tmax, wave_xchg<16>(tmax));
+  tmax = fmaxf(tmax, wave_xchg<32>(tmax));
+  const float mn = fmaxf(m, tmax);
+  const float alpha = exp2f(m - mn);
+  m = mn;
+  float ps = 0.f;
+#pragma unroll
+  for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float p = exp2f(sacc[ni][i] - mn);
+      sacc[ni][i] = p;
+      ps += p;
+    }
+  lsum = lsum * alpha + ps;
+#pragma unroll
+  for (int di = 0; di < HD / 16; ++di) o[di] *= alpha;
+  // O^T += V^T . P^T over the 32 keys: k-slot j of group g <-> key 4g + j
+  // (j < 4), 16 + 4g + (j - 4) (j >= 4)
+  bf16x8 pf;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    pf[j] = f2bf(sacc[0][j]);
+    pf[4 + j] = f2bf(sacc[1][j]);
+  }
+  const int r0 = 4 * g + (r >> 2);
+#pragma unroll
+  for (int di = 0; di < HD / 16; ++di) {
+    const int col = di * 16 + 4 * (r & 3);
+    const bf16x4 lo = ds_read_tr(vs + r0 * LDR + col);
+    const bf16x4 hi = ds_read_tr(vs + (r0 + 16) * LDR + col);
+    const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    o[di] = mfma16(vf, pf, o[di]);
+  }
+}
+
+// The wave's result: the unnormalised partial of split `split` for
+// attn_decode_combine_kernel (splits > 1), or the normalised bf16 rows.
+template <int HD, int G>
+__device__ __forceinline__ void mfma_decode_store(f32x4 (&o)[HD / 16], float m, float lsum, bf16* out, long ldo,
+                                                  float* part_o, float* part_ml, int b, int kvh, int n_kv, int splits,
+                                                  int split, int r, int g) {
+  lsum += wave_xchg<16>(lsum);
+  lsum += wave_xchg<32>(lsum);
+  if (r < G && splits > 1) {  // unnormalised partial for attn_decode_combine_kernel
+    const long pi = ((long)b * n_kv * G + kvh * G + r) * splits + split;
+    float* po = part_o + pi * HD;
+#pragma unroll
+    for (int di = 0; di < HD / 16; ++di) *reinterpret_cast<f32x4*>(po + di * 16 + 4 * g) = o[di];
+    if (g == 0) {
+      part_ml[pi * 2] = m;
+      part_ml[pi * 2 + 1] = lsum;
+    }
+  } else if (r < G) {
+    const float inv = lsum > 0.f ? 1.f / lsum : 0.f;
+    bf16* op = out + (long)b * ldo + (long)(kvh * G + r) * HD;
+#pragma unroll
+    for (int di = 0; di < HD / 16; ++di) {
+      bf16x4 rr;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) rr[i] = f2bf(o[di][i] * inv);
+      st4(op + di * 16 + 4 * g, rr);
+    }
+  }
+}
+
 template <int HD, int G>
 __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
     const bf16* __restrict__ q, long ldq, const bf16* __restrict__ kc, const bf16* __restrict__ vc,
@@ -642,83 +993,95 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
     __builtin_amdgcn_wave_barrier();
     if (t + 1 < ntile) load_tile(t + 1);  // in flight under this tile's math
 
-    f32x4 sacc[2];
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-      sacc[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < HD / 32; ++kk) {
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + (ni * 16 + r) * LDR + kk * 32 + g * 8);
-        sacc[ni] = mfma16(kf, qf[kk], sacc[ni]);
-      }
-    }
-    float tmax = NEG;
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int key = k_lo + t * KT + ni * 16 + 4 * g + i;
-        const float sv = key < k_hi ? sacc[ni][i] * scale_log2 : NEG;
-        sacc[ni][i] = sv;
-        tmax = fmaxf(tmax, sv);
-      }
-    tmax = fmaxf(tmax, wave_xchg<16>(tmax));
-    tmax = fmaxf(tmax, wave_xchg<32>(tmax));
-    const float mn = fmaxf(m, tmax);
-    const float alpha = exp2f(m - mn);
-    m = mn;
-    float ps = 0.f;
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float p = exp2f(sacc[ni][i] - mn);
-        sacc[ni][i] = p;
-        ps += p;
-      }
-    lsum = lsum * alpha + ps;
-#pragma unroll
-    for (int di = 0; di < HD / 16; ++di) o[di] *= alpha;
-    // O^T += V^T . P^T over the 32 keys: k-slot j of group g <-> key 4g + j
-    // (j < 4), 16 + 4g + (j - 4) (j >= 4)
-    bf16x8 pf;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      pf[j] = f2bf(sacc[0][j]);
-      pf[4 + j] = f2bf(sacc[1][j]);
-    }
-    const int r0 = 4 * g + (r >> 2);
-#pragma unroll
-    for (int di = 0; di < HD / 16; ++di) {
-      const int col = di * 16 + 4 * (r & 3);
-      const bf16x4 lo = ds_read_tr(vs + r0 * LDR + col);
-      const bf16x4 hi = ds_read_tr(vs + (r0 + 16) * LDR + col);
-      const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      o[di] = mfma16(vf, pf, o[di]);
-    }
+    mfma_decode_tile<HD>(ks, vs, qf, o, m, lsum, k_lo + t * KT, k_hi, scale_log2, r, g);
   }
-  lsum += wave_xchg<16>(lsum);
-  lsum += wave_xchg<32>(lsum);
-  if (r < G && splits > 1) {  // unnormalised partial for attn_decode_combine_kernel
-    const long pi = ((long)b * n_kv * G + kvh * G + r) * splits + blockIdx.y;
-    float* po = part_o + pi * HD;
+  mfma_decode_store<HD, G>(o, m, lsum, out, ldo, part_o, part_ml, b, kvh, n_kv, splits, blockIdx.y, r, g);
+}
+
+// The same kernel over an FP8 (E4M3) cache.  Tiles stay 32 keys and the LDS
+// image stays bf16 with today's footprint (a 64-key tile would leave one block
+// per CU), so a tile is only CH = 4 16-byte loads per lane for K and 4 for V --
+// half the bf16 kernel's bytes in flight.  The prefetch is therefore TWO tiles
+// deep (register sets A and B, the bf16 kernel's 64 VGPRs): tile t + 2 is
+// requested when tile t leaves its registers.  The bytes are dequantised
+// (exactly) to bf16 at the register -> LDS store; fragment reads, ds_read_tr,
+// MFMAs and softmax are mfma_decode_tile's, unchanged.
+template <int HD, int G>
+__global__ LSD_NO_PK_F32 __launch_bounds__(256) void attn_decode_mfma_fp8_kernel(
+    const bf16* __restrict__ q, long ldq, const unsigned char* __restrict__ kc,
+    const unsigned char* __restrict__ vc, const int* __restrict__ seq_slots,
+    const int* __restrict__ qpos, bf16* out, long ldo, float* part_o, float* part_ml, int n_kv,
+    int max_seq, int splits, float scale_log2, int n_items) {
+  static_assert(G >= 1 && G <= 16, "G query heads per kv head fit one MFMA column tile");
+  constexpr int KT = 32;             // keys per tile
+  constexpr int LDR = HD + 8;        // padded LDS row (bf16 elements): +16 B
+  constexpr int CPR = HD / 16;       // 16-byte (16-element) chunks per key row
+  constexpr int CH = KT * CPR / 64;  // chunks per lane per tile (per K and per V)
+  __shared__ __attribute__((aligned(16))) bf16 lds[4][2][KT * LDR];
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const int item = blockIdx.x * 4 + w;
+  if (item >= n_items) return;  // waves are independent: no barriers below
+  bf16* ks = lds[w][0];
+  bf16* vs = lds[w][1];
+  const int b = item / n_kv, kvh = item % n_kv;
+  const int ctx = qpos[b] + 1;
+  const int per = (ctx + splits - 1) / splits;
+  const int k_lo = blockIdx.y * per, k_hi = min(ctx, k_lo + per);
+  const long base = ((long)seq_slots[b] * n_kv + kvh) * (long)max_seq * HD;  // bytes
+  const int r = lane & 15, g = lane >> 4;
+
+  bf16x8 qf[HD / 32];
 #pragma unroll
-    for (int di = 0; di < HD / 16; ++di) *reinterpret_cast<f32x4*>(po + di * 16 + 4 * g) = o[di];
-    if (g == 0) {
-      part_ml[pi * 2] = m;
-      part_ml[pi * 2 + 1] = lsum;
-    }
-  } else if (r < G) {
-    const float inv = lsum > 0.f ? 1.f / lsum : 0.f;
-    bf16* op = out + (long)b * ldo + (long)(kvh * G + r) * HD;
-#pragma unroll
-    for (int di = 0; di < HD / 16; ++di) {
-      bf16x4 rr;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rr[i] = f2bf(o[di][i] * inv);
-      st4(op + di * 16 + 4 * g, rr);
-    }
+  for (int kk = 0; kk < HD / 32; ++kk) {
+    bf16x8 z = {};
+    qf[kk] = r < G ? ld8(q + (long)b * ldq + (long)(kvh * G + r) * HD + kk * 32 + g * 8) : z;
   }
+  f32x4 o[HD / 16];
+#pragma unroll
+  for (int di = 0; di < HD / 16; ++di) o[di] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = NEG, lsum = 0.f;
+
+  const int ntile = k_hi > k_lo ? (k_hi - k_lo + KT - 1) / KT : 0;
+  Fp8Row<16> kA[CH], vA[CH], kB[CH], vB[CH];
+  // always_inline: this kernel's target features differ from the default, and
+  // the inliner would otherwise leave the lambdas as calls with arguments in scratch
+  auto load_tile = [&](int t, Fp8Row<16> (&kr)[CH], Fp8Row<16> (&vr)[CH]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int idx = lane + c * 64;
+      const int key = min(k_lo + t * KT + idx / CPR, k_hi - 1);
+      const long off = base + (long)key * HD + (idx % CPR) * 16;
+      kr[c] = ld_fp8_row<16>(kc + off);
+      vr[c] = ld_fp8_row<16>(vc + off);
+    }
+  };
+  // tile t: registers -> bf16 LDS image, request tile t + 2 into the freed set, math
+  auto step = [&](int t, Fp8Row<16> (&kr)[CH], Fp8Row<16> (&vr)[CH]) __attribute__((always_inline)) {
+    // the previous tile's fragment reads must be done before the overwrite
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int idx = lane + c * 64;
+      bf16* kd = ks + (idx / CPR) * LDR + (idx % CPR) * 16;
+      bf16* vd = vs + (idx / CPR) * LDR + (idx % CPR) * 16;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        st8(kd + 8 * h, fp8x8_to_bf16(u32x2{kr[c].w[2 * h], kr[c].w[2 * h + 1]}));
+        st8(vd + 8 * h, fp8x8_to_bf16(u32x2{vr[c].w[2 * h], vr[c].w[2 * h + 1]}));
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // this wave's LDS writes landed
+    __builtin_amdgcn_wave_barrier();
+    if (t + 2 < ntile) load_tile(t + 2, kr, vr);  // in flight under two tiles' math
+    mfma_decode_tile<HD>(ks, vs, qf, o, m, lsum, k_lo + t * KT, k_hi, scale_log2, r, g);
+  };
+  if (ntile > 0) load_tile(0, kA, vA);
+  if (ntile > 1) load_tile(1, kB, vB);
+  for (int t = 0; t < ntile; t += 2) {
+    step(t, kA, vA);
+    if (t + 1 < ntile) step(t + 1, kB, vB);
+  }
+  mfma_decode_store<HD, G>(o, m, lsum, out, ldo, part_o, part_ml, b, kvh, n_kv, splits, blockIdx.y, r, g);
 }
 
 }  // namespace lsd
@@ -759,12 +1122,69 @@ static hipError_t attn_decode_combine(const float* part_o, const float* part_ml,
   return hipGetLastError();
 }
 
+// Decode over an FP8 (E4M3) cache.  Routing is the bf16 path's pure functions
+// of shape: the MFMA threshold, and 8-wave blocks for grids of at most 128
+// workgroups; lsd_attn_set_max_wg is honoured, the waves-per-block A/B knobs
+// are not.  EPL: 16 elements per lane for G <= 2, 8 for G >= 4.
+static hipError_t attn_decode_fp8(const bf16* q, long ldq, const unsigned char* kc, const unsigned char* vc,
+                                  const int* seq_slots, const int* qpos, bf16* out, long ldo, float* part_o,
+                                  float* part_ml, int B, int nh, int n_kv, int hd, int max_seq, int splits,
+                                  float scale_log2, hipStream_t st) {
+  const int G = nh / n_kv;
+  const int n_items = B * n_kv;
+  const int gx = g_attn_max_wg > 0 ? (n_items < g_attn_max_wg ? n_items : g_attn_max_wg) : n_items;
+  if (g_attn_mfma_min > 0 && hd == 128 && g_attn_max_wg == 0 && (long)n_items * splits >= g_attn_mfma_min) {
+    const dim3 mgrid((n_items + 3) / 4, splits);
+#define LSD_DEC_MFMA8(GV)                                                                           \
+  if (G == GV) {                                                                                    \
+    hipLaunchKernelGGL((attn_decode_mfma_fp8_kernel<128, GV>), mgrid, dim3(256), 0, st, q, ldq, kc, \
+                       vc, seq_slots, qpos, out, ldo, part_o, part_ml, n_kv, max_seq, splits,       \
+                       scale_log2, n_items);                                                        \
+    return attn_decode_combine(part_o, part_ml, out, ldo, B, nh, hd, splits, st);                  \
+  }
+    LSD_DEC_MFMA8(2)
+    LSD_DEC_MFMA8(4)
+    LSD_DEC_MFMA8(8)
+#undef LSD_DEC_MFMA8
+  }
+  const bool wide = (long)gx * splits <= 128;  // small grids: 8 waves, V requested with K
+  const dim3 grid(gx, splits);
+#define LSD_DEC8(HDV, GV)                                                                            \
+  if (hd == HDV && G == GV) {                                                                        \
+    constexpr int EPL = GV <= 2 ? 16 : 8, U = GV <= 4 ? 4 : 2; /* G = 8 with U = 4 spills */         \
+    if (wide)                                                                                        \
+      hipLaunchKernelGGL((attn_decode_fp8_kernel<HDV, GV, EPL, U, 8>), grid, dim3(512), 0, st, q,    \
+                         ldq, kc, vc, seq_slots, qpos, out, ldo, part_o, part_ml, n_kv, max_seq,     \
+                         splits, scale_log2, n_items);                                               \
+    else                                                                                             \
+      hipLaunchKernelGGL((attn_decode_fp8_kernel<HDV, GV, EPL, U, 4>), grid, dim3(256), 0, st, q,    \
+                         ldq, kc, vc, seq_slots, qpos, out, ldo, part_o, part_ml, n_kv, max_seq,     \
+                         splits, scale_log2, n_items);                                               \
+    return attn_decode_combine(part_o, part_ml, out, ldo, B, nh, hd, splits, st);                   \
+  }
+  LSD_DEC8(64, 1)
+  LSD_DEC8(64, 2)
+  LSD_DEC8(64, 4)
+  LSD_DEC8(128, 1)
+  LSD_DEC8(128, 2)
+  LSD_DEC8(128, 4)
+  LSD_DEC8(128, 8)
+#undef LSD_DEC8
+  return hipErrorInvalidValue;
+}
+
+// kv_elt: bytes per cache element, 2 (bf16) or 1 (FP8 E4M3: kc / vc point at bytes)
 extern "C" hipError_t lsd_attn_decode(const bf16* q, long ldq, const bf16* kc, const bf16* vc,
                                       const int* seq_slots, const int* qpos, bf16* out, long ldo,
                                       float* part_o, float* part_ml, int B, int nh, int n_kv,
-                                      int hd, int max_seq, int splits, float scale_log2,
+                                      int hd, int max_seq, int splits, float scale_log2, int kv_elt,
                                       hipStream_t st) {
   if (B == 0) return hipSuccess;
+  if (kv_elt == 1)
+    return attn_decode_fp8(q, ldq, reinterpret_cast<const unsigned char*>(kc),
+                           reinterpret_cast<const unsigned char*>(vc), seq_slots, qpos, out, ldo, part_o,
+                           part_ml, B, nh, n_kv, hd, max_seq, splits, scale_log2, st);
+  if (kv_elt != 2) return hipErrorInvalidValue;
   const int G = nh / n_kv;
   const int n_items = B * n_kv;
   const int gx = g_attn_max_wg > 0 ? (n_items < g_attn_max_wg ? n_items : g_attn_max_wg) : n_items;
@@ -840,10 +1260,17 @@ extern "C" hipError_t lsd_attn_prefill(const bf16* q, long ldq, const bf16* kc, 
                                        const int* tiles, int n_tiles, const int* seq_slots,
                                        const int* q_start, const int* cu_q, bf16* out, long ldo,
                                        int nh, int n_kv, int hd, int max_seq, float scale_log2,
-                                       hipStream_t st) {
+                                       int kv_elt, hipStream_t st) {
   if (n_tiles == 0) return hipSuccess;
   dim3 grid(n_tiles, nh), block(256);
-  if (hd == 64)
+  if (kv_elt != 1 && kv_elt != 2) return hipErrorInvalidValue;
+  if (kv_elt == 1 && hd == 64)
+    hipLaunchKernelGGL((attn_prefill_fp8_kernel<64>), grid, block, 0, st, q, ldq, kc, vc, tiles,
+                       seq_slots, q_start, cu_q, out, ldo, nh, n_kv, max_seq, scale_log2);
+  else if (kv_elt == 1 && hd == 128)
+    hipLaunchKernelGGL((attn_prefill_fp8_kernel<128>), grid, block, 0, st, q, ldq, kc, vc, tiles,
+                       seq_slots, q_start, cu_q, out, ldo, nh, n_kv, max_seq, scale_log2);
+  else if (hd == 64)
     hipLaunchKernelGGL((attn_prefill_kernel<64>), grid, block, 0, st, q, ldq, kc, vc, tiles,
                        seq_slots, q_start, cu_q, out, ldo, nh, n_kv, max_seq, scale_log2);
   else if (hd == 128)

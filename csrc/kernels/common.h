@@ -49,6 +49,54 @@ __device__ __forceinline__ void st4(bf16* p, bf16x4 v) {
   *reinterpret_cast<u32x2*>(p) = __builtin_bit_cast(u32x2, v);
 }
 
+// ---- FP8 KV cache: OCP E4M3 (finite maximum 448, no infinities), no scales.
+// Encoding saturates: the fp32 value is clamped to [-448, 448] explicitly
+// (v_med3_f32; a NaN is passed around the clamp and stays NaN) and rounded to
+// nearest-even once by v_cvt_pk_fp8_f32.  Decoding (v_cvt_pk_f32_fp8) is
+// exact, and so is the bf16 of a decoded value (3 mantissa bits, exponents
+// inside bf16's).
+//
+// Kernels added with the FP8 cache are compiled without the packed fp32 VALU
+// forms (v_pk_fma_f32 and kin), per kernel, so the flags of the existing
+// kernels -- and their code -- stay as they are.
+#define LSD_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+// __syncthreads() for code those kernels share: HIP's own is a plain inline
+// function, which the inliner leaves as a call in a kernel whose target features
+// differ from its own.  The same three builtins, always inlined.
+__device__ __forceinline__ __attribute__((convergent)) void block_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+constexpr float FP8_MAX = 448.f;
+
+__device__ __forceinline__ float fp8_clamp(float x) {
+  return x != x ? x : __builtin_amdgcn_fmed3f(x, -FP8_MAX, FP8_MAX);
+}
+// four floats -> one dword of four E4M3 bytes (byte i = v[i])
+__device__ __forceinline__ unsigned fp8_pack4(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(a), fp8_clamp(b), 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(c), fp8_clamp(d), w, true);
+  return (unsigned)w;
+}
+__device__ __forceinline__ unsigned char fp8_enc(float a) {
+  return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(a), 0.f, 0, false) & 0xFF);
+}
+// bytes 2 HI, 2 HI + 1 of a dword -> two floats (the word-select operand)
+template <bool HI>
+__device__ __forceinline__ f32x2 fp8_dec2(unsigned w) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)w, HI); }
+// 8 E4M3 bytes -> 8 bf16 (exact)
+__device__ __forceinline__ bf16x8 fp8x8_to_bf16(u32x2 v) {
+  const f32x2 a = fp8_dec2<false>(v[0]), b = fp8_dec2<true>(v[0]);
+  const f32x2 c = fp8_dec2<false>(v[1]), d = fp8_dec2<true>(v[1]);
+  return bf16x8{f2bf(a[0]), f2bf(a[1]), f2bf(b[0]), f2bf(b[1]), f2bf(c[0]), f2bf(c[1]), f2bf(d[0]), f2bf(d[1])};
+}
+// 8 floats -> 8 E4M3 bytes
+__device__ __forceinline__ u32x2 fp8x8_from_f32(const float* y) {
+  return u32x2{fp8_pack4(y[0], y[1], y[2], y[3]), fp8_pack4(y[4], y[5], y[6], y[7])};
+}
+
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }

@@ -34,13 +34,13 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const bf16* __restrict__ 
 // rope_pair_permutation) with the (cos, sin) of the token's position; q ->
 // out bf16 [M, q_size]; k / v -> the caches at [slot][kv head][pos][d].  One
 // thread per 8 columns: two 16-byte fp32 loads, one 16-byte bf16 store (8
-// columns never straddle a head: hd % 8 == 0).
+// columns never straddle a head: hd % 8 == 0); 8 bytes into an FP8 cache.
 __global__ __launch_bounds__(256) void qkv_post_kernel(const float* __restrict__ y, long ldy,
                                                        const bf16* __restrict__ bias, const int* __restrict__ tslot,
                                                        const int* __restrict__ tpos, const float* __restrict__ rope,
                                                        bf16* __restrict__ q, bf16* __restrict__ kc,
                                                        bf16* __restrict__ vc, int M, int q_size, int kv_size, int hd,
-                                                       int n_kv, int max_seq) {
+                                                       int n_kv, int max_seq, int kv_fp8) {
   const int N = q_size + 2 * kv_size, per_row = N / 8;
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)M * per_row) return;
@@ -76,7 +76,11 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(const float* __restrict__
   } else {
     const int c = n < qk ? n - q_size : n - qk;
     bf16* cache = n < qk ? kc : vc;
-    st8(cache + (((long)tslot[m] * n_kv + c / hd) * max_seq + pos) * hd + c % hd, r);
+    const long idx = (((long)tslot[m] * n_kv + c / hd) * max_seq + pos) * hd + c % hd;
+    if (kv_fp8)  // FP8 E4M3 caches (byte pointers): one 8-byte store, encoded from the fp32 values
+      *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned char*>(cache) + idx) = fp8x8_from_f32(v);
+    else
+      st8(cache + idx, r);
   }
 }
 
@@ -95,12 +99,12 @@ extern "C" hipError_t lsd_silu_mul(const bf16* y, long ldy, bf16* out, long ldo,
 
 extern "C" hipError_t lsd_qkv_post(const float* y, long ldy, const bf16* bias, const int* tslot, const int* tpos,
                                    const float* rope, bf16* q, bf16* kc, bf16* vc, int M, int q_size, int kv_size,
-                                   int hd, int n_kv, int max_seq, hipStream_t st) {
+                                   int hd, int n_kv, int max_seq, int kv_fp8, hipStream_t st) {
   if (M == 0) return hipSuccess;
   if (hd % 8 != 0 || q_size % hd != 0 || kv_size % hd != 0) return hipErrorInvalidValue;
   const long n = (long)M * ((q_size + 2 * kv_size) / 8);
   hipLaunchKernelGGL(qkv_post_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, y, ldy, bias, tslot, tpos,
-                     rope, q, kc, vc, M, q_size, kv_size, hd, n_kv, max_seq);
+                     rope, q, kc, vc, M, q_size, kv_size, hd, n_kv, max_seq, kv_fp8);
   return hipGetLastError();
 }
 

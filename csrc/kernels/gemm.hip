@@ -130,7 +130,8 @@ __device__ __forceinline__ void epilogue4(const GemmParams& p, int row0, int n, 
         hd_split(p.hd, c, head, d);
         bf16* cache = n < qk ? p.kc : p.vc;
         const long idx = (((long)p.tslot[m] * p.n_kv + head) * p.max_seq + p.tpos[m]) * p.hd + d;
-        cache[idx] = f2bf(y[i]);
+        if (p.kv_fp8) reinterpret_cast<unsigned char*>(cache)[idx] = fp8_enc(y[i]);  // uniform: FP8 E4M3 cache
+        else cache[idx] = f2bf(y[i]);
       }
     }
   }
@@ -262,7 +263,11 @@ __device__ __forceinline__ void epi8_post(const GemmParams& p, int m, int n, con
       bf16* cache = n < qk ? p.kc : p.vc;
       int head, d;
       hd_split(p.hd, c, head, d);
-      st8(cache + (((long)e.slot * p.n_kv + head) * p.max_seq + e.pos) * p.hd + d, o);
+      const long idx = (((long)e.slot * p.n_kv + head) * p.max_seq + e.pos) * p.hd + d;
+      if (p.kv_fp8)  // uniform: FP8 E4M3 cache, the 8 columns are one 8-byte store (from fp32, not via bf16)
+        *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned char*>(cache) + idx) = fp8x8_from_f32(y);
+      else
+        st8(cache + idx, o);
     }
   }
 }

@@ -27,6 +27,9 @@ struct GemmParams {
   // EPI_F32 (tiled kernels): also the max of every 8-column segment,
   // segmax[m * ldseg + n / 8] -- the sampler's first pass, fused (sample.hip)
   float* segmax; long ldseg;
+  // QKV epilogue: 1 = the caches hold FP8 E4M3 bytes (kc / vc are then byte
+  // pointers: one byte per element, saturating encode at the store)
+  int kv_fp8;
 };
 
 // Small-M (M <= 8) weight-streaming GEMV with an optional fused input norm
@@ -50,6 +53,7 @@ struct GemvParams {
   // fp32 logits epilogue: also the max of every 8-column segment (one
   // workgroup = 8 columns) per row, [M][ldseg] -- the sampler's top-k threshold
   float* segmax; long ldseg;
+  int kv_fp8;                         // QKV epilogue: FP8 E4M3 caches (as GemmParams)
 };
 
 }  // namespace lsd

@@ -339,7 +339,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvParams p) {
           } else {
             const int c = n < qk ? n - p.q_size : n - qk;
             bf16* cache = n < qk ? p.kc : p.vc;
-            cache[(((long)e_slot * p.n_kv + c / p.hd) * p.max_seq + pos) * p.hd + c % p.hd] = f2bf(y);
+            const long idx = (((long)e_slot * p.n_kv + c / p.hd) * p.max_seq + pos) * p.hd + c % p.hd;
+            if (p.kv_fp8) reinterpret_cast<unsigned char*>(cache)[idx] = fp8_enc(y);  // uniform: FP8 E4M3 cache
+            else cache[idx] = f2bf(y);
           }
         }
       }

@@ -723,6 +723,10 @@ class EngineConfig:
     merge_prefill: bool = True
     # Fraction of the HBM left after the weights that the KV cache may use.
     kv_fraction: float = 0.85
+    # KV cache element type: "bf16", or "fp8_e4m3" (OCP E4M3, one byte per
+    # element, values saturated to +-448, no scale factors): half the bytes the
+    # decode attention streams and twice the slots in the same kv_fraction.
+    kv_dtype: str = "bf16"
     # Serving: record per-stage busy / bubble timing on one pipeline session
     # in this many (0 = never) -- it costs a control-plane gather per session.
     metrics_every: int = 16
@@ -770,6 +774,8 @@ class EngineConfig:
     prefix_cache_min_tokens: int = 8
 
     def __post_init__(self):
+        if self.kv_dtype not in ("bf16", "fp8_e4m3"):
+            raise ValueError(f"kv_dtype must be 'bf16' or 'fp8_e4m3', got {self.kv_dtype!r}")
         if not (0 <= self.prefix_cache <= self.max_batch):
             raise ValueError("prefix_cache must be in [0, max_batch]: an entry is one of the replica's KV slots")
         if self.prefix_cache_min_tokens < 1:
@@ -824,6 +830,7 @@ class EngineConfig:
             join_min=int(_env("JOIN_MIN", "32")),
             join_max_wait=int(_env("JOIN_MAX_WAIT", "4")),
             kv_fraction=float(_env("KV_FRACTION", "0.85")),
+            kv_dtype=_env("KV_DTYPE", "bf16"),
             metrics_every=int(_env("METRICS_EVERY", "16")),
             max_logprobs=int(_env("MAX_LOGPROBS", "5")),
             max_logit_edits=int(_env("MAX_LOGIT_EDITS", "300")),

@@ -34,7 +34,8 @@ class StageModel:
                  weights_path: Optional[str] = None, max_slots: int = 8, max_seq: int = 1024,
                  weights: Optional[Dict[str, torch.Tensor]] = None,
                  units: Optional[Tuple[int, int]] = None, backend=None,
-                 variants: Optional[Sequence[Tuple[int, int]]] = None):
+                 variants: Optional[Sequence[Tuple[int, int]]] = None,
+                 kv_dtype: Optional[torch.dtype] = None):
         self.cfg = cfg
         self.device = torch.device(device)
         if dtype is None:
@@ -66,7 +67,7 @@ class StageModel:
         self.w = weights
         self.max_seq = min(max_seq, cfg.max_positions)
         self.kv = KVCache(len(self.kv_layers), max_slots, cfg.n_kv_heads, self.max_seq,
-                          cfg.head_dim, dtype, self.device)
+                          cfg.head_dim, kv_dtype if kv_dtype is not None else dtype, self.device)
         # `backend` overrides the device default: the fp32 golden model runs the
         # plain PyTorch ops (ops/reference.py) on the GPU (utils/golden.py)
         self.backend = backend if backend is not None else get_backend(self.device)

@@ -78,8 +78,16 @@ def apply_rope(x: torch.Tensor, pos: torch.Tensor, theta: float) -> torch.Tensor
 
 def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
               slots: torch.Tensor, pos: torch.Tensor) -> None:
-    """Cache layout [slots, n_kv, max_seq, hd]; k, v: [T, n_kv, hd]."""
+    """Cache layout [slots, n_kv, max_seq, hd]; k, v: [T, n_kv, hd].  An FP8
+    (float8_e4m3fn) cache saturates: values are clamped to +-448 ahead of the
+    cast (a bare cast turns overflow into NaN), rounded to nearest-even once."""
     s, p = slots.long(), pos.long()
+    if k_cache.dtype == torch.float8_e4m3fn:
+        # the bytes are written through a uint8 view: indexed writes of 8-bit
+        # floats are not implemented on every device
+        k_cache.view(torch.uint8)[s, :, p, :] = k.clamp(-448.0, 448.0).to(k_cache.dtype).view(torch.uint8)
+        v_cache.view(torch.uint8)[s, :, p, :] = v.clamp(-448.0, 448.0).to(v_cache.dtype).view(torch.uint8)
+        return
     k_cache[s, :, p, :] = k.to(k_cache.dtype)
     v_cache[s, :, p, :] = v.to(v_cache.dtype)
 

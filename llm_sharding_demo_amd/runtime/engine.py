@@ -47,7 +47,7 @@ from ..parallel.comm import (DeviceLoopFabric, GlooPlanChannel, LocalFabric, Loc
                              open_data_plane, transport_chain)
 from ..parallel.partition import make_alt_unit_plans, make_unit_plan, union_plan, units_to_layers
 from ..parallel.pipeline import StageWorker
-from .kv_cache import KVCache, SlotAllocator, plan_slots
+from .kv_cache import KVCache, SlotAllocator, kv_dtype_of, plan_slots
 from .plan import GroupPlan, StepPlan
 from .scheduler import Request, Scheduler
 
@@ -284,6 +284,7 @@ class Engine(racecheck.Shared):
         for dev, n_kv_layers, w_bytes in per_dev.values():
             fits = min(fits, plan_slots(want + 2, n_kv_layers, self.mcfg.n_kv_heads, self.max_seq,
                                         self.mcfg.head_dim, dev, reserve=w_bytes,
+                                        elt=kv_dtype_of(self.cfg.kv_dtype)[1],  # FP8: twice the slots
                                         fraction=self.cfg.kv_fraction, mem_get_info=share) - 2)
         if collective:
             import torch.distributed as dist
@@ -344,7 +345,8 @@ class Engine(racecheck.Shared):
                           dtype=_dtype(self.cfg.dtype, device), seed=self.cfg.seed,
                           weights_path=self.cfg.weights, max_slots=self.kv_slots + 2,
                           max_seq=self.max_seq, units=self.unit_plan[i],
-                          variants=[p[i] for p in self.unit_plans] if self.unit_plans else None)
+                          variants=[p[i] for p in self.unit_plans] if self.unit_plans else None,
+                          kv_dtype=kv_dtype_of(self.cfg.kv_dtype)[0])
 
     def _worker(self, st: StageModel, t, i: int) -> StageWorker:
         if self.cfg.wire_dtype not in ("fp32", "bf16"):
@@ -365,7 +367,7 @@ class Engine(racecheck.Shared):
 
     def kv_info(self) -> dict:
         st = self.stages[0]
-        return {"kv_slots": self.kv_slots, "kv_bytes_stage0": st.kv.nbytes,
+        return {"kv_slots": self.kv_slots, "kv_bytes_stage0": st.kv.nbytes, "kv_dtype": self.cfg.kv_dtype,
                 "kv_slots_free": sum(p.available for p in self.slot_pools),
                 "group_rows": self.group_cap, "groups": self.M,
                 # half-layer unit ranges per stage: one plan, or (even, odd) group plans

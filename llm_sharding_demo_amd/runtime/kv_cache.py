@@ -6,7 +6,9 @@ pipeline stage owns the K/V of ITS layers only, so the only thing that
 crosses the inter-stage link per decode step is the boundary hidden state.
 
 Layout (one allocation per stage):
-    buf[layer, 0|1 (K|V), slot, kv_head, position, head_dim]   bf16 on GPU
+    buf[layer, 0|1 (K|V), slot, kv_head, position, head_dim]   bf16 on GPU,
+    or FP8 E4M3 (`kv_dtype="fp8_e4m3"`: one byte per element, values
+    saturated to +-448 when written, no scale factors)
 Each (slot, head) row-block is contiguous over positions, so the decode
 attention kernel streams K and V for one sequence/head as one linear 1 KiB-
 per-wave-instruction read.  Sized for MI355X's 288 GB HBM: the engine asks
@@ -21,7 +23,22 @@ from typing import List
 import torch
 
 
+# EngineConfig.kv_dtype values -> (cache dtype or None = the stage's dtype, bytes per element)
+KV_DTYPES = {"bf16": (None, 2), "fp8_e4m3": (torch.float8_e4m3fn, 1)}
+
+
+def kv_dtype_of(name: str):
+    """(torch dtype or None, element bytes) of a `kv_dtype` name; ValueError otherwise."""
+    if name not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {sorted(KV_DTYPES)}, got {name!r}")
+    return KV_DTYPES[name]
+
+
 class KVCache:
+    """One allocation [layers, 2, slots, kv_heads, max_seq, head_dim] in `dtype`:
+    the stage's dtype (bf16 on the GPU) or torch.float8_e4m3fn (the FP8 cache:
+    same shape, one byte per element)."""
+
     def __init__(self, n_layers: int, slots: int, n_kv: int, max_seq: int, head_dim: int,
                  dtype: torch.dtype, device):
         self.n_layers, self.slots, self.n_kv = n_layers, slots, n_kv

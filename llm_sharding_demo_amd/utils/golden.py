@@ -5,7 +5,7 @@ The reference delegates all math to HF transformers on CPU in fp32
 model (same bf16-initialised weights, widened to fp32) run through the plain
 PyTorch ops of ops/reference.py -- on the same GPU, so full GPT-2 XL and
 Llama-3 8B dimensions are affordable -- and the HIP model (bf16 weights and
-activations, fp32 accumulation, bf16 KV cache) is compared logit by logit
+activations, fp32 accumulation, bf16 or FP8 KV cache) is compared logit by logit
 over a prefill plus teacher-forced decode steps (both models are fed the
 golden's greedy tokens, so one near-tie cannot derail the rest of the run).
 
@@ -24,43 +24,59 @@ from ..models.stage import StageModel
 from ..models.weights import init_stage_weights
 from ..ops import ReferenceBackend
 from ..runtime.batch import BatchMeta
+from ..runtime.kv_cache import kv_dtype_of
 
 
 def compare_with_golden(model_id, prompts: List[List[int]], steps: int = 8,
-                        device: str = "cuda", seed: int = 0, inject=1.0):
+                        device: str = "cuda", seed: int = 0, inject=1.0, kv_dtype=None):
     """`inject` scales the HIP logits' deviation from the golden before it is
     measured (1.0: as computed); a tuple of factors returns one result per
     factor from the same forward passes.  The gate tests use 3.0 to show that
-    a kernel regression of that size fails the bounds."""
+    a kernel regression of that size fails the bounds.
+
+    `kv_dtype` (a torch dtype, e.g. torch.float8_e4m3fn; None: as ever) gives
+    the HIP model that KV cache and adds a third model to the same loop: the
+    fp32 golden's ops over a cache of that dtype -- the cost of the cache
+    format alone.  All three are fed the fp32 golden's tokens, and the result
+    is {"golden_kv": metrics of golden/kv_dtype vs golden/fp32,
+        "hip_kv":    metrics of HIP/kv_dtype vs golden/fp32}."""
+    if isinstance(kv_dtype, str):  # an EngineConfig.kv_dtype name; "bf16" is the default cache
+        kv_dtype = kv_dtype_of(kv_dtype)[0]
     mc = get_model_config(model_id) if isinstance(model_id, str) else model_id
     dev = torch.device(device)
     L = mc.n_layers
     max_seq = max(len(p) for p in prompts) + steps + 1
     B = len(prompts)
     w = init_stage_weights(mc, range(L), True, True, seed, dev, torch.bfloat16)
-    gold = StageModel(mc, 0, L, True, True, device=dev, dtype=torch.float32,
-                      weights={k: v.float() for k, v in w.items()}, max_slots=B, max_seq=max_seq,
-                      backend=ReferenceBackend())
+    wf = {k: v.float() for k, v in w.items()}
+    gold = StageModel(mc, 0, L, True, True, device=dev, dtype=torch.float32, weights=wf,
+                      max_slots=B, max_seq=max_seq, backend=ReferenceBackend())
     hip = StageModel(mc, 0, L, True, True, device=dev, dtype=torch.bfloat16, weights=w,
-                     max_slots=B, max_seq=max_seq)
-    del w
+                     max_slots=B, max_seq=max_seq, kv_dtype=kv_dtype)
+    # the models measured against the golden, in the order of the results
+    cands = [hip]
+    if kv_dtype is not None:
+        cands.insert(0, StageModel(mc, 0, L, True, True, device=dev, dtype=torch.float32, weights=wf,
+                                   max_slots=B, max_seq=max_seq, backend=ReferenceBackend(), kv_dtype=kv_dtype))
+    del w, wf
     V = mc.vocab_size
     slots = list(range(B))
     factors = tuple(inject) if isinstance(inject, (tuple, list)) else (inject,)
     flat = torch.tensor([t for p in prompts for t in p], dtype=torch.int32, device=dev)
     meta = lambda: BatchMeta.build(slots, [0] * B, [len(p) for p in prompts], dev)  # noqa: E731
-    errs = [[] for _ in factors]
-    agree = [0] * len(factors)
+    errs = [[[] for _ in factors] for _ in cands]
+    agree = [[0] * len(factors) for _ in cands]
     rows = 0
     with torch.no_grad():
         lg = gold.forward(meta(), flat)[:, :V].float()
-        lh = hip.forward(meta(), flat)[:, :V].float()
+        lhs = [m.forward(meta(), flat)[:, :V].float() for m in cands]
         for step in range(steps + 1):
             std = lg.std(dim=1, keepdim=True)
-            for i, f in enumerate(factors):
-                lf = lh if f == 1.0 else lg + f * (lh - lg)
-                errs[i].append(((lf - lg).abs().amax(dim=1, keepdim=True) / std).squeeze(1))
-                agree[i] += int((lf.argmax(1) == lg.argmax(1)).sum())
+            for c, lh in enumerate(lhs):
+                for i, f in enumerate(factors):
+                    lf = lh if f == 1.0 else lg + f * (lh - lg)
+                    errs[c][i].append(((lf - lg).abs().amax(dim=1, keepdim=True) / std).squeeze(1))
+                    agree[c][i] += int((lf.argmax(1) == lg.argmax(1)).sum())
             rows += B
             if step == steps:
                 break
@@ -68,13 +84,17 @@ def compare_with_golden(model_id, prompts: List[List[int]], steps: int = 8,
             pos = [len(p) + step for p in prompts]
             dm = lambda: BatchMeta.decode(slots, pos, dev, max(pos) + 1)  # noqa: E731
             lg = gold.forward(dm(), tok)[:, :V].float()
-            lh = hip.forward(dm(), tok)[:, :V].float()
-    out = []
-    for i in range(len(factors)):
-        e = torch.cat(errs[i])
-        out.append({"rows": rows, "top1_agreement": agree[i] / rows, "max_rel_err": float(e.max()),
-                    "mean_rel_err": float(e.mean()), "per_step": [round(float(x.max()), 4) for x in errs[i]]})
-    return out if isinstance(inject, (tuple, list)) else out[0]
+            lhs = [m.forward(dm(), tok)[:, :V].float() for m in cands]
+    res = []
+    for c in range(len(cands)):
+        out = []
+        for i in range(len(factors)):
+            e = torch.cat(errs[c][i])
+            out.append({"rows": rows, "top1_agreement": agree[c][i] / rows, "max_rel_err": float(e.max()),
+                        "mean_rel_err": float(e.mean()),
+                        "per_step": [round(float(x.max()), 4) for x in errs[c][i]]})
+        res.append(out if isinstance(inject, (tuple, list)) else out[0])
+    return res[0] if kv_dtype is None else {"golden_kv": res[0], "hip_kv": res[1]}
 
 
 class Bf16EmulationBackend(ReferenceBackend):
