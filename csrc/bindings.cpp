@@ -108,6 +108,10 @@ hipError_t lsd_record_context(int* tok, int L, int nslots, const int* plen, cons
 hipError_t lsd_logprobs(const float* logits, long ld, int B, int V, const int* tokens, const int* nlp, const int* slots,
                         const long long* step, int back, const int* active, float* lp_tok, int* lp_top_id,
                         float* lp_top, int L, int nslots, int W, hipStream_t st);
+int lsd_score_slices(int T, int Vp);
+hipError_t lsd_lm_head_score(const void* xn, long lda, const void* w, long ldw, const int* targets, int T, int V,
+                             int Vp, int K, int S, float* part, float* tok_lp, int* top_id, float* top_lp,
+                             hipStream_t st);
 }
 
 namespace {
@@ -1133,6 +1137,39 @@ void logprobs(torch::Tensor logits, int64_t V, torch::Tensor tokens, torch::Tens
                          (int)lp_top.size(2), cur_stream()), "logprobs");
 }
 
+// Sequence scoring (score.hip): the lm_head GEMM of xn [T, K] against the
+// padded w [Vp, K], reduced per row over columns [0, V) to the target's
+// logprob, the argmax and its logprob; no logit is stored.  slices = 0: the
+// launcher's choice for (T, Vp); else that many vocabulary slices (at most one
+// per 128-column tile).  Targets in [0, V) are the caller's to check.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lm_head_score(torch::Tensor xn, torch::Tensor w,
+                                                                      torch::Tensor targets, int64_t V,
+                                                                      int64_t slices) {
+  need(xn, torch::kBFloat16, "xn");
+  need(w, torch::kBFloat16, "w");
+  need(targets, torch::kInt32, "targets");
+  TORCH_CHECK(xn.dim() == 2 && w.dim() == 2 && xn.stride(1) == 1 && w.stride(1) == 1 && xn.size(1) == w.size(1),
+              "lm_head_score: xn [T, K], w [Vp, K]");
+  const int64_t T = xn.size(0), K = xn.size(1), Vp = w.size(0);
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && Vp >= 64 && Vp % 64 == 0, "lm_head_score: K % 64 == 0 and Vp % 64 == 0");
+  TORCH_CHECK(V >= 1 && V <= Vp, "lm_head_score: vocab lies in [1, Vp]");
+  TORCH_CHECK(xn.stride(0) % 8 == 0 && w.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(xn.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, "lm_head_score: 16-byte rows");
+  TORCH_CHECK(targets.dim() == 1 && targets.numel() == T && targets.is_contiguous(),
+              "lm_head_score: targets is contiguous int32 [T]");
+  TORCH_CHECK(T < (1 << 30) && Vp < (1 << 30) && slices >= 0, "lm_head_score: sizes exceed int32");
+  const int nt = (int)((Vp + 127) / 128);
+  const int S = std::min(nt, slices > 0 ? (int)std::min<int64_t>(slices, nt) : lsd_score_slices((int)T, (int)Vp));
+  auto fo = xn.options().dtype(torch::kFloat32);
+  auto tok_lp = torch::empty({T}, fo), top_lp = torch::empty({T}, fo);
+  auto top_id = torch::empty({T}, xn.options().dtype(torch::kInt32));
+  auto part = torch::empty({T, S, 4}, fo);
+  check_hip(lsd_lm_head_score(xn.data_ptr(), xn.stride(0), w.data_ptr(), w.stride(0), targets.data_ptr<int>(), (int)T,
+                              (int)V, (int)Vp, (int)K, S, part.data_ptr<float>(), tok_lp.data_ptr<float>(),
+                              top_id.data_ptr<int>(), top_lp.data_ptr<float>(), cur_stream()), "lm_head_score");
+  return {tok_lp, top_id, top_lp};
+}
+
 torch::Tensor silu_mul(torch::Tensor y) {
   need(y, torch::kBFloat16, "y");
   TORCH_CHECK(y.dim() == 2 && y.stride(1) == 1 && y.size(1) % 32 == 0, "silu_mul: y [M, 2F], 2F % 32 == 0");
@@ -1235,6 +1272,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("logprobs", &logprobs, py::arg("logits"), py::arg("V"), py::arg("tokens"), py::arg("nlp"), py::arg("slots"),
         py::arg("step"), py::arg("active"), py::arg("lp_tok"), py::arg("lp_top_id"), py::arg("lp_top"),
         py::arg("back") = 0);
+  m.def("lm_head_score", &lm_head_score, py::arg("xn"), py::arg("w"), py::arg("targets"), py::arg("vocab"),
+        py::arg("slices") = 0);
+  m.def("score_slices", [](int64_t T, int64_t Vp) { return lsd_score_slices((int)T, (int)Vp); });
   m.def("qkv_post", &qkv_post);
   // GEMV weight stream with non-temporal loads (A/B knob, LSD_GEMV_NT)
   m.def("gemv_set_nt", [](int64_t v) { lsd_gemv_set_nt((int)v); });

@@ -181,6 +181,17 @@ class StageModel:
             xn = be.norm_rows(x, self.w["norm.weight"], None, c.norm_eps, True, rows)
         return be.logits(xn, self.lm_head_weight)
 
+    def score_head(self, x: torch.Tensor, meta: BatchMeta, targets: torch.Tensor):
+        """Sequence scoring over the last stage's hidden rows x [T, H] (a
+        `forward(..., head=False)`): the final norm of every row, then the
+        backend's `score_rows` -> (tok_lp, top_id, top_lp) of targets [T]."""
+        be, c = self.backend, self.cfg
+        if c.arch == "gpt2":
+            xn = be.norm_rows(x, self.w["ln_f.weight"], self.w["ln_f.bias"], c.norm_eps, False, None)
+        else:
+            xn = be.norm_rows(x, self.w["norm.weight"], None, c.norm_eps, True, None)
+        return be.score_rows(xn, self.lm_head_weight, targets, c.vocab_size)
+
     @property
     def lm_head_weight(self) -> torch.Tensor:
         if hasattr(self, "_lm_head_padded"):

@@ -175,6 +175,13 @@ class ReferenceBackend(Backend):
         W = rec[1].shape[2]
         ref.record_logprobs(rec, slots, step, nlp, *ref.logprobs(logits, tokens, nlp, vocab, W), active, back)
 
+    def score_rows(self, xn, w, targets, vocab: int):
+        """Sequence scoring: of every row's logits xn[r] . w^T over [0, vocab),
+        the logprob of targets[r], the argmax and its logprob (ops/reference.py
+        score_rows) -> (tok_lp, top_id, top_lp), each [T].  Here the float
+        path: fp32 logits, float64 lse; the HIP backend never stores a logit."""
+        return ref.score_rows(ref.linear(xn, w), targets, vocab)
+
     def kv_fork(self, buf, src, dst, lens, idx=None) -> None:
         """Fork prompts' KV (SamplingParams.n): positions [0, lens[f]) of slot
         src[f] of a stage's whole KV allocation go to slot dst[f], for every

@@ -445,5 +445,18 @@ class HipBackend(Backend):
         # nlp < 0 return at once
         self.C.logprobs(logits, vocab, tokens, nlp, slots, step, active, rec[0], rec[1], rec[2], back)
 
+    def score_rows(self, xn, w, targets, vocab: int):
+        # score.hip: the lm_head GEMM reduced per row inside the kernel -- no
+        # [T, vocab_padded] logits.  One host sync to refuse bad targets.
+        targets = targets.to(torch.int32).contiguous()
+        if targets.numel():
+            lo, hi = targets.aminmax()
+            if int(lo) < 0 or int(hi) >= vocab:
+                raise ValueError(f"score: target ids must lie in the vocabulary [0, {vocab})")
+        xn = self.materialize(xn)
+        if w.shape[1] % 64 != 0 or w.shape[0] % 64 != 0:  # tiny-gpt2's hidden size of 2
+            return ref.score_rows(self.logits(xn, w), targets, vocab)
+        return self.C.lm_head_score(xn, w, targets, vocab, 0)
+
     def gather_rows(self, x, idx):
         return x.index_select(0, idx.long())

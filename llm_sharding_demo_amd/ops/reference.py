@@ -536,6 +536,25 @@ def logprobs(logits: torch.Tensor, tokens: torch.Tensor, nlp, vocab: int, W: int
     return tok_lp, top_id, top_lp
 
 
+def score_rows(logits: torch.Tensor, targets: torch.Tensor, vocab: int):
+    """Sequence scoring of fp32 logit rows [T, >= vocab], `logprobs`' arithmetic
+    for every row at once: lse in float64 rounded once to fp32, logprob
+    fl32(x - lse), the argmax by a stable descending sort (lowest index on
+    ties).  Unlike `logprobs`, a target outside [0, vocab) is refused.
+
+    -> (tok_lp [T] fp32, top_id [T] int32, top_lp [T] fp32) on logits' device.
+    """
+    t = targets.long()
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= vocab):
+        raise ValueError(f"score: target ids must lie in the vocabulary [0, {vocab})")
+    row = logits[:, :vocab].detach().float()
+    m = row.max(dim=1, keepdim=True).values
+    lse = (m.double() + torch.log(torch.exp((row - m).double()).sum(dim=1, keepdim=True))).float()
+    lp = row - lse
+    top = torch.sort(row, dim=1, descending=True, stable=True).indices[:, :1]
+    return lp.gather(1, t.view(-1, 1))[:, 0], top[:, 0].to(torch.int32), lp.gather(1, top)[:, 0]
+
+
 def record_logprobs(rec, slots: torch.Tensor, step: Optional[torch.Tensor], nlp, tok_lp, top_id, top_lp,
                     active: Optional[torch.Tensor] = None, back: int = 0) -> None:
     """Store `logprobs` results of the rows with nlp >= 0 as record

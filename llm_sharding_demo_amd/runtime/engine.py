@@ -62,6 +62,16 @@ class SessionStats:
     stages: List[dict] = field(default_factory=list)
 
 
+@dataclass
+class Score:
+    """`Engine.score` of one sequence: entry i scores token i + 1 given tokens
+    [0, i] -- its logprob, the most likely token there and that token's
+    logprob.  Each list has len(sequence) - 1 entries."""
+    token_logprobs: List[float]
+    greedy_ids: List[int]
+    greedy_logprobs: List[float]
+
+
 def _dtype(name: str, device: torch.device) -> torch.dtype:
     if device.type == "cpu":
         return torch.float32
@@ -1070,6 +1080,49 @@ class Engine(racecheck.Shared):
             if dev.type == "cuda":
                 torch.cuda.synchronize(dev)
             return out
+
+
+    # ------------------------------------------------------------------
+    # Sequence scoring
+    # ------------------------------------------------------------------
+    def score(self, sequences: List[List[int]]) -> List[Score]:
+        """Log-probability of every token of each sequence under the model
+        (loglikelihood / perplexity / reranking): one `Score` per sequence.
+
+        A call of its own beside generation: under the engine lock, between
+        sessions, each sequence is run alone on the compat KV slot, stage by
+        stage, and the last stage reduces every row's logits to its score
+        (StageModel.score_head) without storing them.  The scheduler, the plan
+        wire, the prefix cache and the decode graphs take no part.  With
+        kv_dtype = fp8 the attention reads the FP8 cache, so the scores are
+        those of the FP8 cache, as the tokens it generates are."""
+        from .batch import BatchMeta
+
+        if self.mode == "dist":
+            # as for logprobs: the last stage's results are read in this process
+            raise ValueError("score needs the last stage in the coordinator process")
+        V = self.mcfg.vocab_size
+        if len(sequences) == 0:
+            raise ValueError("score: no sequences given")
+        for seq in sequences:
+            if not 2 <= len(seq) <= self.max_seq:
+                raise ValueError(f"score: a sequence has {len(seq)} tokens, it needs 2 to {self.max_seq}")
+            for t in seq:
+                if not 0 <= t < V:
+                    raise ValueError(f"score: token id {t} outside the vocabulary [0, {V})")
+        out = []
+        slot = self.kv_slots + 1
+        with self._lock:
+            for seq in sequences:
+                T = len(seq)
+                x = torch.tensor(seq, dtype=torch.int32, device=self.stages[0].device)
+                for st in self.stages:
+                    meta = BatchMeta.build([slot], [0], [T], st.device)
+                    x = st.forward(meta, x.to(st.device), head=False)
+                targets = torch.tensor(seq[1:], dtype=torch.int32, device=st.device)
+                tok_lp, top_id, top_lp = st.score_head(x[: T - 1], meta, targets)
+                out.append(Score(tok_lp.tolist(), top_id.tolist(), top_lp.tolist()))
+        return out
 
 
 def _ranks_sharing_device(dev: torch.device, group) -> int:

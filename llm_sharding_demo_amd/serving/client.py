@@ -49,3 +49,21 @@ def generate_text(prompt: str, max_new_tokens: int = 20, url: str = None,
         return f"Error: {r.status_code} - {r.text}"
     except requests.exceptions.RequestException as e:
         return f"Request failed: {e}"
+
+
+def score(input_ids: list = None, texts: list = None, url: str = None, timeout: float = 300.0) -> Union[dict, str]:
+    """POST /score of the coordinator beside `url` (default COORDINATOR_URL's
+    host): token id lists or texts -> {"scores": [...]}, one object per
+    sequence with token_logprobs, greedy_ids and greedy_logprobs (entry i
+    scores token i + 1).  Errors come back as generate_text's strings."""
+    import requests
+
+    base = url or COORDINATOR_URL.rsplit("/", 1)[0] + "/score"
+    payload = {"input_ids": input_ids} if input_ids is not None else {"texts": texts}
+    try:
+        r = requests.post(base, json=payload, timeout=timeout)
+        if r.status_code == 200:
+            return r.json()
+        return f"Error: {r.status_code} - {r.text}"
+    except requests.exceptions.RequestException as e:
+        return f"Request failed: {e}"

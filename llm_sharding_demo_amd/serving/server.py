@@ -14,7 +14,10 @@ Roles (env SHARD_ROLE, `server.py:21`):
   a            stage 0 = embeddings + blocks[0:SPLIT_AT]          -> /forward
   b            blocks[SPLIT_AT:] + ln_f + lm_head                 -> /forward_b
   all          one process answers every endpoint (debug)
-Additions: optional sampling fields on /generate (temperature, top_k, top_p,
+Additions: POST /score {input_ids: [[int]]} or {texts: [str]} -> {"scores": [{input_ids,
+token_logprobs, greedy_ids, greedy_logprobs}]}, entry i scoring token i + 1 (coordinator with an
+engine; 422 on an empty list, a sequence of < 2 or too many tokens, ids outside the vocabulary);
+optional sampling fields on /generate (temperature, top_k, top_p,
 min_p, presence_penalty, frequency_penalty, logprobs, logit_bias, banned_token_ids,
 min_new_tokens, repetition_penalty, no_repeat_ngram_size, allowed_token_ids, bad_words,
 bad_words_ids, stop, stop_token_ids, include_stop_in_output, guided_regex, guided_choice,
@@ -105,6 +108,12 @@ class GenerateReq(BaseModel):
     # nor leaves an entry behind; a JSON bool.  While the cache is on the response gains
     # "cached_tokens", the leading prompt tokens whose prefill an entry's KV replaced
     prefix_cache: StrictBool = True
+
+
+class ScoreReq(BaseModel):
+    # the sequences to score, as token ids or as texts for the server's tokenizer (one of the two)
+    input_ids: Optional[List[List[int]]] = None
+    texts: Optional[List[str]] = None
 
 
 class GuideCache:
@@ -246,6 +255,22 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
         except RuntimeError as e:
             raise HTTPException(400, str(e))
         return {"logits": torch.stack(outs).tolist()}
+
+    @app.post("/score")
+    def score(req: ScoreReq):
+        if not _role_is("coordinator"):
+            return {"error": "This instance is not coordinator."}
+        if engine is None:
+            raise HTTPException(400, "scoring needs an engine in this process")
+        if (req.input_ids is None) == (req.texts is None):
+            raise HTTPException(422, "give one of input_ids and texts")
+        seqs = req.input_ids if req.input_ids is not None else [tok.encode(t) for t in req.texts]
+        try:
+            res = engine.score(seqs)
+        except ValueError as e:
+            raise HTTPException(422, str(e))
+        return {"scores": [{"input_ids": list(s), "token_logprobs": r.token_logprobs, "greedy_ids": r.greedy_ids,
+                            "greedy_logprobs": r.greedy_logprobs} for s, r in zip(seqs, res)]}
 
     @app.post("/generate")
     def generate(req: GenerateReq):
