@@ -69,6 +69,10 @@ hipError_t lsd_attn_oproj(const bf16* q, long ldq, const bf16* kc, const bf16* v
 int lsd_gemv_ok(int M, int K, int epi, int norm);
 void lsd_gemv_set_nt(int v);
 hipError_t lsd_gemv(const lsd::GemvParams* p, int epi, int norm, hipStream_t st);
+int lsd_gemv_ok_w(int M, int K, int epi, int norm, int w_fp8);
+hipError_t lsd_gemv_fp8(const lsd::GemvParams* p, const float* wscale, int epi, int norm, hipStream_t st);
+hipError_t lsd_quantize_rows_fp8(const void* W, long ldw, void* q, float* scale, int N, int K, hipStream_t st);
+hipError_t lsd_dequant_rows_fp8(const void* q, const float* scale, void* out, int N, int K, hipStream_t st);
 hipError_t lsd_apply_rows(const int64_t* args, int nargs, int b, hipStream_t st);
 hipError_t lsd_silu_mul(const lsd_bf16_t* y, long ldy, lsd_bf16_t* out, long ldo, int M, int F, hipStream_t st);
 hipError_t lsd_qkv_post(const float* y, long ldy, const lsd_bf16_t* bias, const int* tslot, const int* tpos,
@@ -350,6 +354,8 @@ torch::Tensor linear_qkv(torch::Tensor a, torch::Tensor w, c10::optional<torch::
 //   residual [M, K], normalised in the kernel with gamma (+ beta).
 //   epi: 0 bf16, 1 gelu, 2 silu(gate)*up, 3 f32, 4 residual add into `resid`,
 //   6 QKV (q returned, k/v appended to the caches, optional RoPE).
+//   wscale: w holds FP8 E4M3 rows (csrc/kernels/wquant.hip) and wscale their
+//   fp32 scales [N]; the outputs are what the bf16 weight's would be.
 c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias,
                                   int64_t epi, int64_t norm, c10::optional<torch::Tensor> gamma,
                                   c10::optional<torch::Tensor> beta, double eps,
@@ -358,16 +364,23 @@ c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optiona
                                   c10::optional<torch::Tensor> tslot, c10::optional<torch::Tensor> tpos,
                                   int64_t q_size, int64_t kv_size, int64_t hd,
                                   c10::optional<torch::Tensor> rope,
-                                  c10::optional<torch::Tensor> segmax = c10::nullopt) {
-  need(w, torch::kBFloat16, "w");
+                                  c10::optional<torch::Tensor> segmax = c10::nullopt,
+                                  c10::optional<torch::Tensor> wscale = c10::nullopt) {
+  const bool w8 = wscale.has_value();
+  need(w, w8 ? torch::kFloat8_e4m3fn : torch::kBFloat16, "w");
   need_rows(w, "w");
+  if (w8) {
+    need(*wscale, torch::kFloat32, "wscale");
+    TORCH_CHECK(w.stride(0) % 16 == 0, "FP8 w rows must be 16-byte aligned");
+    TORCH_CHECK(wscale->is_contiguous() && wscale->numel() == w.size(0), "wscale must be contiguous [N]");
+  }
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1, "x must be 2-D with unit last stride");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "x must be 16-byte aligned");
   GemvParams p{};
   p.M = x.size(0); p.K = x.size(1); p.N = w.size(0);
   TORCH_CHECK(w.size(1) == p.K, "K mismatch: x ", x.sizes(), " w ", w.sizes());
-  TORCH_CHECK(lsd_gemv_ok(p.M, p.K, (int)epi, (int)norm), "gemv: shape M=", p.M, " K=", p.K,
-              " epi=", epi, " norm=", norm, " not supported");
+  TORCH_CHECK(lsd_gemv_ok_w(p.M, p.K, (int)epi, (int)norm, w8), "gemv: shape M=", p.M, " K=", p.K,
+              " epi=", epi, " norm=", norm, w8 ? " (FP8 weights)" : "", " not supported");
   p.W = bptr(w); p.ldw = w.stride(0);
   if (norm == 0) {
     need(x, torch::kBFloat16, "x");
@@ -395,7 +408,7 @@ c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optiona
     p.bias = bptr(*bias);
   }
   c10::optional<torch::Tensor> ret;
-  auto bopt = w.options();
+  auto bopt = w.options().dtype(torch::kBFloat16);
   if (epi == EPI_RESID) {
     TORCH_CHECK(resid.has_value(), "residual epilogue needs the residual");
     need(*resid, torch::kFloat32, "resid");
@@ -446,8 +459,40 @@ c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optiona
     TORCH_CHECK(false, "gemv: unknown epilogue ", epi);
   }
   TORCH_CHECK(!segmax.has_value() || epi == EPI_F32, "segmax needs the fp32 logits epilogue");
-  check_hip(lsd_gemv(&p, (int)epi, (int)norm, cur_stream()), "gemv");
+  if (w8) check_hip(lsd_gemv_fp8(&p, wscale->data_ptr<float>(), (int)epi, (int)norm, cur_stream()), "gemv(fp8)");
+  else check_hip(lsd_gemv(&p, (int)epi, (int)norm, cur_stream()), "gemv");
   return ret;
+}
+
+// Weight-only FP8 (csrc/kernels/wquant.hip): w bf16 [N, K] -> (q E4M3 [N, K],
+// scale fp32 [N]), scale = rowwise amax / 448 (1 for a zero row).
+std::tuple<torch::Tensor, torch::Tensor> quantize_rows_fp8(torch::Tensor w) {
+  need(w, torch::kBFloat16, "w");
+  need_rows(w, "w");
+  TORCH_CHECK(w.size(0) >= 1 && w.size(1) >= 16 && w.size(1) % 16 == 0, "quantize_rows_fp8: K must be a multiple of 16, got ",
+              w.sizes());
+  auto q = torch::empty({w.size(0), w.size(1)}, w.options().dtype(torch::kFloat8_e4m3fn));
+  auto scale = torch::empty({w.size(0)}, w.options().dtype(torch::kFloat32));
+  check_hip(lsd_quantize_rows_fp8(w.data_ptr(), w.stride(0), q.data_ptr(), scale.data_ptr<float>(),
+                                  (int)w.size(0), (int)w.size(1), cur_stream()), "quantize_rows_fp8");
+  return {q, scale};
+}
+
+// q, scale -> bf16 [N, K] = bf16(float(q) * scale) into the first N * K elements of `out`
+torch::Tensor dequant_rows_fp8(torch::Tensor q, torch::Tensor scale, torch::Tensor out) {
+  need(q, torch::kFloat8_e4m3fn, "q");
+  need(scale, torch::kFloat32, "scale");
+  need(out, torch::kBFloat16, "out");
+  const int64_t N = q.size(0), K = q.dim() == 2 ? q.size(1) : 0;
+  TORCH_CHECK(q.dim() == 2 && q.is_contiguous() && N >= 1 && K >= 16 && K % 16 == 0,
+              "dequant_rows_fp8: q must be contiguous [N, K], K % 16 == 0");
+  TORCH_CHECK(scale.is_contiguous() && scale.numel() == N, "scale must be contiguous [N]");
+  TORCH_CHECK(out.is_contiguous() && out.numel() >= N * K, "out must be contiguous with room for N * K elements");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0, "q and out must be 16-byte aligned");
+  check_hip(lsd_dequant_rows_fp8(q.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), (int)N, (int)K, cur_stream()),
+            "dequant_rows_fp8");
+  return out.flatten().narrow(0, 0, N * K).view({N, K});
 }
 
 torch::Tensor embed(torch::Tensor ids, torch::Tensor pos, torch::Tensor wte,
@@ -1238,15 +1283,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                    double eps, c10::optional<torch::Tensor> resid, c10::optional<torch::Tensor> kc,
                    c10::optional<torch::Tensor> vc, c10::optional<torch::Tensor> tslot,
                    c10::optional<torch::Tensor> tpos, int64_t q_size, int64_t kv_size, int64_t hd,
-                   c10::optional<torch::Tensor> rope) {
-    return gemv(x, w, bias, epi, norm, gamma, beta, eps, resid, kc, vc, tslot, tpos, q_size, kv_size, hd, rope);
-  });
+                   c10::optional<torch::Tensor> rope, c10::optional<torch::Tensor> wscale) {
+    return gemv(x, w, bias, epi, norm, gamma, beta, eps, resid, kc, vc, tslot, tpos, q_size, kv_size, hd, rope,
+                c10::nullopt, wscale);
+  }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("epi"), py::arg("norm"), py::arg("gamma"), py::arg("beta"),
+     py::arg("eps"), py::arg("resid"), py::arg("kc"), py::arg("vc"), py::arg("tslot"), py::arg("tpos"),
+     py::arg("q_size"), py::arg("kv_size"), py::arg("hd"), py::arg("rope"), py::arg("wscale") = py::none());
   // fp32 logits GEMV that also writes the 8-column segment maxima (the sampler's threshold)
   m.def("gemv_logits", [](torch::Tensor x, torch::Tensor w, int64_t norm, c10::optional<torch::Tensor> gamma,
-                          c10::optional<torch::Tensor> beta, double eps, torch::Tensor segmax) {
+                          c10::optional<torch::Tensor> beta, double eps, torch::Tensor segmax,
+                          c10::optional<torch::Tensor> wscale) {
     return gemv(x, w, c10::nullopt, EPI_F32, norm, gamma, beta, eps, c10::nullopt, c10::nullopt,
-                c10::nullopt, c10::nullopt, c10::nullopt, 0, 0, 0, c10::nullopt, segmax);
-  });
+                c10::nullopt, c10::nullopt, c10::nullopt, 0, 0, 0, c10::nullopt, segmax, wscale);
+  }, py::arg("x"), py::arg("w"), py::arg("norm"), py::arg("gamma"), py::arg("beta"), py::arg("eps"),
+     py::arg("segmax"), py::arg("wscale") = py::none());
+  // weight-only FP8 (wquant.hip)
+  m.def("quantize_rows_fp8", &quantize_rows_fp8);
+  m.def("dequant_rows_fp8", &dequant_rows_fp8);
   m.def("silu_mul", &silu_mul);
   m.def("apply_rows", &apply_rows, py::arg("args"), py::arg("b"));
   m.def("penalize", &penalize, py::arg("logits"), py::arg("V"), py::arg("hist"), py::arg("slots"),
@@ -1278,8 +1331,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("qkv_post", &qkv_post);
   // GEMV weight stream with non-temporal loads (A/B knob, LSD_GEMV_NT)
   m.def("gemv_set_nt", [](int64_t v) { lsd_gemv_set_nt((int)v); });
-  m.def("gemv_ok", [](int64_t M, int64_t K, int64_t epi, int64_t norm) {
-    return lsd_gemv_ok((int)M, (int)K, (int)epi, (int)norm) != 0; });
+  m.def("gemv_ok", [](int64_t M, int64_t K, int64_t epi, int64_t norm, bool w_fp8) {
+    return lsd_gemv_ok_w((int)M, (int)K, (int)epi, (int)norm, w_fp8 ? 1 : 0) != 0; },
+    py::arg("M"), py::arg("K"), py::arg("epi"), py::arg("norm"), py::arg("w_fp8") = false);
   m.def("set_stamps", &set_stamps);
   m.def("gemm_last_launch", [] { return std::string(lsd_gemm_last_launch()); });
   m.def("norm_last_launch", [] { return std::string(lsd_norm_last_launch()); });

@@ -18,7 +18,7 @@ from .config import EngineConfig
 def _cfg(args) -> EngineConfig:
     over = {}
     for k in ("model_id", "num_stages", "max_batch", "max_seq_len", "device", "dtype",
-              "weights", "transport", "role", "num_microbatches", "kv_dtype"):
+              "weights", "transport", "role", "num_microbatches", "kv_dtype", "weight_dtype"):
         v = getattr(args, k, None)
         if v is not None:
             over[k] = v
@@ -51,6 +51,8 @@ def main(argv=None) -> int:
     sub.choices["serve"].add_argument("--role")
     sub.choices["serve"].add_argument("--kv-dtype", dest="kv_dtype", choices=("bf16", "fp8_e4m3"),
                                       help="KV cache element type (fp8_e4m3: half the bytes, twice the slots)")
+    sub.choices["serve"].add_argument("--weight-dtype", dest="weight_dtype", choices=("bf16", "fp8_e4m3"),
+                                      help="block linear weights (fp8_e4m3: half the bytes streamed at small batch)")
     sub.choices["serve"].add_argument("--host", default="0.0.0.0")
     sub.choices["serve"].add_argument("--port", type=int,
                                       default=int(os.environ.get("PORT", os.environ.get("SHARD_PORT", "5000"))))

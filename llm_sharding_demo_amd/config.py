@@ -70,6 +70,16 @@ class ModelConfig:
             return 12 * h * h + 13 * h  # qkv+proj+fc+proj weights/biases + 2 LN
         return h * self.qkv_size + self.q_size * h + 3 * h * f + 2 * h
 
+    def block_linears(self) -> dict:
+        """(rows N, row length K) of a block's four linear projections by their
+        weight's name inside the layer: what `weight_dtype="fp8_e4m3"` quantises."""
+        h, f = self.hidden, self.ffn
+        if self.arch == "gpt2":
+            return {"attn.c_attn.weight": (3 * h, h), "attn.c_proj.weight": (h, h),
+                    "mlp.c_fc.weight": (f, h), "mlp.c_proj.weight": (h, f)}
+        return {"self_attn.qkv.weight": (self.qkv_size, h), "self_attn.o_proj.weight": (h, self.q_size),
+                "mlp.gate_up.weight": (2 * f, h), "mlp.down_proj.weight": (h, f)}
+
     def embed_params(self) -> int:
         n = self.vocab_size * self.hidden
         if self.arch == "gpt2":
@@ -727,6 +737,12 @@ class EngineConfig:
     # element, values saturated to +-448, no scale factors): half the bytes the
     # decode attention streams and twice the slots in the same kv_fraction.
     kv_dtype: str = "bf16"
+    # Weights of the blocks' four linear projections: "bf16", or "fp8_e4m3"
+    # (OCP E4M3 rows with one fp32 scale per output row, quantised when a stage
+    # is prepared): half the bytes a small-batch decode step streams, and the
+    # freed memory goes to the KV cache.  Embeddings, lm_head, norms and biases
+    # stay bf16.
+    weight_dtype: str = "bf16"
     # Serving: record per-stage busy / bubble timing on one pipeline session
     # in this many (0 = never) -- it costs a control-plane gather per session.
     metrics_every: int = 16
@@ -776,6 +792,8 @@ class EngineConfig:
     def __post_init__(self):
         if self.kv_dtype not in ("bf16", "fp8_e4m3"):
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8_e4m3', got {self.kv_dtype!r}")
+        if self.weight_dtype not in ("bf16", "fp8_e4m3"):
+            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8_e4m3', got {self.weight_dtype!r}")
         if not (0 <= self.prefix_cache <= self.max_batch):
             raise ValueError("prefix_cache must be in [0, max_batch]: an entry is one of the replica's KV slots")
         if self.prefix_cache_min_tokens < 1:
@@ -831,6 +849,7 @@ class EngineConfig:
             join_max_wait=int(_env("JOIN_MAX_WAIT", "4")),
             kv_fraction=float(_env("KV_FRACTION", "0.85")),
             kv_dtype=_env("KV_DTYPE", "bf16"),
+            weight_dtype=_env("WEIGHT_DTYPE", "bf16"),
             metrics_every=int(_env("METRICS_EVERY", "16")),
             max_logprobs=int(_env("MAX_LOGPROBS", "5")),
             max_logit_edits=int(_env("MAX_LOGIT_EDITS", "300")),

@@ -35,8 +35,10 @@ class StageModel:
                  weights: Optional[Dict[str, torch.Tensor]] = None,
                  units: Optional[Tuple[int, int]] = None, backend=None,
                  variants: Optional[Sequence[Tuple[int, int]]] = None,
-                 kv_dtype: Optional[torch.dtype] = None):
+                 kv_dtype: Optional[torch.dtype] = None, weight_dtype: str = "bf16"):
         self.cfg = cfg
+        # "fp8_e4m3": the backend's prepare_stage quantises the blocks' linear projections
+        self.weight_dtype = weight_dtype
         self.device = torch.device(device)
         if dtype is None:
             dtype = torch.float32 if self.device.type == "cpu" else torch.bfloat16

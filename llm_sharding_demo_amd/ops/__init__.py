@@ -19,6 +19,7 @@ extra kernel launch.
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
@@ -33,6 +34,13 @@ class Residual:
     pending: List[Tuple[torch.Tensor, Optional[torch.Tensor]]] = field(default_factory=list)
 
 
+def dequant_lanes() -> int:
+    """Microbatch lanes (streams, LSD_LANES) a stage's FP8-weight dequant
+    scratch is made for: one bf16 buffer per lane (ops/hip.py prepare_stage;
+    counted by Engine._weight_bytes)."""
+    return min(8, max(1, int(os.environ.get("LSD_LANES", "2"))))
+
+
 class Backend:
     name = "abstract"
 
@@ -44,6 +52,10 @@ class ReferenceBackend(Backend):
     """fp32 PyTorch implementation of the engine ops (CPU golden path)."""
 
     name = "reference"
+
+    def prepare_stage(self, stage) -> None:
+        if getattr(stage, "weight_dtype", "bf16") == "fp8_e4m3":
+            ref.quantize_stage(stage)
 
     def embed(self, ids, pos, wte, wpe):
         return ref.embed(ids, pos, wte, wpe)

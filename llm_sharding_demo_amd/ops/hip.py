@@ -12,6 +12,12 @@ Device weight layout (set up once per stage by `prepare_stage`):
     q and the K cache simply live in that order.
   * Llama gate/up rows interleaved in 16-row blocks so one wave holds the gate
     and up value of the same output column (silu(gate)*up fused epilogue).
+  * `weight_dtype="fp8_e4m3"`: after all of the above (so the scales travel
+    with their rows) the blocks' four linear projections become E4M3 rows with
+    one fp32 scale per row (csrc/kernels/wquant.hip), `w._lsd_scale`.  At
+    M <= gemv_max_m rows the FP8 GEMV streams them as they are; every other
+    GEMM first dequantises the weight into a per-lane bf16 scratch and then
+    runs exactly as it does on a bf16 weight.
 """
 from __future__ import annotations
 
@@ -21,7 +27,7 @@ from typing import Optional
 
 import torch
 
-from . import Backend, Residual
+from . import Backend, Residual, dequant_lanes
 from . import reference as ref
 from .routing import Routing
 
@@ -103,6 +109,7 @@ class LazyNorm:
 # gemv epilogue codes (csrc/kernels/gemm_plan.h Epi)
 _EPI = {"none": 0, "gelu": 1, "silu_mul": 2}
 EPI_F32, EPI_RESID, EPI_QKV = 3, 4, 6
+FP8 = torch.float8_e4m3fn
 # longest row the sampler loads once into registers (sample.hip: CH x NT x 4)
 SAMPLER_ONE_LOAD = 13 * 1024 * 4
 
@@ -178,6 +185,19 @@ class HipBackend(Backend):
         # split-K ticket counters: zero at rest, re-armed by each tile's last
         # arriver; one row per microbatch lane so concurrent lanes never share one
         self._counters = torch.zeros(8, 1 << 16, dtype=torch.int32, device=dev)
+        self._wscratch = None
+        if getattr(stage, "weight_dtype", "bf16") == "fp8_e4m3":
+            # layer by layer, each bf16 tensor freed as it is replaced; a row that
+            # is not whole 16-byte chunks of bytes (tiny-gpt2) stays bf16
+            ref.quantize_stage(stage, self.C.quantize_rows_fp8, keep=lambda t: t.shape[1] % 16 != 0)
+            big = max((t.numel() for t in w.values() if t.dtype == FP8), default=0)
+            if big:
+                # bf16 scratch of the dequant route, one per microbatch lane (indexed
+                # by self.lane like the counters above).  A lane is one stream: the dequant kernel,
+                # the GEMM that reads the scratch and the next layer's dequant
+                # run in that order, so one buffer serves every layer -- in a
+                # captured graph too, whose nodes keep the stream's order.
+                self._wscratch = torch.empty(dequant_lanes(), big, dtype=torch.bfloat16, device=dev)
         stage._hip_prepared = True
 
     @property
@@ -248,28 +268,42 @@ class HipBackend(Backend):
             return self.C.norm(xn.x, None, None, xn.w, xn.b, xn.eps, xn.rms, None, True)
         return xn
 
-    def _gemv_in(self, xn, K: int, epi: int):
+    def _gemv_in(self, xn, K: int, epi: int, w8: bool = False):
         """(x, norm code, gamma, beta, eps) for a GEMV launch, or None when this
-        GEMM does not run on the GEMV (the caller takes the MFMA path)."""
+        GEMM does not run on the GEMV (the caller takes the MFMA path).  `w8`:
+        the weight is FP8 rows (the GEMV's FP8 variant answers)."""
         M = xn.shape[0]
         if M > self.R.gemv_max_m:
             return None
         if isinstance(xn, LazyNorm):
-            if self.C.gemv_ok(M, K, epi, xn.code):
+            if self.C.gemv_ok(M, K, epi, xn.code, w8):
                 return xn.x, xn.code, xn.w, xn.b, xn.eps
             xn = self.materialize(xn)
-        if self.C.gemv_ok(M, K, epi, 0):
+        if self.C.gemv_ok(M, K, epi, 0, w8):
             return xn, 0, None, None, 0.0
         return None
 
+    @staticmethod
+    def _ws(w) -> dict:
+        """The GEMV's extra argument for an FP8 weight: its row scales."""
+        return {"wscale": w._lsd_scale} if w.dtype == FP8 else {}
+
+    def _dense(self, w):
+        """The weight a GEMM other than the FP8 GEMV reads: an FP8 weight is
+        dequantised into this lane's scratch (wquant.hip), a bf16 one is itself."""
+        if w.dtype != FP8:
+            return w
+        return self.C.dequant_rows_fp8(w, w._lsd_scale, self._wscratch[self.lane % self._wscratch.shape[0]])
+
     def qkv_kv_append(self, xn, w, b, cache_k, cache_v, meta, mcfg):
-        g = self._gemv_in(xn, w.shape[1], EPI_QKV)
+        g = self._gemv_in(xn, w.shape[1], EPI_QKV, w.dtype == FP8)
         if g is not None:
             x, nc, gw, gb, eps = g
             return self.C.gemv(x, w, b, EPI_QKV, nc, gw, gb, eps, None, cache_k, cache_v,
                                meta.token_slots, meta.token_pos, mcfg.q_size, mcfg.kv_size,
-                               mcfg.head_dim, self._rope)
+                               mcfg.head_dim, self._rope, **self._ws(w))
         xn = self.materialize(xn)
+        w = self._dense(w)
         if self.R.blaslt_qkv(xn.shape[0], w.shape[1], getattr(self, "decode", False)) and xn.is_contiguous():
             y = self.C.blaslt_f32(xn, w, self.lane)
             if y is not None:
@@ -295,12 +329,13 @@ class HipBackend(Backend):
 
     def linear(self, a, w, b=None, act: str = "none"):
         code = _EPI[act]
-        g = self._gemv_in(a, w.shape[1], code)
+        g = self._gemv_in(a, w.shape[1], code, w.dtype == FP8)
         if g is not None:
             x, nc, gw, gb, eps = g
             return self.C.gemv(x, w, b, code, nc, gw, gb, eps, None, None, None, None, None,
-                               0, 0, 0, None)
+                               0, 0, 0, None, **self._ws(w))
         a = self.materialize(a)
+        w = self._dense(w)
         dec = getattr(self, "decode", False)
         if code == 1 and self.R.blaslt_gelu(a.shape[0], dec) and a.is_contiguous():
             y = self.C.blaslt_linear(a, w, b, code, self.lane)
@@ -316,10 +351,11 @@ class HipBackend(Backend):
     def linear_residual(self, a, w, b, r: Residual) -> None:
         M, K = a.shape
         N = w.shape[0]
-        if self._gemv_in(a, K, EPI_RESID) is not None:  # adds straight into r.x
+        if self._gemv_in(a, K, EPI_RESID, w.dtype == FP8) is not None:  # adds straight into r.x
             self.C.gemv(a, w, b, EPI_RESID, 0, None, None, 0.0, r.x, None, None, None, None,
-                        0, 0, 0, None)
+                        0, 0, 0, None, **self._ws(w))
             return
+        w = self._dense(w)
         if self.R.blaslt_resid(M, K, self._decode) and a.is_contiguous() \
                 and self.C.blaslt_residual(a, w, b, r.x, self.lane):
             return

@@ -47,9 +47,46 @@ def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
     return xf * torch.rsqrt(var + eps) * w.float()
 
 
+def quantize_rows(w: torch.Tensor):
+    """Weight-only FP8: w [N, K] -> (q float8_e4m3fn [N, K], scale fp32 [N]).
+    scale[n] = max |w[n, :]| / 448 (1 for a row of zeros), q = rne(clamp(w /
+    scale, +-448)); every step is one fp32 operation (IEEE divisions by a
+    tensor, never a reciprocal multiply), clamped ahead of the cast as kv_append
+    does, so csrc/kernels/wquant.hip reproduces it bit for bit."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax == 0, torch.ones_like(amax), amax / torch.full_like(amax, 448.0))
+    q = (wf / scale[:, None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    return q, scale
+
+
+def dequantize_rows(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    return q.float() * scale[:, None]
+
+
+def quantize_stage(stage, quantize=quantize_rows, keep=lambda w: False) -> None:
+    """Replace the four linear projections of every block a stage owns by
+    their FP8 rows, one tensor at a time (each original is dropped as it is
+    replaced); the scales ride on the tensor as `_lsd_scale`.  `keep(w)`: a
+    weight the backend cannot take in FP8 stays as it is."""
+    p = "h." if stage.cfg.arch == "gpt2" else "layers."
+    for i in stage.layers:
+        for name in stage.cfg.block_linears():
+            key = f"{p}{i}.{name}"
+            if key not in stage.w or keep(stage.w[key]):  # a boundary layer may hold one half only
+                continue
+            q, scale = quantize(stage.w.pop(key))
+            q._lsd_scale = scale
+            stage.w[key] = q
+
+
 def linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """a [T, K] @ w[N, K]^T (+ bias) in fp32."""
-    out = a.float() @ w.float().t()
+    """a [T, K] @ w[N, K]^T (+ bias) in fp32; an FP8 weight (quantize_rows) is
+    dequantised first."""
+    if w.dtype == torch.float8_e4m3fn:
+        out = a.float() @ dequantize_rows(w, w._lsd_scale).t()
+    else:
+        out = a.float() @ w.float().t()
     if bias is not None:
         out = out + bias.float()
     return out

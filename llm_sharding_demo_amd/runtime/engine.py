@@ -42,6 +42,7 @@ from ..config import EngineConfig, SamplingParams
 from ..guide import GuideRows
 from ..utils import racecheck
 from ..models.stage import StageModel
+from ..ops import dequant_lanes
 from ..parallel.comm import (DeviceLoopFabric, GlooPlanChannel, LocalFabric, LocalPlanChannel,
                              Transport, TransportError, init_distributed, make_plan_channel,
                              open_data_plane, transport_chain)
@@ -339,7 +340,14 @@ class Engine(racecheck.Shared):
         mc = self.mcfg
         a, b = self.unit_plan[i]
         per_layer = mc.block_params() * 2
-        n = per_layer * (b - a) // 2
+        scratch = 0
+        if self.cfg.weight_dtype == "fp8_e4m3":
+            # one byte per quantised element and an fp32 scale per row, plus the
+            # HIP backend's per-lane bf16 dequant scratch (ops/hip.py prepare_stage)
+            lin = mc.block_linears().values()
+            per_layer += sum(4 * n_ - n_ * k_ for n_, k_ in lin)
+            scratch = dequant_lanes() * 2 * max(n_ * k_ for n_, k_ in lin) if b > a else 0
+        n = per_layer * (b - a) // 2 + scratch
         if i == 0:
             n += mc.embed_params() * 2
         if i == self.P - 1 and not (i == 0 and mc.tie_embeddings):
@@ -356,7 +364,7 @@ class Engine(racecheck.Shared):
                           weights_path=self.cfg.weights, max_slots=self.kv_slots + 2,
                           max_seq=self.max_seq, units=self.unit_plan[i],
                           variants=[p[i] for p in self.unit_plans] if self.unit_plans else None,
-                          kv_dtype=kv_dtype_of(self.cfg.kv_dtype)[0])
+                          kv_dtype=kv_dtype_of(self.cfg.kv_dtype)[0], weight_dtype=self.cfg.weight_dtype)
 
     def _worker(self, st: StageModel, t, i: int) -> StageWorker:
         if self.cfg.wire_dtype not in ("fp32", "bf16"):
@@ -378,6 +386,7 @@ class Engine(racecheck.Shared):
     def kv_info(self) -> dict:
         st = self.stages[0]
         return {"kv_slots": self.kv_slots, "kv_bytes_stage0": st.kv.nbytes, "kv_dtype": self.cfg.kv_dtype,
+                "weight_dtype": self.cfg.weight_dtype,
                 "kv_slots_free": sum(p.available for p in self.slot_pools),
                 "group_rows": self.group_cap, "groups": self.M,
                 # half-layer unit ranges per stage: one plan, or (even, odd) group plans

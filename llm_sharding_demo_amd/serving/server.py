@@ -399,6 +399,7 @@ def create_app(cfg: EngineConfig, engine=None, shard: Optional[ShardRunner] = No
                       "kv_slots_total": kv["kv_slots"] * engine.R,
                       "kv_cache_bytes_stage0": kv["kv_bytes_stage0"],
                       "kv_cache_fp8_e4m3": 1 if kv["kv_dtype"] == "fp8_e4m3" else 0,
+                      "weights_fp8_e4m3": 1 if kv["weight_dtype"] == "fp8_e4m3" else 0,
                       "queue_depth": sch.queue_depth,
                       "max_batch_rows_seen": sch.stats["max_rows"]}
             counters = {"pipeline_steps_total": sch.stats["steps"],

@@ -28,7 +28,8 @@ from ..runtime.kv_cache import kv_dtype_of
 
 
 def compare_with_golden(model_id, prompts: List[List[int]], steps: int = 8,
-                        device: str = "cuda", seed: int = 0, inject=1.0, kv_dtype=None):
+                        device: str = "cuda", seed: int = 0, inject=1.0, kv_dtype=None,
+                        weight_dtype: str = "bf16"):
     """`inject` scales the HIP logits' deviation from the golden before it is
     measured (1.0: as computed); a tuple of factors returns one result per
     factor from the same forward passes.  The gate tests use 3.0 to show that
@@ -39,7 +40,18 @@ def compare_with_golden(model_id, prompts: List[List[int]], steps: int = 8,
     fp32 golden's ops over a cache of that dtype -- the cost of the cache
     format alone.  All three are fed the fp32 golden's tokens, and the result
     is {"golden_kv": metrics of golden/kv_dtype vs golden/fp32,
-        "hip_kv":    metrics of HIP/kv_dtype vs golden/fp32}."""
+        "hip_kv":    metrics of HIP/kv_dtype vs golden/fp32}.
+
+    `weight_dtype="fp8_e4m3"` gives the HIP model FP8 weights (EngineConfig's
+    field).  Its reference is then the fp32 golden over the *dequantised*
+    weights -- the same numbers the kernels multiply by -- and the result is
+    {"hip_w":    metrics of HIP/FP8 weights vs golden over dequantised weights,
+     "golden_w": metrics of that golden vs the golden over the bf16 weights:
+                 the quantisation's own cost}."""
+    if weight_dtype != "bf16":
+        if kv_dtype is not None:
+            raise ValueError("compare_with_golden: one of kv_dtype / weight_dtype at a time")
+        return _compare_weight_dtype(model_id, prompts, steps, device, seed, inject, weight_dtype)
     if isinstance(kv_dtype, str):  # an EngineConfig.kv_dtype name; "bf16" is the default cache
         kv_dtype = kv_dtype_of(kv_dtype)[0]
     mc = get_model_config(model_id) if isinstance(model_id, str) else model_id
@@ -95,6 +107,59 @@ def compare_with_golden(model_id, prompts: List[List[int]], steps: int = 8,
                         "per_step": [round(float(x.max()), 4) for x in errs[c][i]]})
         res.append(out if isinstance(inject, (tuple, list)) else out[0])
     return res[0] if kv_dtype is None else {"golden_kv": res[0], "hip_kv": res[1]}
+
+
+def _compare_weight_dtype(model_id, prompts, steps, device, seed, inject, weight_dtype):
+    """compare_with_golden(weight_dtype=): see there.  The golden over the
+    dequantised weights is the reference backend's own FP8 path (it dequantises
+    in ref.linear), whose quantiser the HIP one matches bit for bit."""
+    mc = get_model_config(model_id) if isinstance(model_id, str) else model_id
+    dev = torch.device(device)
+    L = mc.n_layers
+    max_seq = max(len(p) for p in prompts) + steps + 1
+    B = len(prompts)
+    w = init_stage_weights(mc, range(L), True, True, seed, dev, torch.bfloat16)
+    mk = lambda dt, ww, be, wd: StageModel(mc, 0, L, True, True, device=dev, dtype=dt, weights=ww,  # noqa: E731
+                                           max_slots=B, max_seq=max_seq, backend=be, weight_dtype=wd)
+    gold = mk(torch.float32, {k: v.float() for k, v in w.items()}, ReferenceBackend(), weight_dtype)
+    gold16 = mk(torch.float32, {k: v.float() for k, v in w.items()}, ReferenceBackend(), "bf16")
+    hip = mk(torch.bfloat16, w, None, weight_dtype)
+    del w
+    V = mc.vocab_size
+    slots = list(range(B))
+    factors = tuple(inject) if isinstance(inject, (tuple, list)) else (inject,)
+    flat = torch.tensor([t for p in prompts for t in p], dtype=torch.int32, device=dev)
+    # (candidate, its reference): HIP vs the golden it shares weights with, that golden vs the bf16 one
+    pairs = [(hip, gold), (gold, gold16)]
+    errs = [[[] for _ in factors] for _ in pairs]
+    agree = [[0] * len(factors) for _ in pairs]
+    rows = 0
+    with torch.no_grad():
+        meta = lambda: BatchMeta.build(slots, [0] * B, [len(p) for p in prompts], dev)  # noqa: E731
+        for step in range(steps + 1):
+            out = {id(m): m.forward(meta(), inp)[:, :V].float() for m, inp in
+                   ((m, flat if step == 0 else tok) for m in (gold, gold16, hip))}
+            for c, (cand, refm) in enumerate(pairs):
+                lg, lh = out[id(refm)], out[id(cand)]
+                std = lg.std(dim=1, keepdim=True)
+                for i, f in enumerate(factors):
+                    lf = lh if f == 1.0 else lg + f * (lh - lg)
+                    errs[c][i].append(((lf - lg).abs().amax(dim=1, keepdim=True) / std).squeeze(1))
+                    agree[c][i] += int((lf.argmax(1) == lg.argmax(1)).sum())
+            rows += B
+            tok = out[id(gold)].argmax(1).to(torch.int32)  # teacher forcing: the golden's tokens
+            pos = [len(p) + step for p in prompts]
+            meta = lambda: BatchMeta.decode(slots, pos, dev, max(pos) + 1)  # noqa: E731
+    res = []
+    for c in range(len(pairs)):
+        o = []
+        for i in range(len(factors)):
+            e = torch.cat(errs[c][i])
+            o.append({"rows": rows, "top1_agreement": agree[c][i] / rows, "max_rel_err": float(e.max()),
+                      "mean_rel_err": float(e.mean()),
+                      "per_step": [round(float(x.max()), 4) for x in errs[c][i]]})
+        res.append(o if isinstance(inject, (tuple, list)) else o[0])
+    return {"hip_w": res[0], "golden_w": res[1]}
 
 
 class Bf16EmulationBackend(ReferenceBackend):

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""bf16-weight vs FP8-weight GEMV (csrc/kernels/gemv.hip) over the per-layer
+shapes of GPT-2 XL and Llama-3 8B at M = 1, 2, 4, 8 rows.
+
+    python tools/weight_fp8_ab.py [--label NAME] [--hot]
+
+Each launch reads another copy of the weight (enough copies to pass 1 GiB, so
+no copy is still cached when its turn comes again; --hot: one copy, the
+cache-resident figure).  The QKV shapes run the plain bf16 epilogue (no cache
+to append to); the others run the epilogue the model uses.  One JSON line per
+case: median of 5 rounds of graph-replayed launches, weight bytes per us, and
+the FP8 speed-up against the byte ratio of 2."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from sampler_topp_ab import timeit  # noqa: E402
+
+# (model, projection, N, K, epilogue: 0 bf16, 1 gelu, 2 silu_mul, 4 residual)
+SHAPES = [("gpt2-xl", "c_attn", 4800, 1600, 0), ("gpt2-xl", "attn.c_proj", 1600, 1600, 4),
+          ("gpt2-xl", "c_fc", 6400, 1600, 1), ("gpt2-xl", "mlp.c_proj", 1600, 6400, 4),
+          ("llama-3-8b", "qkv", 6144, 4096, 0), ("llama-3-8b", "o_proj", 4096, 4096, 4),
+          ("llama-3-8b", "gate_up", 28672, 4096, 2), ("llama-3-8b", "down_proj", 4096, 14336, 4)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--label", default="this")
+    ap.add_argument("--hot", action="store_true")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    from llm_sharding_demo_amd.ops.hip import _load
+
+    C = _load()
+    dev = "cuda"
+    for model, name, N, K, epi in SHAPES:
+        g = torch.Generator(device=dev).manual_seed(1)
+        copies = 1 if a.hot else max(2, -(-(1 << 30) // (N * K)))
+        w16 = [(torch.randn(N, K, device=dev, generator=g) * 0.03).bfloat16() for _ in range(copies)]
+        w8 = [C.quantize_rows_fp8(w) for w in w16]
+        bias = None if epi == 2 else torch.zeros(N, dtype=torch.bfloat16, device=dev)
+        for M in (1, 2, 4, 8):
+            if not (C.gemv_ok(M, K, epi, 0) and C.gemv_ok(M, K, epi, 0, True)):
+                continue
+            x = torch.randn(M, K, device=dev, generator=g).bfloat16()
+            res = torch.zeros(M, N, device=dev) if epi == 4 else None
+            turn = [0, 0]
+
+            def run16():
+                turn[0] += 1
+                C.gemv(x, w16[turn[0] % len(w16)], bias, epi, 0, None, None, 0.0, res, None, None, None, None,
+                       0, 0, 0, None)
+
+            def run8():
+                turn[1] += 1
+                q, s = w8[turn[1] % len(w8)]
+                C.gemv(x, q, bias, epi, 0, None, None, 0.0, res, None, None, None, None, 0, 0, 0, None, wscale=s)
+
+            iters = max(len(w16), 64)
+            t16 = statistics.median(timeit(run16, iters=iters) for _ in range(5))
+            t8 = statistics.median(timeit(run8, iters=iters) for _ in range(5))
+            print(json.dumps({"label": a.label, "model": model, "proj": name, "N": N, "K": K, "M": M,
+                              "hot": a.hot, "bf16_us": round(t16, 2), "fp8_us": round(t8, 2),
+                              "bf16_bytes_per_us": round(2 * N * K / t16), "fp8_bytes_per_us": round(N * K / t8),
+                              "speedup": round(t16 / t8, 3)}), flush=True)
+        del w16, w8
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
