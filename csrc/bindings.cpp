@@ -10,113 +10,12 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 
-#include "kernels/gemm_params.h"
-#include "kernels/gemm_plan.h"
+#include "kernels/api.h"
 
 typedef lsd_bf16_t bf16;
 using lsd::GemmParams;
 using lsd::GemmPlan;
 using lsd::GemvParams;
-
-extern "C" {
-// the one launch decision (kernels/gemm_plan.h) under the current tuning, and the launch of exactly that plan
-void lsd_gemm_plan(int M, int N, int K, int splits, int epi, int kind, GemmPlan* out);
-hipError_t lsd_gemm(const GemmParams* p, const GemmPlan* plan, int* cnt, float* ws, hipStream_t st);
-const char* lsd_gemm_last_launch();
-const char* lsd_norm_last_launch();
-void lsd_gemm_set_big_min(int v);
-void lsd_gemm_set_big_group(int v);
-void lsd_gemm_set_big_kind(int v);
-void lsd_gemm_set_tiled3_max(int v);
-void lsd_gemm_set_ring_slots(int v);
-void lsd_gemm_set_ring_tn(int v);
-void lsd_gemm_set_ring_fill(int v);
-void lsd_gemm_set_ring_m96(int v);
-void lsd_gemm_set_d256_slots(int v);
-void lsd_gemm_set_ring8(int v);
-void lsd_gemm_set_ring8_flags(int v);
-void lsd_gemm_set_ring8_pack(int v);
-void lsd_norm_set_wave_narrow_min(int v);
-void lsd_norm_set_wave_min(int v);
-int lsd_gemm_d256_bn(int kind, int M, int N, int K);
-int lsd_gemm_ring8_tiles(int M, int N, int K, int S);
-void lsd_attn_set_max_wg(int v);
-void lsd_attn_set_small_waves(int v);
-void lsd_attn_set_small_waves128(int v);
-void lsd_attn_set_large_waves(int hd, int v);
-void lsd_attn_set_mfma_min(int v);
-int lsd_gemm_sk_rblocks(int M, int N, int S);
-int lsd_gemm_sk_nw(int M, int epi);
-void lsd_gemm_set_nw2_rows(int v);
-void lsd_gemm_set_sk_rows(int v);
-hipError_t lsd_embed(const int* ids, const int* pos, const bf16* wte, const bf16* wpe, float* out,
-                     int T, int H, int vocab, hipStream_t st);
-hipError_t lsd_norm(float* x, const void* slab, int slab_bf16, int splits, const bf16* pbias, const bf16* w,
-                    const bf16* b, bf16* out, int T, int H, float eps, int rms, const int* rows,
-                    int nrows, hipStream_t st);
-hipError_t lsd_attn_decode(const bf16* q, long ldq, const bf16* kc, const bf16* vc,
-                           const int* seq_slots, const int* qpos, bf16* out, long ldo,
-                           float* part_o, float* part_ml, int B, int nh, int n_kv, int hd,
-                           int max_seq, int splits, float scale_log2, int kv_elt, hipStream_t st);
-hipError_t lsd_attn_prefill(const bf16* q, long ldq, const bf16* kc, const bf16* vc,
-                            const int* tiles, int n_tiles, const int* seq_slots,
-                            const int* q_start, const int* cu_q, bf16* out, long ldo, int nh,
-                            int n_kv, int hd, int max_seq, float scale_log2, int kv_elt, hipStream_t st);
-hipError_t lsd_attn_oproj(const bf16* q, long ldq, const bf16* kc, const bf16* vc,
-                          const int* seq_slots, const int* qpos, int B, int nh, int n_kv, int hd,
-                          int max_seq, float scale_log2, const bf16* W, long ldw, const bf16* bias,
-                          float* x, int N, int NC, float* part, int* cnt, hipStream_t st);
-int lsd_gemv_ok(int M, int K, int epi, int norm);
-void lsd_gemv_set_nt(int v);
-hipError_t lsd_gemv(const lsd::GemvParams* p, int epi, int norm, hipStream_t st);
-int lsd_gemv_ok_w(int M, int K, int epi, int norm, int w_fp8);
-hipError_t lsd_gemv_fp8(const lsd::GemvParams* p, const float* wscale, int epi, int norm, hipStream_t st);
-hipError_t lsd_quantize_rows_fp8(const void* W, long ldw, void* q, float* scale, int N, int K, hipStream_t st);
-hipError_t lsd_dequant_rows_fp8(const void* q, const float* scale, void* out, int N, int K, hipStream_t st);
-hipError_t lsd_apply_rows(const int64_t* args, int nargs, int b, hipStream_t st);
-hipError_t lsd_silu_mul(const lsd_bf16_t* y, long ldy, lsd_bf16_t* out, long ldo, int M, int F, hipStream_t st);
-hipError_t lsd_qkv_post(const float* y, long ldy, const lsd_bf16_t* bias, const int* tslot, const int* tpos,
-                        const float* rope, lsd_bf16_t* q, lsd_bf16_t* kc, lsd_bf16_t* vc, int M, int q_size,
-                        int kv_size, int hd, int n_kv, int max_seq, int kv_fp8, hipStream_t st);
-hipError_t lsd_sample(const float* logits, long ld, int B, int V, const float* temp,
-                      const int* topk, const int* greedy, const long long* seeds,
-                      long long* step, int* out, int advance, const int* active, int* pos,
-                      const float* segmax, long ldseg, const float* top_p, const float* min_p,
-                      hipStream_t st);
-hipError_t lsd_penalize(float* logits, long ld, int B, int V, const int* hist, int L, int nslots, const int* slots,
-                        const long long* counts, const float* presence, const float* frequency, float* segmax,
-                        long ldseg, hipStream_t st);
-hipError_t lsd_record_tokens(int* hist, int L, int nslots, const int* slots, const long long* step, int back,
-                             const int* tokens, const int* active, int B, hipStream_t st);
-hipError_t lsd_logit_edits(float* logits, long ld, int B, int V, const int* cnt, const int* tok, const float* val,
-                           const int* until, int E, int nslots, const int* slots, const long long* step,
-                           float* segmax, long ldseg, hipStream_t st);
-hipError_t lsd_allow_mask(float* logits, long ld, int B, int V, const int* on, const int* bits, int W, int nslots,
-                          const int* slots, float* segmax, long ldseg, hipStream_t st);
-hipError_t lsd_kv_fork(void* buf, int outer, int slots, int heads, int max_seq, long row_bytes, const int* src,
-                       const int* dst, const int* len, int F, int max_len, hipStream_t st);
-hipError_t lsd_bad_words(float* logits, long ld, int B, int V, const int* cnt, const int* end, int N, const int* btok,
-                         int T, const int* plen, const int* ctok, int L, int nslots, const int* slots,
-                         const long long* step, float* segmax, long ldseg, hipStream_t st);
-hipError_t lsd_guide_mask(float* logits, long ld, int B, int V, const short* gcls, long Vp, const short* gnext,
-                          long cells, const int* gdim, int G, const int* gsl, int nslots, const int* slots,
-                          float* segmax, long ldseg, hipStream_t st);
-hipError_t lsd_guide_advance(int* gsl, int nslots, const short* gcls, long Vp, const short* gnext, long cells,
-                             const int* gdim, int G, int V, const int* slots, const int* tokens, const int* active,
-                             int B, hipStream_t st);
-hipError_t lsd_repeat_penalty(float* logits, long ld, int B, int V, const int* plen, const float* rpen, const int* ngram,
-                              const int* tok, int L, int nslots, const int* slots, const long long* step,
-                              float* segmax, long ldseg, hipStream_t st);
-hipError_t lsd_record_context(int* tok, int L, int nslots, const int* plen, const int* slots, const long long* step,
-                              int back, const int* tokens, const int* active, int B, hipStream_t st);
-hipError_t lsd_logprobs(const float* logits, long ld, int B, int V, const int* tokens, const int* nlp, const int* slots,
-                        const long long* step, int back, const int* active, float* lp_tok, int* lp_top_id,
-                        float* lp_top, int L, int nslots, int W, hipStream_t st);
-int lsd_score_slices(int T, int Vp);
-hipError_t lsd_lm_head_score(const void* xn, long lda, const void* w, long ldw, const int* targets, int T, int V,
-                             int Vp, int K, int S, float* part, float* tok_lp, int* top_id, float* top_lp,
-                             hipStream_t st);
-}
 
 namespace {
 
@@ -152,21 +51,108 @@ void set_stamps(c10::optional<torch::Tensor> t) {
   g_stamps = reinterpret_cast<long long*>(t->data_ptr<int64_t>());
 }
 
+bool aligned16(const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+
 void need_rows(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1, name, " must be 2-D with unit last stride");
   TORCH_CHECK(t.stride(0) % 8 == 0, name, " row stride must be a multiple of 8 elements");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+  TORCH_CHECK(aligned16(t), name, " must be 16-byte aligned");
 }
 
 const bf16* bptr(const torch::Tensor& t) { return reinterpret_cast<const bf16*>(t.data_ptr()); }
 bf16* bptr_mut(const torch::Tensor& t) { return reinterpret_cast<bf16*>(t.data_ptr()); }
 
-const bf16* opt_bias(const c10::optional<torch::Tensor>& b, int N) {
+// align16 = false: the GEMV, which reads its bias one element at a time (gemv_body.h)
+const bf16* opt_bias(const c10::optional<torch::Tensor>& b, int N, bool align16 = true) {
   if (!b.has_value()) return nullptr;
   need(*b, torch::kBFloat16, "bias");
   TORCH_CHECK(b->is_contiguous() && b->numel() == N, "bias must be contiguous [N]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(b->data_ptr()) % 16 == 0, "bias must be 16-byte aligned");
+  TORCH_CHECK(!align16 || aligned16(*b), "bias must be 16-byte aligned");
   return bptr(*b);
+}
+
+// One value per row (or token): a contiguous GPU tensor of n elements of T's
+// dtype -- float, int (int32) or long long (int64), const or not.  `what` is
+// the entry point.  The optional form returns null for an absent tensor.
+template <class T>
+T* row_vec(const torch::Tensor& t, int64_t n, const char* what, const char* name) {
+  using E = std::remove_const_t<T>;
+  static_assert(std::is_same_v<E, float> || std::is_same_v<E, int> || std::is_same_v<E, long long>, "row_vec dtype");
+  const auto dt = std::is_same_v<E, float> ? torch::kFloat32 : std::is_same_v<E, int> ? torch::kInt32 : torch::kInt64;
+  need(t, dt, name);
+  TORCH_CHECK(t.numel() == n && t.is_contiguous(), what, ": ", name, " must be contiguous ", dt, " [", n, "]");
+  return static_cast<T*>(t.data_ptr());
+}
+template <class T>
+T* row_vec(const c10::optional<torch::Tensor>& t, int64_t n, const char* what, const char* name) {
+  return t.has_value() ? row_vec<T>(*t, n, what, name) : nullptr;
+}
+
+// The logits of the draw passes: fp32 [B, width] with unit last stride, their
+// first V columns the vocabulary; v_min <= V, and V <= width unless the
+// launcher is the one to refuse that (v_in_row = false).  Returns B.
+int64_t need_logits(const torch::Tensor& logits, int64_t V, const char* what, int64_t v_min = 1, bool v_in_row = true) {
+  need(logits, torch::kFloat32, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= v_min && (!v_in_row || V <= logits.size(1)), what,
+              ": logits must be fp32 [B, >= V] with unit last stride, V >= ", v_min);
+  return logits.size(0);
+}
+
+// linear_f32's maxima of the 8-column segments of `logits`, which a pass that
+// rewrites logits repairs: fp32 [B, n] with unit last stride.
+//   SEG_EXACT  n == width / 8 for rows of whole segments at a stride of whole segments
+//   SEG_DENSE  n >= width / 8 beside dense logits rows (the caller checks those)
+// Returns (null, 0) for an absent tensor, else the pointer and its row stride.
+enum SegContract { SEG_EXACT, SEG_DENSE };
+std::pair<float*, long> opt_segmax(const c10::optional<torch::Tensor>& segmax, const torch::Tensor& logits,
+                                   SegContract contract) {
+  if (!segmax.has_value()) return {nullptr, 0};
+  need(*segmax, torch::kFloat32, "segmax");
+  const int64_t B = logits.size(0), ld = logits.size(1);
+  TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B, "segmax must be fp32 [B, n]");
+  if (contract == SEG_EXACT) {
+    TORCH_CHECK(ld % 8 == 0 && logits.stride(0) % 8 == 0 && segmax->size(1) == ld / 8,
+                "segmax must be fp32 [B, logits row length / 8] (row length and stride % 8 == 0)");
+    return {segmax->data_ptr<float>(), segmax->stride(0)};
+  }
+  TORCH_CHECK(segmax->size(1) * 8 >= ld, "segmax must be fp32 [B, >= logits row length / 8]");
+  return {segmax->data_ptr<float>(), B <= 1 ? segmax->size(1) : segmax->stride(0)};
+}
+
+// A KV cache pair: contiguous [slots, n_kv, max_seq, hd], bf16 or FP8 alike
+// (need_kv), 16-byte aligned for every kernel but the GEMV, which stores one
+// element at a time (gemv_body.h).  Returns 1 for FP8.
+int check_cache(const torch::Tensor& kc, const torch::Tensor& vc, bool align16 = true) {
+  const int fp8 = need_kv(kc, vc);
+  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() && kc.sizes() == vc.sizes(),
+              "caches must be contiguous [slots, n_kv, max_seq, hd]");
+  TORCH_CHECK(!align16 || (aligned16(kc) && aligned16(vc)), "caches must be 16-byte aligned");
+  return fp8;
+}
+
+// Where a QKV epilogue writes: the caches, of kv_size = n_kv * hd columns per
+// token; the cache slot and position of each of the M tokens; the optional
+// RoPE table, fp32 [>= max_seq, hd / 2, 2].  Fills the fields of that name in
+// p (GemmParams or GemvParams).  What a kernel asks of hd beyond this is its
+// entry point's to check.
+template <class P>
+void qkv_target(P& p, int64_t M, const torch::Tensor& kc, const torch::Tensor& vc, const torch::Tensor& tslot,
+                const torch::Tensor& tpos, int64_t q_size, int64_t kv_size, int64_t hd,
+                const c10::optional<torch::Tensor>& rope, const char* what, bool align16 = true) {
+  p.kv_fp8 = check_cache(kc, vc, align16);
+  TORCH_CHECK(kc.size(3) == hd && kc.size(1) * hd == kv_size, "cache shape mismatch");
+  p.kc = bptr_mut(kc); p.vc = bptr_mut(vc);
+  p.tslot = row_vec<const int>(tslot, M, what, "token_slots");
+  p.tpos = row_vec<const int>(tpos, M, what, "token_pos");
+  p.q_size = q_size; p.kv_size = kv_size; p.hd = hd;
+  p.max_seq = kc.size(2); p.n_kv = kc.size(1);
+  p.rope = nullptr;
+  if (rope.has_value()) {
+    need(*rope, torch::kFloat32, "rope");
+    TORCH_CHECK(rope->is_contiguous() && rope->dim() == 3 && rope->size(1) == hd / 2 && rope->size(2) == 2 &&
+                rope->size(0) >= p.max_seq, "rope table must be [>=max_seq, hd/2, 2]");
+    p.rope = rope->data_ptr<float>();
+  }
 }
 
 // Slab dtype of split-K residual projections: LSD_SLAB_BF16 (default 1),
@@ -290,7 +276,7 @@ c10::optional<torch::Tensor> linear_residual(torch::Tensor a, torch::Tensor w,
   need(x, torch::kFloat32, "x");
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && x.size(0) == p.M && x.size(1) == p.N,
               "residual x must be contiguous [M, N]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "residual x must be 16-byte aligned");
+  TORCH_CHECK(aligned16(x), "residual x must be 16-byte aligned");
   if (p.M == 0) return c10::nullopt;
   if ((tiled || defer) && (splits > 1 || (defer && tiled))) {
     // bf16 partial slabs (LSD_SLAB_BF16=0: fp32): half the bytes the GEMM
@@ -320,28 +306,9 @@ torch::Tensor linear_qkv(torch::Tensor a, torch::Tensor w, c10::optional<torch::
                          c10::optional<torch::Tensor> counters) {
   GemmParams p = base_params(a, w, tiled);
   p.bias = opt_bias(bias, p.N);
-  p.kv_fp8 = need_kv(kc, vc);
-  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.sizes() == kc.sizes() && vc.is_contiguous(),
-              "caches must be contiguous [slots, n_kv, max_seq, hd]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(kc.data_ptr()) % 16 == 0 &&
-              reinterpret_cast<uintptr_t>(vc.data_ptr()) % 16 == 0, "caches must be 16-byte aligned");
-  TORCH_CHECK(kc.size(3) == hd && kc.size(1) * hd == kv_size, "cache shape mismatch");
+  qkv_target(p, p.M, kc, vc, tslot, tpos, q_size, kv_size, hd, rope, "linear_qkv");
   TORCH_CHECK(p.N == q_size + 2 * kv_size, "w rows must be q_size + 2*kv_size");
   TORCH_CHECK(q_size % hd == 0 && hd % 16 == 0, "bad head dims");
-  need(tslot, torch::kInt32, "token_slots");
-  need(tpos, torch::kInt32, "token_pos");
-  TORCH_CHECK(tslot.numel() == p.M && tpos.numel() == p.M && tslot.is_contiguous() &&
-              tpos.is_contiguous(), "token_slots/token_pos must be contiguous [M]");
-  p.kc = bptr_mut(kc); p.vc = bptr_mut(vc);
-  p.tslot = tslot.data_ptr<int>(); p.tpos = tpos.data_ptr<int>();
-  p.q_size = q_size; p.kv_size = kv_size; p.hd = hd;
-  p.max_seq = kc.size(2); p.n_kv = kc.size(1);
-  if (rope.has_value()) {
-    need(*rope, torch::kFloat32, "rope");
-    TORCH_CHECK(rope->is_contiguous() && rope->dim() == 3 && rope->size(1) == hd / 2 &&
-                rope->size(2) == 2 && rope->size(0) >= p.max_seq, "rope table must be [>=max_seq, hd/2, 2]");
-    p.rope = rope->data_ptr<float>();
-  }
   auto q = torch::empty({p.M, q_size}, a.options());
   if (p.M == 0) return q;
   p.out = q.data_ptr(); p.ldo = q_size;
@@ -375,7 +342,7 @@ c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optiona
     TORCH_CHECK(wscale->is_contiguous() && wscale->numel() == w.size(0), "wscale must be contiguous [N]");
   }
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1, "x must be 2-D with unit last stride");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "x must be 16-byte aligned");
+  TORCH_CHECK(aligned16(x), "x must be 16-byte aligned");
   GemvParams p{};
   p.M = x.size(0); p.K = x.size(1); p.N = w.size(0);
   TORCH_CHECK(w.size(1) == p.K, "K mismatch: x ", x.sizes(), " w ", w.sizes());
@@ -402,11 +369,7 @@ c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optiona
     }
     p.eps = (float)eps;
   }
-  if (bias.has_value()) {
-    need(*bias, torch::kBFloat16, "bias");
-    TORCH_CHECK(bias->is_contiguous() && bias->numel() == p.N, "bias must be contiguous [N]");
-    p.bias = bptr(*bias);
-  }
+  p.bias = opt_bias(bias, p.N, /*align16=*/false);
   c10::optional<torch::Tensor> ret;
   auto bopt = w.options().dtype(torch::kBFloat16);
   if (epi == EPI_RESID) {
@@ -434,25 +397,8 @@ c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optiona
   } else if (epi == EPI_QKV) {
     TORCH_CHECK(kc.has_value() && vc.has_value() && tslot.has_value() && tpos.has_value(),
                 "qkv needs caches and token slots/positions");
-    p.kv_fp8 = need_kv(*kc, *vc);
-    TORCH_CHECK(kc->dim() == 4 && kc->is_contiguous() && vc->sizes() == kc->sizes() && vc->is_contiguous(),
-                "caches must be contiguous [slots, n_kv, max_seq, hd]");
-    TORCH_CHECK(kc->size(3) == hd && kc->size(1) * hd == kv_size, "cache shape mismatch");
+    qkv_target(p, p.M, *kc, *vc, *tslot, *tpos, q_size, kv_size, hd, rope, "gemv", /*align16=*/false);
     TORCH_CHECK(p.N == q_size + 2 * kv_size && q_size % hd == 0 && hd % 2 == 0, "bad qkv dims");
-    need(*tslot, torch::kInt32, "token_slots");
-    need(*tpos, torch::kInt32, "token_pos");
-    TORCH_CHECK(tslot->numel() == p.M && tpos->numel() == p.M && tslot->is_contiguous() &&
-                tpos->is_contiguous(), "token_slots/token_pos must be contiguous [M]");
-    p.kc = bptr_mut(*kc); p.vc = bptr_mut(*vc);
-    p.tslot = tslot->data_ptr<int>(); p.tpos = tpos->data_ptr<int>();
-    p.q_size = q_size; p.kv_size = kv_size; p.hd = hd;
-    p.max_seq = kc->size(2); p.n_kv = kc->size(1);
-    if (rope.has_value()) {
-      need(*rope, torch::kFloat32, "rope");
-      TORCH_CHECK(rope->is_contiguous() && rope->dim() == 3 && rope->size(1) == hd / 2 &&
-                  rope->size(2) == 2 && rope->size(0) >= p.max_seq, "rope table must be [>=max_seq, hd/2, 2]");
-      p.rope = rope->data_ptr<float>();
-    }
     ret = torch::empty({p.M, q_size}, bopt);
     p.out = ret->data_ptr(); p.ldo = q_size;
   } else {
@@ -488,8 +434,7 @@ torch::Tensor dequant_rows_fp8(torch::Tensor q, torch::Tensor scale, torch::Tens
               "dequant_rows_fp8: q must be contiguous [N, K], K % 16 == 0");
   TORCH_CHECK(scale.is_contiguous() && scale.numel() == N, "scale must be contiguous [N]");
   TORCH_CHECK(out.is_contiguous() && out.numel() >= N * K, "out must be contiguous with room for N * K elements");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
-              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0, "q and out must be 16-byte aligned");
+  TORCH_CHECK(aligned16(q) && aligned16(out), "q and out must be 16-byte aligned");
   check_hip(lsd_dequant_rows_fp8(q.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), (int)N, (int)K, cur_stream()),
             "dequant_rows_fp8");
   return out.flatten().narrow(0, 0, N * K).view({N, K});
@@ -571,15 +516,6 @@ c10::optional<torch::Tensor> norm(torch::Tensor x, c10::optional<torch::Tensor> 
   check_hip(lsd_norm(x.data_ptr<float>(), sp, slab_bf16, splits, pb, wp, (want_out && b.has_value()) ? bptr(*b) : nullptr,
                      op, T, H, (float)eps, rms ? 1 : 0, rp, n, cur_stream()), "norm");
   return out;
-}
-
-int check_cache(const torch::Tensor& kc, const torch::Tensor& vc) {
-  const int fp8 = need_kv(kc, vc);
-  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() && kc.sizes() == vc.sizes(),
-              "caches must be contiguous [slots, n_kv, max_seq, hd]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(kc.data_ptr()) % 16 == 0 &&
-              reinterpret_cast<uintptr_t>(vc.data_ptr()) % 16 == 0, "caches must be 16-byte aligned");
-  return fp8;
 }
 
 torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
@@ -681,33 +617,9 @@ void sample_launch(const torch::Tensor& logits, int64_t V, const torch::Tensor& 
                    const c10::optional<torch::Tensor>& segmax = c10::nullopt,
                    const c10::optional<torch::Tensor>& top_p = c10::nullopt,
                    const c10::optional<torch::Tensor>& min_p = c10::nullopt) {
-  need(logits, torch::kFloat32, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V <= logits.size(1) && V >= 1, "logits [B, >=V]");
+  const int B = need_logits(logits, V, "sample");
   TORCH_CHECK(logits.stride(0) % 4 == 0 && logits.size(1) % 4 == 0, "logits row length must be a multiple of 4");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "logits must be 16-byte aligned");
-  const int B = logits.size(0);
-  need(temp, torch::kFloat32, "temperature");
-  need(topk, torch::kInt32, "top_k");
-  need(greedy, torch::kInt32, "greedy");
-  need(seeds, torch::kInt64, "seeds");
-  need(step, torch::kInt64, "step");
-  TORCH_CHECK(temp.numel() == B && topk.numel() == B && greedy.numel() == B && seeds.numel() == B &&
-              step.numel() == B, "sampling params must be [B]");
-  TORCH_CHECK(step.is_contiguous(), "step must be contiguous");
-  need(out, torch::kInt32, "out");
-  TORCH_CHECK(out.numel() == B && out.is_contiguous(), "out must be contiguous int32 [B]");
-  const int* act = nullptr;
-  if (active.has_value()) {
-    need(*active, torch::kInt32, "active");
-    TORCH_CHECK(active->numel() == B && active->is_contiguous(), "active must be contiguous int32 [B]");
-    act = active->data_ptr<int>();
-  }
-  int* pp = nullptr;
-  if (pos.has_value()) {
-    need(*pos, torch::kInt32, "pos");
-    TORCH_CHECK(pos->numel() == B && pos->is_contiguous(), "pos must be contiguous int32 [B]");
-    pp = pos->data_ptr<int>();
-  }
+  TORCH_CHECK(aligned16(logits), "logits must be 16-byte aligned");
   const float* sm = nullptr;
   long ldseg = 0;
   if (segmax.has_value()) {  // linear_f32's segment maxima of these logits
@@ -718,20 +630,17 @@ void sample_launch(const torch::Tensor& logits, int64_t V, const torch::Tensor& 
     sm = segmax->data_ptr<float>();
     ldseg = segmax->size(1);
   }
-  // per-row nucleus / min-p cuts (sample.hip); absent = disabled
-  auto rowf = [&](const c10::optional<torch::Tensor>& t, const char* what) -> const float* {
-    if (!t.has_value()) return nullptr;
-    need(*t, torch::kFloat32, what);
-    TORCH_CHECK(t->numel() == B && t->is_contiguous(), what, " must be contiguous fp32 [B]");
-    return t->data_ptr<float>();
-  };
-  const float* tpp = rowf(top_p, "top_p");
-  const float* mpp = rowf(min_p, "min_p");
-  check_hip(lsd_sample(logits.data_ptr<float>(), logits.stride(0), B, V, temp.data_ptr<float>(),
-                       topk.data_ptr<int>(), greedy.data_ptr<int>(),
-                       reinterpret_cast<const long long*>(seeds.data_ptr<int64_t>()),
-                       reinterpret_cast<long long*>(step.data_ptr<int64_t>()),
-                       out.data_ptr<int>(), advance ? 1 : 0, act, pp, sm, ldseg, tpp, mpp, cur_stream()),
+  // top_p / min_p: per-row nucleus / min-p cuts (sample.hip); absent = disabled
+  check_hip(lsd_sample(logits.data_ptr<float>(), logits.stride(0), B, V,
+                       row_vec<const float>(temp, B, "sample", "temperature"),
+                       row_vec<const int>(topk, B, "sample", "top_k"),
+                       row_vec<const int>(greedy, B, "sample", "greedy"),
+                       row_vec<const long long>(seeds, B, "sample", "seeds"),
+                       row_vec<long long>(step, B, "sample", "step"), row_vec<int>(out, B, "sample", "out"),
+                       advance ? 1 : 0, row_vec<const int>(active, B, "sample", "active"),
+                       row_vec<int>(pos, B, "sample", "pos"), sm, ldseg,
+                       row_vec<const float>(top_p, B, "sample", "top_p"),
+                       row_vec<const float>(min_p, B, "sample", "min_p"), cur_stream()),
             "sample");
 }
 
@@ -745,32 +654,16 @@ torch::Tensor qkv_post(torch::Tensor y, c10::optional<torch::Tensor> bias, torch
                        c10::optional<torch::Tensor> rope) {
   need(y, torch::kFloat32, "y");
   const long M = y.size(0), N = y.size(1);
-  TORCH_CHECK(y.dim() == 2 && y.stride(1) == 1 && y.stride(0) % 4 == 0 &&
-              reinterpret_cast<uintptr_t>(y.data_ptr()) % 16 == 0, "qkv_post: y [M, N] with 16-byte rows");
+  TORCH_CHECK(y.dim() == 2 && y.stride(1) == 1 && y.stride(0) % 4 == 0 && aligned16(y),
+              "qkv_post: y [M, N] with 16-byte rows");
   TORCH_CHECK(N == q_size + 2 * kv_size && hd % 8 == 0 && q_size % hd == 0 && kv_size % hd == 0,
               "qkv_post: N must be q_size + 2 kv_size, head dims multiples of 8");
-  const lsd_bf16_t* b = opt_bias(bias, N);
-  const int kv_fp8 = need_kv(kc, vc);
-  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.sizes() == kc.sizes() && vc.is_contiguous(),
-              "caches must be contiguous [slots, n_kv, max_seq, hd]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(kc.data_ptr()) % 16 == 0 &&
-              reinterpret_cast<uintptr_t>(vc.data_ptr()) % 16 == 0, "caches must be 16-byte aligned");
-  TORCH_CHECK(kc.size(3) == hd && kc.size(1) * hd == kv_size, "cache shape mismatch");
-  need(tslot, torch::kInt32, "token_slots");
-  need(tpos, torch::kInt32, "token_pos");
-  TORCH_CHECK(tslot.numel() == M && tpos.numel() == M && tslot.is_contiguous() && tpos.is_contiguous(),
-              "token_slots/token_pos must be contiguous [M]");
-  const float* rp = nullptr;
-  if (rope.has_value()) {
-    need(*rope, torch::kFloat32, "rope");
-    TORCH_CHECK(rope->is_contiguous() && rope->dim() == 3 && rope->size(1) == hd / 2 && rope->size(2) == 2 &&
-                rope->size(0) >= kc.size(2), "rope table must be [>=max_seq, hd/2, 2]");
-    rp = rope->data_ptr<float>();
-  }
+  GemmParams p{};  // the QKV target only
+  p.bias = opt_bias(bias, N);
+  qkv_target(p, M, kc, vc, tslot, tpos, q_size, kv_size, hd, rope, "qkv_post");
   auto q = torch::empty({M, q_size}, y.options().dtype(torch::kBFloat16));
-  check_hip(lsd_qkv_post(y.data_ptr<float>(), y.stride(0), b, tslot.data_ptr<int>(), tpos.data_ptr<int>(), rp,
-                         reinterpret_cast<lsd_bf16_t*>(q.data_ptr()), bptr_mut(kc), bptr_mut(vc), (int)M,
-                         (int)q_size, (int)kv_size, (int)hd, (int)kc.size(1), (int)kc.size(2), kv_fp8, cur_stream()),
+  check_hip(lsd_qkv_post(y.data_ptr<float>(), y.stride(0), p.bias, p.tslot, p.tpos, p.rope, bptr_mut(q), p.kc, p.vc,
+                         (int)M, p.q_size, p.kv_size, p.hd, p.n_kv, p.max_seq, p.kv_fp8, cur_stream()),
             "qkv_post");
   return q;
 }
@@ -790,33 +683,18 @@ void apply_rows(torch::Tensor args, int64_t b) {
 // in place, from their generated-token history hist[slots[row], 0 .. counts[row]).
 void penalize(torch::Tensor logits, int64_t V, torch::Tensor hist, torch::Tensor slots, torch::Tensor counts,
               torch::Tensor presence, torch::Tensor frequency, c10::optional<torch::Tensor> segmax) {
-  need(logits, torch::kFloat32, "logits");
+  const int64_t B = need_logits(logits, V, "penalize");
   need(hist, torch::kInt32, "hist");
-  need(slots, torch::kInt32, "slots");
-  need(counts, torch::kInt64, "counts");
-  need(presence, torch::kFloat32, "presence");
-  need(frequency, torch::kFloat32, "frequency");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= 1 && V <= logits.size(1), "logits [B, >=V]");
-  const int64_t B = logits.size(0);
   TORCH_CHECK(hist.dim() == 2 && hist.is_contiguous(), "hist must be contiguous int32 [slots, max_seq]");
   TORCH_CHECK(hist.size(1) >= 1 && hist.size(1) <= 8192,
               "penalize: histories of more than 8192 tokens do not fit the kernel's 128 KB LDS table");
-  for (const torch::Tensor* t : {&slots, &counts, &presence, &frequency})
-    TORCH_CHECK(t->numel() == B && t->is_contiguous(), "penalize: row vectors must be contiguous [B]");
-  float* sm = nullptr;
-  long ldseg = 0;
-  if (segmax.has_value()) {
-    need(*segmax, torch::kFloat32, "segmax");
-    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && logits.size(1) % 8 == 0 &&
-                    logits.stride(0) % 8 == 0 && segmax->size(1) == logits.size(1) / 8,
-                "segmax must be fp32 [B, logits row length / 8]");
-    sm = segmax->data_ptr<float>();
-    ldseg = segmax->stride(0);
-  }
+  const auto [sm, ldseg] = opt_segmax(segmax, logits, SEG_EXACT);
   check_hip(lsd_penalize(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V, hist.data_ptr<int>(),
-                         (int)hist.size(1), (int)hist.size(0), slots.data_ptr<int>(),
-                         reinterpret_cast<const long long*>(counts.data_ptr<int64_t>()), presence.data_ptr<float>(),
-                         frequency.data_ptr<float>(), sm, ldseg, cur_stream()), "penalize");
+                         (int)hist.size(1), (int)hist.size(0), row_vec<const int>(slots, B, "penalize", "slots"),
+                         row_vec<const long long>(counts, B, "penalize", "counts"),
+                         row_vec<const float>(presence, B, "penalize", "presence"),
+                         row_vec<const float>(frequency, B, "penalize", "frequency"), sm, ldseg, cur_stream()),
+            "penalize");
 }
 
 // Per-request logit edits (logit_edit.hip): logit_bias, banned tokens and
@@ -827,40 +705,23 @@ void penalize(torch::Tensor logits, int64_t V, torch::Tensor hist, torch::Tensor
 void logit_edits(torch::Tensor logits, int64_t V, torch::Tensor cnt, torch::Tensor tok, torch::Tensor val,
                  torch::Tensor until, torch::Tensor slots, c10::optional<torch::Tensor> step,
                  c10::optional<torch::Tensor> segmax) {
-  need(logits, torch::kFloat32, "logits");
+  const int64_t B = need_logits(logits, V, "logit_edits");
   need(cnt, torch::kInt32, "cnt");
   need(tok, torch::kInt32, "tok");
   need(val, torch::kFloat32, "val");
   need(until, torch::kInt32, "until");
-  need(slots, torch::kInt32, "slots");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= 1 && V <= logits.size(1), "logits [B, >=V]");
-  const int64_t B = logits.size(0);
   TORCH_CHECK(tok.dim() == 2 && tok.is_contiguous() && val.is_contiguous() && until.is_contiguous() &&
                   cnt.is_contiguous() && val.sizes() == tok.sizes() && until.sizes() == tok.sizes() &&
                   cnt.dim() == 1 && cnt.size(0) == tok.size(0) && tok.size(0) >= 1,
               "logit_edits: the table is contiguous cnt [slots], tok / val / until [slots, E]");
   TORCH_CHECK(tok.size(1) >= 1 && tok.size(1) <= 1024,
               "logit_edits: a table of more than 1024 entries per slot is more than the kernel's 4 trips per thread");
-  TORCH_CHECK(slots.numel() == B && slots.is_contiguous(), "logit_edits: slots must be contiguous [B]");
-  const long long* sp = nullptr;
-  if (step.has_value()) {
-    need(*step, torch::kInt64, "step");
-    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
-    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
-  }
-  float* sm = nullptr;
-  long ldseg = 0;
-  if (segmax.has_value()) {
-    need(*segmax, torch::kFloat32, "segmax");
-    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && logits.size(1) % 8 == 0 &&
-                    logits.stride(0) % 8 == 0 && segmax->size(1) == logits.size(1) / 8,
-                "segmax must be fp32 [B, logits row length / 8] (row length % 8 == 0)");
-    sm = segmax->data_ptr<float>();
-    ldseg = segmax->stride(0);
-  }
+  const auto [sm, ldseg] = opt_segmax(segmax, logits, SEG_EXACT);
   check_hip(lsd_logit_edits(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V, cnt.data_ptr<int>(),
                             tok.data_ptr<int>(), val.data_ptr<float>(), until.data_ptr<int>(), (int)tok.size(1),
-                            (int)tok.size(0), slots.data_ptr<int>(), sp, sm, ldseg, cur_stream()), "logit_edits");
+                            (int)tok.size(0), row_vec<const int>(slots, B, "logit_edits", "slots"),
+                            row_vec<const long long>(step, B, "logit_edits", "step"), sm, ldseg, cur_stream()),
+            "logit_edits");
 }
 
 // Per-request allowed_token_ids (allow_mask.hip).  Row i whose KV slot s =
@@ -870,28 +731,17 @@ void logit_edits(torch::Tensor logits, int64_t V, torch::Tensor cnt, torch::Tens
 // satisfy beyond their types and layouts is lsd_allow_mask's to refuse.
 void allow_mask(torch::Tensor logits, int64_t V, torch::Tensor on, torch::Tensor bits, torch::Tensor slots,
                 c10::optional<torch::Tensor> segmax) {
-  need(logits, torch::kFloat32, "logits");
+  const int64_t B = need_logits(logits, V, "allow_mask", /*v_min=*/0, /*v_in_row=*/false), ld = logits.size(1);
   need(on, torch::kInt32, "on");
   need(bits, torch::kInt32, "bits");
-  need(slots, torch::kInt32, "slots");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits [B, width]");
-  const int64_t B = logits.size(0), ld = logits.size(1);
   TORCH_CHECK(B <= 1 || logits.stride(0) == ld, "allow_mask: the rows of logits must be dense");
-  TORCH_CHECK(V >= 0 && V <= INT32_MAX && bits.dim() == 2 && bits.is_contiguous() && on.is_contiguous() &&
+  TORCH_CHECK(V <= INT32_MAX && bits.dim() == 2 && bits.is_contiguous() && on.is_contiguous() &&
                   on.dim() == 1 && on.size(0) == bits.size(0),
               "allow_mask: the table is contiguous on [slots], bits [slots, W]");
-  TORCH_CHECK(slots.numel() == B && slots.is_contiguous(), "allow_mask: slots must be contiguous [B]");
-  float* sm = nullptr;
-  long ldseg = 0;
-  if (segmax.has_value()) {
-    need(*segmax, torch::kFloat32, "segmax");
-    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && segmax->size(1) * 8 >= ld,
-                "segmax must be fp32 [B, >= logits row length / 8]");
-    sm = segmax->data_ptr<float>();
-    ldseg = B <= 1 ? segmax->size(1) : segmax->stride(0);
-  }
+  const auto [sm, ldseg] = opt_segmax(segmax, logits, SEG_DENSE);
   check_hip(lsd_allow_mask(logits.data_ptr<float>(), ld, (int)B, (int)V, on.data_ptr<int>(), bits.data_ptr<int>(),
-                           (int)bits.size(1), (int)on.size(0), slots.data_ptr<int>(), sm, ldseg, cur_stream()),
+                           (int)bits.size(1), (int)on.size(0), row_vec<const int>(slots, B, "allow_mask", "slots"), sm,
+                           ldseg, cur_stream()),
             "allow_mask");
 }
 
@@ -942,26 +792,15 @@ void need_guide_table(const torch::Tensor& gcls, const torch::Tensor& gnext, con
 // refuse.
 void guide_mask(torch::Tensor logits, int64_t V, torch::Tensor gcls, torch::Tensor gnext, torch::Tensor gdim,
                 torch::Tensor gsl, torch::Tensor slots, c10::optional<torch::Tensor> segmax) {
-  need(logits, torch::kFloat32, "logits");
-  need(slots, torch::kInt32, "slots");
+  const int64_t B = need_logits(logits, V, "guide_mask", /*v_min=*/0, /*v_in_row=*/false), ld = logits.size(1);
   need_guide_table(gcls, gnext, gdim, gsl, "guide_mask");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits [B, width]");
-  const int64_t B = logits.size(0), ld = logits.size(1);
   TORCH_CHECK(B <= 1 || logits.stride(0) == ld, "guide_mask: the rows of logits must be dense");
-  TORCH_CHECK(V >= 0 && V <= INT32_MAX, "guide_mask: V");
-  TORCH_CHECK(slots.numel() == B && slots.is_contiguous(), "guide_mask: slots must be contiguous [B]");
-  float* sm = nullptr;
-  long ldseg = 0;
-  if (segmax.has_value()) {
-    need(*segmax, torch::kFloat32, "segmax");
-    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && segmax->size(1) * 8 >= ld,
-                "segmax must be fp32 [B, >= logits row length / 8]");
-    sm = segmax->data_ptr<float>();
-    ldseg = B <= 1 ? segmax->size(1) : segmax->stride(0);
-  }
+  TORCH_CHECK(V <= INT32_MAX, "guide_mask: V");
+  const auto [sm, ldseg] = opt_segmax(segmax, logits, SEG_DENSE);
   check_hip(lsd_guide_mask(logits.data_ptr<float>(), ld, (int)B, (int)V, gcls.data_ptr<int16_t>(), gcls.size(1),
                            gnext.data_ptr<int16_t>(), gnext.size(1), gdim.data_ptr<int>(), (int)gcls.size(0),
-                           gsl.data_ptr<int>(), (int)gsl.size(0), slots.data_ptr<int>(), sm, ldseg, cur_stream()),
+                           gsl.data_ptr<int>(), (int)gsl.size(0), row_vec<const int>(slots, B, "guide_mask", "slots"),
+                           sm, ldseg, cur_stream()),
             "guide_mask");
 }
 
@@ -970,21 +809,14 @@ void guide_mask(torch::Tensor logits, int64_t V, torch::Tensor gcls, torch::Tens
 // guided slot.
 void guide_advance(torch::Tensor gcls, torch::Tensor gnext, torch::Tensor gdim, torch::Tensor gsl, int64_t V,
                    torch::Tensor slots, torch::Tensor tokens, c10::optional<torch::Tensor> active) {
-  need(slots, torch::kInt32, "slots");
-  need(tokens, torch::kInt32, "tokens");
   need_guide_table(gcls, gnext, gdim, gsl, "guide_advance");
   const int64_t B = tokens.numel();
   TORCH_CHECK(V >= 0 && V <= INT32_MAX, "guide_advance: V");
-  TORCH_CHECK(slots.numel() == B && slots.is_contiguous() && tokens.is_contiguous(), "guide_advance: [B] vectors");
-  const int* act = nullptr;
-  if (active.has_value()) {
-    need(*active, torch::kInt32, "active");
-    TORCH_CHECK(active->numel() == B && active->is_contiguous(), "active must be contiguous int32 [B]");
-    act = active->data_ptr<int>();
-  }
   check_hip(lsd_guide_advance(gsl.data_ptr<int>(), (int)gsl.size(0), gcls.data_ptr<int16_t>(), gcls.size(1),
                               gnext.data_ptr<int16_t>(), gnext.size(1), gdim.data_ptr<int>(), (int)gcls.size(0),
-                              (int)V, slots.data_ptr<int>(), tokens.data_ptr<int>(), act, (int)B, cur_stream()),
+                              (int)V, row_vec<const int>(slots, B, "guide_advance", "slots"),
+                              row_vec<const int>(tokens, B, "guide_advance", "tokens"),
+                              row_vec<const int>(active, B, "guide_advance", "active"), (int)B, cur_stream()),
             "guide_advance");
 }
 
@@ -997,39 +829,22 @@ void guide_advance(torch::Tensor gcls, torch::Tensor gnext, torch::Tensor gdim, 
 void repetition(torch::Tensor logits, int64_t V, torch::Tensor plen, torch::Tensor rpen, torch::Tensor ngram,
                 torch::Tensor tok, torch::Tensor slots, c10::optional<torch::Tensor> step,
                 c10::optional<torch::Tensor> segmax) {
-  need(logits, torch::kFloat32, "logits");
+  const int64_t B = need_logits(logits, V, "repetition");
   need(plen, torch::kInt32, "plen");
   need(rpen, torch::kFloat32, "rpen");
   need(ngram, torch::kInt32, "ngram");
   need(tok, torch::kInt32, "tok");
-  need(slots, torch::kInt32, "slots");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= 1 && V <= logits.size(1), "logits [B, >=V]");
-  const int64_t B = logits.size(0);
   TORCH_CHECK(tok.dim() == 2 && tok.is_contiguous() && plen.is_contiguous() && rpen.is_contiguous() &&
                   ngram.is_contiguous() && plen.dim() == 1 && rpen.dim() == 1 && ngram.dim() == 1 &&
                   plen.size(0) == tok.size(0) && rpen.size(0) == tok.size(0) && ngram.size(0) == tok.size(0) &&
                   tok.size(0) >= 1 && tok.size(1) >= 1,
               "repetition: the table is contiguous plen / rpen / ngram [slots], tok [slots, max_seq]");
-  TORCH_CHECK(slots.numel() == B && slots.is_contiguous(), "repetition: slots must be contiguous [B]");
-  const long long* sp = nullptr;
-  if (step.has_value()) {
-    need(*step, torch::kInt64, "step");
-    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
-    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
-  }
-  float* sm = nullptr;
-  long ldseg = 0;
-  if (segmax.has_value()) {
-    need(*segmax, torch::kFloat32, "segmax");
-    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && logits.size(1) % 8 == 0 &&
-                    logits.stride(0) % 8 == 0 && segmax->size(1) == logits.size(1) / 8,
-                "segmax must be fp32 [B, logits row length / 8] (row length % 8 == 0)");
-    sm = segmax->data_ptr<float>();
-    ldseg = segmax->stride(0);
-  }
+  const auto [sm, ldseg] = opt_segmax(segmax, logits, SEG_EXACT);
   check_hip(lsd_repeat_penalty(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V, plen.data_ptr<int>(),
                                rpen.data_ptr<float>(), ngram.data_ptr<int>(), tok.data_ptr<int>(), (int)tok.size(1),
-                               (int)tok.size(0), slots.data_ptr<int>(), sp, sm, ldseg, cur_stream()), "repetition");
+                               (int)tok.size(0), row_vec<const int>(slots, B, "repetition", "slots"),
+                               row_vec<const long long>(step, B, "repetition", "step"), sm, ldseg, cur_stream()),
+            "repetition");
 }
 
 // Per-request bad_words (bad_words.hip).  Row i whose KV slot s = slots[i] has
@@ -1043,15 +858,12 @@ void repetition(torch::Tensor logits, int64_t V, torch::Tensor plen, torch::Tens
 void bad_words(torch::Tensor logits, int64_t V, torch::Tensor cnt, torch::Tensor end, torch::Tensor btok,
                torch::Tensor plen, torch::Tensor ctok, torch::Tensor slots, c10::optional<torch::Tensor> step,
                c10::optional<torch::Tensor> segmax) {
-  need(logits, torch::kFloat32, "logits");
+  const int64_t B = need_logits(logits, V, "bad_words");
   need(cnt, torch::kInt32, "cnt");
   need(end, torch::kInt32, "end");
   need(btok, torch::kInt32, "tok");
   need(plen, torch::kInt32, "plen");
   need(ctok, torch::kInt32, "context tok");
-  need(slots, torch::kInt32, "slots");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= 1 && V <= logits.size(1), "logits [B, >=V]");
-  const int64_t B = logits.size(0);
   TORCH_CHECK(cnt.dim() == 1 && end.dim() == 2 && btok.dim() == 2 && cnt.is_contiguous() && end.is_contiguous() &&
                   btok.is_contiguous() && end.size(0) == cnt.size(0) && btok.size(0) == cnt.size(0) &&
                   cnt.size(0) >= 1 && end.size(1) >= 1 && btok.size(1) >= 1,
@@ -1059,27 +871,13 @@ void bad_words(torch::Tensor logits, int64_t V, torch::Tensor cnt, torch::Tensor
   TORCH_CHECK(ctok.dim() == 2 && ctok.is_contiguous() && plen.dim() == 1 && plen.is_contiguous() &&
                   plen.size(0) == cnt.size(0) && ctok.size(0) == cnt.size(0) && ctok.size(1) >= 1,
               "bad_words: the context table is contiguous plen [slots], tok [slots, max_seq] over the same slots");
-  TORCH_CHECK(slots.numel() == B && slots.is_contiguous(), "bad_words: slots must be contiguous [B]");
-  const long long* sp = nullptr;
-  if (step.has_value()) {
-    need(*step, torch::kInt64, "step");
-    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
-    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
-  }
-  float* sm = nullptr;
-  long ldseg = 0;
-  if (segmax.has_value()) {
-    need(*segmax, torch::kFloat32, "segmax");
-    TORCH_CHECK(segmax->dim() == 2 && segmax->stride(1) == 1 && segmax->size(0) == B && logits.size(1) % 8 == 0 &&
-                    logits.stride(0) % 8 == 0 && segmax->size(1) == logits.size(1) / 8,
-                "segmax must be fp32 [B, logits row length / 8] (row length % 8 == 0)");
-    sm = segmax->data_ptr<float>();
-    ldseg = segmax->stride(0);
-  }
+  const auto [sm, ldseg] = opt_segmax(segmax, logits, SEG_EXACT);
   check_hip(lsd_bad_words(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V, cnt.data_ptr<int>(),
                           end.data_ptr<int>(), (int)end.size(1), btok.data_ptr<int>(), (int)btok.size(1),
                           plen.data_ptr<int>(), ctok.data_ptr<int>(), (int)ctok.size(1), (int)cnt.size(0),
-                          slots.data_ptr<int>(), sp, sm, ldseg, cur_stream()), "bad_words");
+                          row_vec<const int>(slots, B, "bad_words", "slots"),
+                          row_vec<const long long>(step, B, "bad_words", "step"), sm, ldseg, cur_stream()),
+            "bad_words");
 }
 
 // tok[slots[i], plen[slots[i]] + step[i] - back] = tokens[i] for active rows
@@ -1090,28 +888,16 @@ void record_context(torch::Tensor tok, torch::Tensor plen, torch::Tensor slots, 
                     torch::Tensor tokens, c10::optional<torch::Tensor> active, int64_t back) {
   need(tok, torch::kInt32, "tok");
   need(plen, torch::kInt32, "plen");
-  need(slots, torch::kInt32, "slots");
-  need(tokens, torch::kInt32, "tokens");
   TORCH_CHECK(tok.dim() == 2 && tok.is_contiguous() && plen.dim() == 1 && plen.is_contiguous() &&
                   plen.size(0) == tok.size(0),
               "record_context: tok must be contiguous int32 [slots, max_seq], plen [slots]");
   const int64_t B = tokens.numel();
-  TORCH_CHECK(slots.numel() == B && slots.is_contiguous() && tokens.is_contiguous(), "record_context: [B] vectors");
-  const long long* sp = nullptr;
-  if (step.has_value()) {
-    need(*step, torch::kInt64, "step");
-    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
-    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
-  }
-  const int* act = nullptr;
-  if (active.has_value()) {
-    need(*active, torch::kInt32, "active");
-    TORCH_CHECK(active->numel() == B && active->is_contiguous(), "active must be contiguous int32 [B]");
-    act = active->data_ptr<int>();
-  }
   check_hip(lsd_record_context(tok.data_ptr<int>(), (int)tok.size(1), (int)tok.size(0), plen.data_ptr<int>(),
-                               slots.data_ptr<int>(), sp, (int)back, tokens.data_ptr<int>(), act, (int)B,
-                               cur_stream()), "record_context");
+                               row_vec<const int>(slots, B, "record_context", "slots"),
+                               row_vec<const long long>(step, B, "record_context", "step"), (int)back,
+                               row_vec<const int>(tokens, B, "record_context", "tokens"),
+                               row_vec<const int>(active, B, "record_context", "active"), (int)B, cur_stream()),
+            "record_context");
 }
 
 // hist[slots[i], step[i] - back] = tokens[i] for active rows (all rows without
@@ -1120,25 +906,14 @@ void record_context(torch::Tensor tok, torch::Tensor plen, torch::Tensor slots, 
 void record_tokens(torch::Tensor hist, torch::Tensor slots, c10::optional<torch::Tensor> step, torch::Tensor tokens,
                    c10::optional<torch::Tensor> active, int64_t back) {
   need(hist, torch::kInt32, "hist");
-  need(slots, torch::kInt32, "slots");
-  need(tokens, torch::kInt32, "tokens");
   TORCH_CHECK(hist.dim() == 2 && hist.is_contiguous(), "hist must be contiguous int32 [slots, max_seq]");
   const int64_t B = tokens.numel();
-  TORCH_CHECK(slots.numel() == B && slots.is_contiguous() && tokens.is_contiguous(), "record_tokens: [B] vectors");
-  const long long* sp = nullptr;
-  if (step.has_value()) {
-    need(*step, torch::kInt64, "step");
-    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
-    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
-  }
-  const int* act = nullptr;
-  if (active.has_value()) {
-    need(*active, torch::kInt32, "active");
-    TORCH_CHECK(active->numel() == B && active->is_contiguous(), "active must be contiguous int32 [B]");
-    act = active->data_ptr<int>();
-  }
-  check_hip(lsd_record_tokens(hist.data_ptr<int>(), (int)hist.size(1), (int)hist.size(0), slots.data_ptr<int>(), sp,
-                              (int)back, tokens.data_ptr<int>(), act, (int)B, cur_stream()), "record_tokens");
+  check_hip(lsd_record_tokens(hist.data_ptr<int>(), (int)hist.size(1), (int)hist.size(0),
+                              row_vec<const int>(slots, B, "record_tokens", "slots"),
+                              row_vec<const long long>(step, B, "record_tokens", "step"), (int)back,
+                              row_vec<const int>(tokens, B, "record_tokens", "tokens"),
+                              row_vec<const int>(active, B, "record_tokens", "active"), (int)B, cur_stream()),
+            "record_tokens");
 }
 
 // Token logprobs and top-N alternatives (logprob.hip) of the rows with
@@ -1148,36 +923,21 @@ void record_tokens(torch::Tensor hist, torch::Tensor slots, c10::optional<torch:
 void logprobs(torch::Tensor logits, int64_t V, torch::Tensor tokens, torch::Tensor nlp, torch::Tensor slots,
               c10::optional<torch::Tensor> step, c10::optional<torch::Tensor> active, torch::Tensor lp_tok,
               torch::Tensor lp_top_id, torch::Tensor lp_top, int64_t back) {
-  need(logits, torch::kFloat32, "logits");
-  need(tokens, torch::kInt32, "tokens");
-  need(nlp, torch::kInt32, "nlp");
-  need(slots, torch::kInt32, "slots");
+  // W > 20 and V beyond the row are the wrapper's to refuse (hipErrorInvalidValue)
+  const int64_t B = need_logits(logits, V, "logprobs", /*v_min=*/1, /*v_in_row=*/false);
   need(lp_tok, torch::kFloat32, "lp_tok");
   need(lp_top_id, torch::kInt32, "lp_top_id");
   need(lp_top, torch::kFloat32, "lp_top");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && V >= 1, "logits [B, >=V]");
-  const int64_t B = logits.size(0);
-  for (const torch::Tensor* t : {&tokens, &nlp, &slots})
-    TORCH_CHECK(t->numel() == B && t->is_contiguous(), "logprobs: row vectors must be contiguous [B]");
   TORCH_CHECK(lp_tok.dim() == 2 && lp_tok.is_contiguous() && lp_top_id.dim() == 3 && lp_top_id.is_contiguous() &&
                   lp_top.dim() == 3 && lp_top.is_contiguous() && lp_top_id.sizes() == lp_top.sizes() &&
                   lp_top.size(0) == lp_tok.size(0) && lp_top.size(1) == lp_tok.size(1),
               "logprobs: records are contiguous lp_tok [slots, L], lp_top_id / lp_top [slots, L, W]");
-  const long long* sp = nullptr;
-  if (step.has_value()) {
-    need(*step, torch::kInt64, "step");
-    TORCH_CHECK(step->numel() == B && step->is_contiguous(), "step must be contiguous int64 [B]");
-    sp = reinterpret_cast<const long long*>(step->data_ptr<int64_t>());
-  }
-  const int* act = nullptr;
-  if (active.has_value()) {
-    need(*active, torch::kInt32, "active");
-    TORCH_CHECK(active->numel() == B && active->is_contiguous(), "active must be contiguous int32 [B]");
-    act = active->data_ptr<int>();
-  }
-  // W > 20 and V beyond the row are the wrapper's to refuse (hipErrorInvalidValue)
-  check_hip(lsd_logprobs(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V, tokens.data_ptr<int>(),
-                         nlp.data_ptr<int>(), slots.data_ptr<int>(), sp, (int)back, act, lp_tok.data_ptr<float>(),
+  check_hip(lsd_logprobs(logits.data_ptr<float>(), logits.stride(0), (int)B, (int)V,
+                         row_vec<const int>(tokens, B, "logprobs", "tokens"),
+                         row_vec<const int>(nlp, B, "logprobs", "nlp"),
+                         row_vec<const int>(slots, B, "logprobs", "slots"),
+                         row_vec<const long long>(step, B, "logprobs", "step"), (int)back,
+                         row_vec<const int>(active, B, "logprobs", "active"), lp_tok.data_ptr<float>(),
                          lp_top_id.data_ptr<int>(), lp_top.data_ptr<float>(), (int)lp_tok.size(1), (int)lp_tok.size(0),
                          (int)lp_top.size(2), cur_stream()), "logprobs");
 }
@@ -1198,8 +958,8 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lm_head_score(torch::Ten
   const int64_t T = xn.size(0), K = xn.size(1), Vp = w.size(0);
   TORCH_CHECK(K >= 64 && K % 64 == 0 && Vp >= 64 && Vp % 64 == 0, "lm_head_score: K % 64 == 0 and Vp % 64 == 0");
   TORCH_CHECK(V >= 1 && V <= Vp, "lm_head_score: vocab lies in [1, Vp]");
-  TORCH_CHECK(xn.stride(0) % 8 == 0 && w.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(xn.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, "lm_head_score: 16-byte rows");
+  TORCH_CHECK(xn.stride(0) % 8 == 0 && w.stride(0) % 8 == 0 && aligned16(xn) && aligned16(w),
+              "lm_head_score: 16-byte rows");
   TORCH_CHECK(targets.dim() == 1 && targets.numel() == T && targets.is_contiguous(),
               "lm_head_score: targets is contiguous int32 [T]");
   TORCH_CHECK(T < (1 << 30) && Vp < (1 << 30) && slices >= 0, "lm_head_score: sizes exceed int32");
@@ -1218,7 +978,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lm_head_score(torch::Ten
 torch::Tensor silu_mul(torch::Tensor y) {
   need(y, torch::kBFloat16, "y");
   TORCH_CHECK(y.dim() == 2 && y.stride(1) == 1 && y.size(1) % 32 == 0, "silu_mul: y [M, 2F], 2F % 32 == 0");
-  TORCH_CHECK(y.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(y.data_ptr()) % 16 == 0, "silu_mul: 16-byte rows");
+  TORCH_CHECK(y.stride(0) % 8 == 0 && aligned16(y), "silu_mul: 16-byte rows");
   const int M = y.size(0), F = y.size(1) / 2;
   auto out = torch::empty({M, F}, y.options());
   check_hip(lsd_silu_mul(bptr(y), y.stride(0), reinterpret_cast<lsd_bf16_t*>(out.data_ptr()), F, M, F,
@@ -1287,8 +1047,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return gemv(x, w, bias, epi, norm, gamma, beta, eps, resid, kc, vc, tslot, tpos, q_size, kv_size, hd, rope,
                 c10::nullopt, wscale);
   }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("epi"), py::arg("norm"), py::arg("gamma"), py::arg("beta"),
-     py::arg("eps"), py::arg("resid"), py::arg("kc"), py::arg("vc"), py::arg("tslot"), py::arg("tpos"),
-     py::arg("q_size"), py::arg("kv_size"), py::arg("hd"), py::arg("rope"), py::arg("wscale") = py::none());
+     py::arg("eps"), py::arg("resid") = py::none(), py::arg("kc") = py::none(), py::arg("vc") = py::none(),
+     py::arg("tslot") = py::none(), py::arg("tpos") = py::none(), py::arg("q_size") = 0, py::arg("kv_size") = 0,
+     py::arg("hd") = 0, py::arg("rope") = py::none(), py::arg("wscale") = py::none());
   // fp32 logits GEMV that also writes the 8-column segment maxima (the sampler's threshold)
   m.def("gemv_logits", [](torch::Tensor x, torch::Tensor w, int64_t norm, c10::optional<torch::Tensor> gamma,
                           c10::optional<torch::Tensor> beta, double eps, torch::Tensor segmax,

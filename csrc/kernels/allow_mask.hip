@@ -38,6 +38,7 @@
 // of 4); otherwise the same walk with dword accesses.
 #include "common.h"
 #include "mask8.h"
+#include "api.h"
 
 namespace lsd {
 

@@ -22,6 +22,7 @@
 //   round trip for P).  V^T fragments come from the row-major V tile via the
 //   gfx950 hardware transpose read ds_read_b64_tr_b16.
 #include "common.h"
+#include "api.h"
 
 namespace lsd {
 

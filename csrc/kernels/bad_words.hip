@@ -35,6 +35,7 @@
 // A sequence whose offsets do not describe 1 to 32 tokens inside the row is
 // skipped: the kernel never reads outside the tables whatever they hold.
 #include "common.h"
+#include "api.h"
 
 namespace lsd {
 

@@ -9,6 +9,7 @@
 // per 8 outputs, 16-byte loads of the gate and up chunks, fp32 math, one
 // 16-byte store -- out[m, 16 j + i] = silu(y[m, 32 j + i]) * y[m, 32 j + 16 + i].
 #include "common.h"
+#include "api.h"
 
 namespace lsd {
 

@@ -28,6 +28,7 @@
 #include "common.h"
 #include "gemm_params.h"
 #include "gemm_plan.h"  // Epi, tile constants, GemmTuning / GemmPlan / plan_gemm()
+#include "api.h"
 
 namespace lsd {
 

@@ -44,6 +44,7 @@
 // branch below away).
 #include "common.h"
 #include "gemm_params.h"
+#include "api.h"
 
 namespace lsd {
 namespace gv {
@@ -212,7 +213,7 @@ using namespace lsd;
 static int gv_mr(int M) { return M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 0; }
 static int gv_nb(int K) { return K <= 2048 ? 1 : K <= 4096 ? 2 : K <= 8192 ? 4 : K <= 14336 ? 7 : 0; }
 
-extern "C" int lsd_gemv_ok(int M, int K, int epi, int norm) {
+static int lsd_gemv_ok(int M, int K, int epi, int norm) {  // host code asks lsd_gemv_ok_w
   const int mr = gv_mr(M), nb = gv_nb(K);
   if (M < 1 || mr == 0 || nb == 0 || K % 8 != 0) return 0;
   if (mr * nb > 16) return 0;

@@ -42,6 +42,7 @@
 // otherwise the same walk with dword and 2-byte accesses.
 #include "common.h"
 #include "mask8.h"
+#include "api.h"
 
 namespace lsd {
 

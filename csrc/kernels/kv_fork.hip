@@ -28,6 +28,7 @@
 // likewise for 4; else bytes.  The test models' head dims are small, and a
 // view of a larger tensor may start anywhere.
 #include "common.h"
+#include "api.h"
 
 namespace lsd {
 

@@ -34,6 +34,7 @@
 // E <= 1024: no LDS table, a thread makes at most 4 trips (their active runs
 // are remembered in a 4-bit mask across the barrier).
 #include "common.h"
+#include "api.h"
 
 namespace lsd {
 

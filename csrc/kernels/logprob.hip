@@ -35,6 +35,7 @@
 // groups hold a finite logit) take n rounds of block arg-max, each excluding
 // what the rounds before it took: slower, exact.
 #include "row_visit.h"
+#include "api.h"
 
 namespace lsd {
 

@@ -1,6 +1,7 @@
 // Device-resident state of a loopback channel (csrc/kernels/loopback.hip) and
 // the pinned status block its kernels report to (csrc/loop_fabric.cpp).
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 #define LOOP_HEADERS 64  // message headers in flight per channel
@@ -38,3 +39,11 @@ struct LoopStatus {
   uint32_t err_chan;
   uint32_t pad;
 };
+
+// The launchers of loopback.hip (one launch per op, on stream s) and the ring
+// placement its send kernel uses, for the host mirror of loop_fabric.cpp.
+extern "C" {
+hipError_t lsd_loop_send(LoopChan* ch, void* ring, const void* src, uint64_t bytes, LoopStatus* st, hipStream_t s);
+hipError_t lsd_loop_recv(LoopChan* ch, const void* ring, void* dst, uint64_t bytes, LoopStatus* st, hipStream_t s);
+uint64_t lsd_loop_place(uint64_t head, uint64_t bytes, uint64_t cap);
+}

@@ -13,6 +13,7 @@
 #include <cstdio>
 
 #include "common.h"
+#include "api.h"
 
 namespace lsd {
 

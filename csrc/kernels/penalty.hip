@@ -31,6 +31,7 @@
 // the host wrapper.  A row clears and probes only the 2^j >= 2 * count slots
 // it needs.
 #include "common.h"
+#include "api.h"
 
 // hipcc contracts a + b * c into one FMA by default, and through the inlined
 // __fmul_rn / __fadd_rn too (their bodies carry the header's contraction

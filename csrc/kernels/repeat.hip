@@ -48,6 +48,7 @@
 // needs.  L <= 8192 also bounds a thread's scan to 32 start positions, which
 // it remembers in a 32-bit mask across the barrier.
 #include "common.h"
+#include "api.h"
 
 namespace lsd {
 

@@ -37,6 +37,7 @@
 //           top_p >= 1 and min_p <= 0 (or null arrays) take the uncut
 //           arithmetic unchanged.  Pure nucleus sampling: top_k = 1024.
 #include "row_visit.h"
+#include "api.h"
 
 namespace lsd {
 

@@ -31,6 +31,7 @@
 // No atomics anywhere and every merge order is fixed by (T, Vp, S): two
 // launches on the same input give the same bits.
 #include "common.h"
+#include "api.h"
 
 namespace lsd {
 

@@ -18,6 +18,7 @@
 //     (ops/hip.py): q, scale -> bf16 [N, K] in a caller's scratch, 16 bytes in
 //     and 2 x 16 bytes out per lane, one rounding (bf16(float(q) * scale)).
 #include "common.h"
+#include "api.h"
 
 namespace lsd {
 

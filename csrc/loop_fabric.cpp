@@ -47,12 +47,6 @@
 
 namespace py = pybind11;
 
-extern "C" hipError_t lsd_loop_send(LoopChan* ch, void* ring, const void* src, uint64_t bytes,
-                                    LoopStatus* st, hipStream_t s);
-extern "C" hipError_t lsd_loop_recv(LoopChan* ch, const void* ring, void* dst, uint64_t bytes,
-                                    LoopStatus* st, hipStream_t s);
-extern "C" uint64_t lsd_loop_place(uint64_t head, uint64_t bytes, uint64_t cap);
-
 namespace {
 
 struct Fabric;

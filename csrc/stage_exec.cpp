@@ -30,13 +30,14 @@
 #include <string>
 #include <vector>
 
+#include "kernels/api.h"  // lsd_apply_rows (elementwise.hip)
+
 namespace py = pybind11;
 
 void lsd_rccl_recv_raw(int64_t h, void* ptr, size_t bytes, int peer, hipStream_t st);  // comm.cpp
 void lsd_loop_recv_raw(int64_t chan, void* ptr, size_t bytes, hipStream_t st);          // loop_fabric.cpp
 void lsd_loop_io_wait(int64_t io);
 void lsd_loop_io_done(int64_t io);
-extern "C" hipError_t lsd_apply_rows(const int64_t* args, int nargs, int b, hipStream_t st);  // elementwise.hip
 
 namespace {
 

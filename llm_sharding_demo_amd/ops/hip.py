@@ -299,9 +299,9 @@ class HipBackend(Backend):
         g = self._gemv_in(xn, w.shape[1], EPI_QKV, w.dtype == FP8)
         if g is not None:
             x, nc, gw, gb, eps = g
-            return self.C.gemv(x, w, b, EPI_QKV, nc, gw, gb, eps, None, cache_k, cache_v,
-                               meta.token_slots, meta.token_pos, mcfg.q_size, mcfg.kv_size,
-                               mcfg.head_dim, self._rope, **self._ws(w))
+            return self.C.gemv(x, w, b, EPI_QKV, nc, gw, gb, eps, kc=cache_k, vc=cache_v,
+                               tslot=meta.token_slots, tpos=meta.token_pos, q_size=mcfg.q_size,
+                               kv_size=mcfg.kv_size, hd=mcfg.head_dim, rope=self._rope, **self._ws(w))
         xn = self.materialize(xn)
         w = self._dense(w)
         if self.R.blaslt_qkv(xn.shape[0], w.shape[1], getattr(self, "decode", False)) and xn.is_contiguous():
@@ -332,8 +332,7 @@ class HipBackend(Backend):
         g = self._gemv_in(a, w.shape[1], code, w.dtype == FP8)
         if g is not None:
             x, nc, gw, gb, eps = g
-            return self.C.gemv(x, w, b, code, nc, gw, gb, eps, None, None, None, None, None,
-                               0, 0, 0, None, **self._ws(w))
+            return self.C.gemv(x, w, b, code, nc, gw, gb, eps, **self._ws(w))
         a = self.materialize(a)
         w = self._dense(w)
         dec = getattr(self, "decode", False)
@@ -352,8 +351,7 @@ class HipBackend(Backend):
         M, K = a.shape
         N = w.shape[0]
         if self._gemv_in(a, K, EPI_RESID, w.dtype == FP8) is not None:  # adds straight into r.x
-            self.C.gemv(a, w, b, EPI_RESID, 0, None, None, 0.0, r.x, None, None, None, None,
-                        0, 0, 0, None, **self._ws(w))
+            self.C.gemv(a, w, b, EPI_RESID, 0, None, None, 0.0, resid=r.x, **self._ws(w))
             return
         w = self._dense(w)
         if self.R.blaslt_resid(M, K, self._decode) and a.is_contiguous() \
@@ -373,8 +371,7 @@ class HipBackend(Backend):
         if g is not None:
             x, nc, gw, gb, eps = g
             if not (self.R.segmax and w.shape[0] % 8 == 0 and w.shape[0] > SAMPLER_ONE_LOAD):
-                return self.C.gemv(x, w, None, EPI_F32, nc, gw, gb, eps, None, None, None, None,
-                                   None, 0, 0, 0, None)
+                return self.C.gemv(x, w, None, EPI_F32, nc, gw, gb, eps)
             # one GEMV workgroup = one 8-logit segment: its epilogue writes the
             # segment maxima too, so the single-stream sampler reads ~100
             # candidate segments instead of three passes over a row too long
