@@ -191,13 +191,42 @@ GemmParams base_params(const torch::Tensor& a, const torch::Tensor& w, int64_t t
   return p;
 }
 
+// The same for the FP8-weight decode GEMM (csrc/kernels/gemm_w8.hip): w holds
+// E4M3 rows, wscale their fp32 scales [N]; p.W / p.ldw are a byte pointer and
+// a byte stride.  Kind 0 only: no other kernel reads FP8 weights.
+GemmParams w8_params(const torch::Tensor& a, const torch::Tensor& w, const torch::Tensor& wscale, int64_t tiled,
+                     int epi, const char* what) {
+  TORCH_CHECK(tiled == 0, what, ": FP8 weights run on the split-K decode kernel (kind 0) only, got kind ", tiled);
+  need(a, torch::kBFloat16, "a");
+  need(w, torch::kFloat8_e4m3fn, "w");
+  need_rows(a, "a");
+  need_rows(w, "w");
+  TORCH_CHECK(w.stride(0) % 16 == 0, "FP8 w rows must be 16-byte aligned");
+  TORCH_CHECK(a.size(1) == w.size(1), "K mismatch: a ", a.sizes(), " w ", w.sizes());
+  GemmParams p{};
+  p.A = bptr(a); p.lda = a.stride(0);
+  p.W = bptr(w); p.ldw = w.stride(0);
+  p.M = a.size(0); p.N = w.size(0); p.K = a.size(1);
+  p.splits = 1;
+  row_vec<const float>(wscale, p.N, what, "wscale");
+  TORCH_CHECK(p.M == 0 || lsd_gemm_w8_ok(p.M, p.N, p.K, epi), what, ": the FP8-weight GEMM needs K % 64 == 0 and ",
+              "N % 8 == 0 (silu_mul: N % 128 == 0), got M=", p.M, " N=", p.N, " K=", p.K);
+  return p;
+}
+
+GemmParams gemm_params(const torch::Tensor& a, const torch::Tensor& w, const c10::optional<torch::Tensor>& wscale,
+                       int64_t tiled, int epi, const char* what) {
+  return wscale.has_value() ? w8_params(a, w, *wscale, tiled, epi, what) : base_params(a, w, tiled);
+}
+
 // Launch with split-K bookkeeping: an in-kernel combine needs persistent
 // zeroed ticket counters (one per output tile) and an fp32 partial-tile
 // workspace, both sized from the plan that is then launched.
+// wscale: the FP8-weight kernel launches the (kind 0) plan.
 void run_gemm(GemmParams& p, int epi, int64_t tiled, int64_t splits,
               const c10::optional<torch::Tensor>& counters, const torch::Tensor& like,
-              const char* what) {
-  const int kt = tiled ? p.K / 64 : p.K / 32;
+              const char* what, const c10::optional<torch::Tensor>& wscale = c10::nullopt) {
+  const int kt = tiled || wscale.has_value() ? p.K / 64 : p.K / 32;
   TORCH_CHECK(splits >= 1 && splits <= kt, what, ": splits must be in [1, ", kt, "], got ", splits);
   p.splits = (int)splits;
   GemmPlan plan;
@@ -222,23 +251,24 @@ void run_gemm(GemmParams& p, int epi, int64_t tiled, int64_t splits,
     ws = wsbuf.data_ptr<float>();
   }
   p.stamps = g_stamps;
-  check_hip(lsd_gemm(&p, &plan, cnt, ws, cur_stream()), what);
+  if (wscale.has_value()) check_hip(lsd_gemm_w8(&p, wscale->data_ptr<float>(), &plan, cnt, ws, cur_stream()), what);
+  else check_hip(lsd_gemm(&p, &plan, cnt, ws, cur_stream()), what);
 }
 
 
 // out = act(a @ w^T + bias), bf16
 torch::Tensor linear(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> bias,
                      int64_t act, int64_t tiled, int64_t splits,
-                     c10::optional<torch::Tensor> counters) {
-  GemmParams p = base_params(a, w, tiled);
-  p.bias = opt_bias(bias, p.N);
+                     c10::optional<torch::Tensor> counters, c10::optional<torch::Tensor> wscale) {
   int epi = act == 1 ? EPI_GELU : (act == 2 ? EPI_SILU_MUL : EPI_BF16);
+  GemmParams p = gemm_params(a, w, wscale, tiled, epi, "linear");
+  p.bias = opt_bias(bias, p.N);
   if (epi == EPI_SILU_MUL) TORCH_CHECK(p.N % 32 == 0, "silu_mul needs N % 32 == 0");
   const int n_out = epi == EPI_SILU_MUL ? p.N / 2 : p.N;
   auto out = torch::empty({p.M, n_out}, a.options());
   if (p.M == 0) return out;
   p.out = out.data_ptr(); p.ldo = n_out;
-  run_gemm(p, epi, tiled, splits, counters, a, "linear");
+  run_gemm(p, epi, tiled, splits, counters, a, "linear", wscale);
   return out;
 }
 
@@ -246,11 +276,13 @@ torch::Tensor linear(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tens
 // 8-column segment, fp32 [M, N / 8] -- the sampler then reads the logits only
 // in the segments that can hold a top-k element (sample.hip)
 torch::Tensor linear_f32(torch::Tensor a, torch::Tensor w, int64_t tiled, int64_t splits,
-                         c10::optional<torch::Tensor> counters, c10::optional<torch::Tensor> segmax) {
-  GemmParams p = base_params(a, w, tiled);
+                         c10::optional<torch::Tensor> counters, c10::optional<torch::Tensor> segmax,
+                         c10::optional<torch::Tensor> wscale) {
+  GemmParams p = gemm_params(a, w, wscale, tiled, EPI_F32, "linear_f32");
   auto out = torch::empty({p.M, p.N}, a.options().dtype(torch::kFloat32));
   if (segmax.has_value()) {
-    TORCH_CHECK(tiled != 0, "linear_f32: segment maxima need a tiled kernel");
+    // ... or the FP8-weight decode kernel, whose fp32 stores always go through store_pass
+    TORCH_CHECK(tiled != 0 || wscale.has_value(), "linear_f32: segment maxima need a tiled kernel");
     need(*segmax, torch::kFloat32, "segmax");
     TORCH_CHECK(segmax->dim() == 2 && segmax->is_contiguous() && segmax->size(0) == p.M &&
                 segmax->size(1) == p.N / 8, "segmax must be contiguous fp32 [M, N / 8]");
@@ -259,7 +291,7 @@ torch::Tensor linear_f32(torch::Tensor a, torch::Tensor w, int64_t tiled, int64_
   }
   if (p.M == 0) return out;
   p.out = out.data_ptr(); p.ldo = p.N;
-  run_gemm(p, EPI_F32, tiled, splits, counters, a, "linear_f32");
+  run_gemm(p, EPI_F32, tiled, splits, counters, a, "linear_f32", wscale);
   return out;
 }
 
@@ -271,8 +303,9 @@ torch::Tensor linear_f32(torch::Tensor a, torch::Tensor w, int64_t tiled, int64_
 c10::optional<torch::Tensor> linear_residual(torch::Tensor a, torch::Tensor w,
                                               c10::optional<torch::Tensor> bias, torch::Tensor x,
                                               int64_t splits, int64_t tiled,
-                                              c10::optional<torch::Tensor> counters, bool defer) {
-  GemmParams p = base_params(a, w, tiled);
+                                              c10::optional<torch::Tensor> counters, bool defer,
+                                              c10::optional<torch::Tensor> wscale) {
+  GemmParams p = gemm_params(a, w, wscale, tiled, EPI_RESID, "linear_residual");
   need(x, torch::kFloat32, "x");
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && x.size(0) == p.M && x.size(1) == p.N,
               "residual x must be contiguous [M, N]");
@@ -289,12 +322,12 @@ c10::optional<torch::Tensor> linear_residual(torch::Tensor a, torch::Tensor w,
     auto slab = torch::empty({splits, p.M, p.N}, x.options().dtype(slab_bf16 ? torch::kBFloat16 : torch::kFloat32));
     p.slab = static_cast<float*>(slab.data_ptr());
     p.slab_bf16 = slab_bf16 ? 1 : 0;
-    run_gemm(p, EPI_SLAB, tiled, splits, c10::nullopt, x, "linear_residual(split)");
+    run_gemm(p, EPI_SLAB, tiled, splits, c10::nullopt, x, "linear_residual(split)", wscale);
     return slab;
   }
   p.bias = opt_bias(bias, p.N);
   p.out = x.data_ptr(); p.ldo = p.N;
-  run_gemm(p, EPI_RESID, tiled, splits, counters, x, "linear_residual");
+  run_gemm(p, EPI_RESID, tiled, splits, counters, x, "linear_residual", wscale);
   return c10::nullopt;
 }
 
@@ -303,8 +336,8 @@ torch::Tensor linear_qkv(torch::Tensor a, torch::Tensor w, c10::optional<torch::
                          torch::Tensor kc, torch::Tensor vc, torch::Tensor tslot,
                          torch::Tensor tpos, int64_t q_size, int64_t kv_size, int64_t hd,
                          c10::optional<torch::Tensor> rope, int64_t tiled, int64_t splits,
-                         c10::optional<torch::Tensor> counters) {
-  GemmParams p = base_params(a, w, tiled);
+                         c10::optional<torch::Tensor> counters, c10::optional<torch::Tensor> wscale) {
+  GemmParams p = gemm_params(a, w, wscale, tiled, EPI_QKV, "linear_qkv");
   p.bias = opt_bias(bias, p.N);
   qkv_target(p, p.M, kc, vc, tslot, tpos, q_size, kv_size, hd, rope, "linear_qkv");
   TORCH_CHECK(p.N == q_size + 2 * kv_size, "w rows must be q_size + 2*kv_size");
@@ -312,7 +345,7 @@ torch::Tensor linear_qkv(torch::Tensor a, torch::Tensor w, c10::optional<torch::
   auto q = torch::empty({p.M, q_size}, a.options());
   if (p.M == 0) return q;
   p.out = q.data_ptr(); p.ldo = q_size;
-  run_gemm(p, EPI_QKV, tiled, splits, counters, a, "linear_qkv");
+  run_gemm(p, EPI_QKV, tiled, splits, counters, a, "linear_qkv", wscale);
   return q;
 }
 
@@ -1021,11 +1054,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   lsd_register_exec(m);
   lsd_register_loopback(m);
   lsd_register_blaslt(m);
-  m.def("linear", &linear);
+  // wscale (all four): w is FP8 E4M3 rows with these fp32 row scales, run by gemm_w8.hip (kind 0)
+  m.def("linear", &linear, py::arg("a"), py::arg("w"), py::arg("bias"), py::arg("act"), py::arg("tiled"),
+        py::arg("splits"), py::arg("counters"), py::arg("wscale") = py::none());
   m.def("linear_f32", &linear_f32, py::arg("a"), py::arg("w"), py::arg("tiled"), py::arg("splits"),
-        py::arg("counters"), py::arg("segmax") = py::none());
-  m.def("linear_residual", &linear_residual);
-  m.def("linear_qkv", &linear_qkv);
+        py::arg("counters"), py::arg("segmax") = py::none(), py::arg("wscale") = py::none());
+  m.def("linear_residual", &linear_residual, py::arg("a"), py::arg("w"), py::arg("bias"), py::arg("x"),
+        py::arg("splits"), py::arg("tiled"), py::arg("counters"), py::arg("defer"), py::arg("wscale") = py::none());
+  m.def("linear_qkv", &linear_qkv, py::arg("a"), py::arg("w"), py::arg("bias"), py::arg("kc"), py::arg("vc"),
+        py::arg("tslot"), py::arg("tpos"), py::arg("q_size"), py::arg("kv_size"), py::arg("hd"), py::arg("rope"),
+        py::arg("tiled"), py::arg("splits"), py::arg("counters"), py::arg("wscale") = py::none());
+  m.def("gemm_w8_ok", [](int64_t M, int64_t N, int64_t K, int64_t epi) {
+    return lsd_gemm_w8_ok((int)M, (int)N, (int)K, (int)epi) != 0; });
   m.def("embed", &embed);
   m.def("norm", &norm);
   m.def("attn_decode", &attn_decode);

@@ -19,6 +19,7 @@ extern "C" {
 void lsd_gemm_plan(int M, int N, int K, int splits, int epi, int kind, lsd::GemmPlan* out);
 hipError_t lsd_gemm(const lsd::GemmParams* p, const lsd::GemmPlan* plan, int* cnt, float* ws, hipStream_t st);
 const char* lsd_gemm_last_launch();
+void lsd_gemm_note_launch(const char* tag);  // tag: a string literal
 void lsd_gemm_set_big_min(int v);
 void lsd_gemm_set_big_group(int v);
 void lsd_gemm_set_big_kind(int v);
@@ -37,6 +38,11 @@ int lsd_gemm_d256_bn(int kind, int M, int N, int K);
 int lsd_gemm_ring8_tiles(int M, int N, int K, int S);
 int lsd_gemm_sk_rblocks(int M, int N, int S);
 int lsd_gemm_sk_nw(int M, int epi);
+
+// gemm_w8.hip: a kind-0 plan on FP8 E4M3 weight rows (p->W bytes, p->ldw in bytes) with fp32 row scales
+int lsd_gemm_w8_ok(int M, int N, int K, int epi);
+hipError_t lsd_gemm_w8(const lsd::GemmParams* p, const float* wscale, const lsd::GemmPlan* plan, int* cnt, float* ws,
+                       hipStream_t st);
 
 // gemv.hip
 int lsd_gemv_ok_w(int M, int K, int epi, int norm, int w_fp8);

@@ -15,9 +15,10 @@ Device weight layout (set up once per stage by `prepare_stage`):
   * `weight_dtype="fp8_e4m3"`: after all of the above (so the scales travel
     with their rows) the blocks' four linear projections become E4M3 rows with
     one fp32 scale per row (csrc/kernels/wquant.hip), `w._lsd_scale`.  At
-    M <= gemv_max_m rows the FP8 GEMV streams them as they are; every other
-    GEMM first dequantises the weight into a per-lane bf16 scratch and then
-    runs exactly as it does on a bf16 weight.
+    M <= gemv_max_m rows the FP8 GEMV streams them as they are, and decode
+    GEMMs up to w8_max_m rows the FP8-weight MFMA kernel (gemm_w8.hip); every
+    other GEMM (prefill included) first dequantises the weight into a per-lane
+    bf16 scratch and then runs exactly as it does on a bf16 weight.
 """
 from __future__ import annotations
 
@@ -288,6 +289,11 @@ class HipBackend(Backend):
         """The GEMV's extra argument for an FP8 weight: its row scales."""
         return {"wscale": w._lsd_scale} if w.dtype == FP8 else {}
 
+    def _w8(self, M: int, w, epi: int) -> bool:
+        """This decode GEMM streams its FP8 weight in the FP8-weight kernel."""
+        return (w.dtype == FP8 and self._decode and self.R.gemv_max_m < M <= self.R.w8_max_m
+                and self.C.gemm_w8_ok(M, w.shape[0], w.shape[1], epi))
+
     def _dense(self, w):
         """The weight a GEMM other than the FP8 GEMV reads: an FP8 weight is
         dequantised into this lane's scratch (wquant.hip), a bf16 one is itself."""
@@ -303,6 +309,11 @@ class HipBackend(Backend):
                                tslot=meta.token_slots, tpos=meta.token_pos, q_size=mcfg.q_size,
                                kv_size=mcfg.kv_size, hd=mcfg.head_dim, rope=self._rope, **self._ws(w))
         xn = self.materialize(xn)
+        if self._w8(xn.shape[0], w, EPI_QKV):
+            splits = self.R.w8_splits(xn.shape[0], w.shape[0], w.shape[1], self.concurrency)
+            return self.C.linear_qkv(xn, w, b, cache_k, cache_v, meta.token_slots, meta.token_pos,
+                                     mcfg.q_size, mcfg.kv_size, mcfg.head_dim, self._rope,
+                                     0, splits, self.counters, wscale=w._lsd_scale)
         w = self._dense(w)
         if self.R.blaslt_qkv(xn.shape[0], w.shape[1], getattr(self, "decode", False)) and xn.is_contiguous():
             y = self.C.blaslt_f32(xn, w, self.lane)
@@ -334,6 +345,9 @@ class HipBackend(Backend):
             x, nc, gw, gb, eps = g
             return self.C.gemv(x, w, b, code, nc, gw, gb, eps, **self._ws(w))
         a = self.materialize(a)
+        if self._w8(a.shape[0], w, code):
+            splits = self.R.w8_splits(a.shape[0], w.shape[0], w.shape[1], self.concurrency, 2 if code == 2 else 1)
+            return self.C.linear(a, w, b, code, 0, splits, self.counters, wscale=w._lsd_scale)
         w = self._dense(w)
         dec = getattr(self, "decode", False)
         if code == 1 and self.R.blaslt_gelu(a.shape[0], dec) and a.is_contiguous():
@@ -352,6 +366,13 @@ class HipBackend(Backend):
         N = w.shape[0]
         if self._gemv_in(a, K, EPI_RESID, w.dtype == FP8) is not None:  # adds straight into r.x
             self.C.gemv(a, w, b, EPI_RESID, 0, None, None, 0.0, resid=r.x, **self._ws(w))
+            return
+        if self._w8(M, w, EPI_RESID):
+            splits = self.R.w8_resid_splits(M, N, K, getattr(self, "concurrency", 1))
+            defer = bool(self.R.defer_resid) and splits > 1
+            slab = self.C.linear_residual(a, w, b, r.x, splits, 0, self.counters, defer, wscale=w._lsd_scale)
+            if slab is not None:
+                r.pending.append((slab, b))
             return
         w = self._dense(w)
         if self.R.blaslt_resid(M, K, self._decode) and a.is_contiguous() \

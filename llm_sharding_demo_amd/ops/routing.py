@@ -73,6 +73,15 @@ class Routing:
     sk_min_steps: int = 2
     sk_rows: int = 64
     defer_resid: int = 1  # residual split-K partials as slabs folded by the next norm
+    # FP8 weights (weight_dtype="fp8_e4m3"): decode GEMMs of gemv_max_m < rows <=
+    # w8_max_m stream the E4M3 rows in the FP8-weight kernel (gemm_w8.hip)
+    # instead of dequantising into the bf16 scratch first (0: always dequantise).
+    # 128: the largest measured row count at which it beats the dequant route on
+    # all eight GPT-2 XL / Llama-3 8B projections by more than that route's own
+    # spread (1.51-2.24x at 128 rows; at 256 Llama-3 8B gate_up is inside it:
+    # "M": 256 ... "dequant_us": 126.56, "w8_us": 119.73, "dequant_spread_us": 7.84,
+    # "w8_wins": false; profiles/gemm_w8_ab.log)
+    w8_max_m: int = 128
     # LDS ring kernels: grids of <= tiled3_max 128x64 tiles (QKV at 256 rows
     # 25.8 -> 20.4 us; profiles/r1_ab_ring_n64.log), ring depth, tile columns
     # (0 = auto: 32-wide below ring_fill 64-wide workgroups; r2_ring_tn32.log)
@@ -182,6 +191,18 @@ class Routing:
         tiles = math.ceil(N / (64 * nw))  # >= the target: never row-blocked
         target = self.sk_target or max(128, 384 // max(1, lanes))
         return max(1, min(math.ceil(target / tiles), K // 32 // self.sk_min_steps or 1))
+
+    def w8_splits(self, M: int, N: int, K: int, lanes: int = 1, nw: int = 1) -> int:
+        """K splits of a non-residual GEMM on the FP8-weight kernel: sk_splits,
+        with at least two of that kernel's 64-k blocks per split."""
+        return max(1, min(self.sk_splits(M, N, K, lanes, nw), K // 64 // 2 or 1))
+
+    def w8_resid_splits(self, M: int, N: int, K: int, lanes: int = 1) -> int:
+        """... and of a residual projection: the split-K kernel's own rule
+        (deferred slabs: ~800 k per split, 4..8 splits)."""
+        if self.defer_resid:
+            return max(1, min(8, max(4, K // 800), K // 64))
+        return self.w8_splits(M, N, K, lanes)
 
     def gemm_kw(self, M: int, N: int, K: int, lanes: int = 1, nw: int = 1):
         """(tiled kind, K splits) of a non-residual GEMM (QKV, MLP-up,

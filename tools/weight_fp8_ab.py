@@ -9,7 +9,18 @@ no copy is still cached when its turn comes again; --hot: one copy, the
 cache-resident figure).  The QKV shapes run the plain bf16 epilogue (no cache
 to append to); the others run the epilogue the model uses.  One JSON line per
 case: median of 5 rounds of graph-replayed launches, weight bytes per us, and
-the FP8 speed-up against the byte ratio of 2."""
+the FP8 speed-up against the byte ratio of 2.
+
+    python tools/weight_fp8_ab.py --gemm [--label NAME]
+
+The decode GEMMs of the same shapes at M = 16 .. 512 rows through the backend
+(ops/hip.py), three routes alternating within each of 5 rounds: (a) the bf16
+weight on the kernel ops/routing.py picks for it, (b) the FP8 weight on the
+dequant route (dequant_rows_fp8 into the scratch + that kernel; w8_max_m = 0),
+(c) the FP8 weight on the FP8-weight kernel (csrc/kernels/gemm_w8.hip).  One
+JSON line per case: medians in us, (b)'s spread (max - min of its rounds), the
+weight TB/s of (a) and (c), and whether (c) beats (b) by more than that spread
+-- what sets Routing.w8_max_m."""
 from __future__ import annotations
 
 import argparse
@@ -33,12 +44,72 @@ SHAPES = [("gpt2-xl", "c_attn", 4800, 1600, 0), ("gpt2-xl", "attn.c_proj", 1600,
           ("llama-3-8b", "gate_up", 28672, 4096, 2), ("llama-3-8b", "down_proj", 4096, 14336, 4)]
 
 
+def gemm_rows(a):
+    from llm_sharding_demo_amd.ops import Residual
+    from llm_sharding_demo_amd.ops.hip import HipBackend
+    from llm_sharding_demo_amd.ops.routing import Routing
+
+    dev = "cuda"
+    bes = {}
+    for route, m in (("dequant", 0), ("w8", 1 << 30)):
+        be = bes[route] = HipBackend()
+        be.R = Routing.from_env("").replace(w8_max_m=m)
+        be._counters = torch.zeros(8, 1 << 16, dtype=torch.int32, device=dev)
+    C = bes["w8"].C
+    for model, name, N, K, epi in SHAPES:
+        g = torch.Generator(device=dev).manual_seed(1)
+        copies = max(2, -(-(1 << 30) // (N * K)))
+        w16 = [(torch.randn(N, K, device=dev, generator=g) * 0.03).bfloat16() for _ in range(copies)]
+        w8 = []
+        for w in w16:
+            q, sc = C.quantize_rows_fp8(w)
+            q._lsd_scale = sc
+            w8.append(q)
+        for be in bes.values():
+            be._wscratch = torch.empty(1, N * K, dtype=torch.bfloat16, device=dev)
+        bias = None if epi == 2 else torch.zeros(N, dtype=torch.bfloat16, device=dev)
+        for M in (16, 32, 64, 128, 256, 512):
+            x = torch.randn(M, K, device=dev, generator=g).bfloat16()
+            r = Residual(torch.zeros(M, N, device=dev))
+            turn = [0]
+
+            def run(be, ws):
+                turn[0] += 1
+                w = ws[turn[0] % len(ws)]
+                if epi == 4:
+                    be.linear_residual(x, w, bias, r)
+                    r.pending.clear()  # the fold into the next norm is the same on every route
+                else:
+                    be.linear(x, w, bias, {0: "none", 1: "gelu", 2: "silu_mul"}[epi])
+
+            routes = {"bf16": (bes["dequant"], w16), "dequant": (bes["dequant"], w8), "w8": (bes["w8"], w8)}
+            t = {k: [] for k in routes}
+            for _ in range(5):
+                for k, (be, ws) in routes.items():
+                    t[k].append(timeit(lambda: run(be, ws), iters=max(copies, 32)))
+            med = {k: statistics.median(v) for k, v in t.items()}
+            spread = max(t["dequant"]) - min(t["dequant"])
+            print(json.dumps({"label": a.label, "model": model, "proj": name, "N": N, "K": K, "M": M,
+                              "bf16_us": round(med["bf16"], 2), "dequant_us": round(med["dequant"], 2),
+                              "w8_us": round(med["w8"], 2), "dequant_spread_us": round(spread, 2),
+                              "bf16_TBps": round(2 * N * K / med["bf16"] / 1e6, 3),
+                              "w8_TBps": round(N * K / med["w8"] / 1e6, 3),
+                              "w8_vs_dequant": round(med["dequant"] / med["w8"], 3),
+                              "w8_vs_bf16": round(med["bf16"] / med["w8"], 3),
+                              "w8_wins": bool(med["dequant"] - med["w8"] > spread)}), flush=True)
+        del w16, w8
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--label", default="this")
     ap.add_argument("--hot", action="store_true")
+    ap.add_argument("--gemm", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
+    if a.gemm:
+        return gemm_rows(a)
     from llm_sharding_demo_amd.ops.hip import _load
 
     C = _load()
