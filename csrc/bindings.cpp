@@ -191,12 +191,14 @@ GemmParams base_params(const torch::Tensor& a, const torch::Tensor& w, int64_t t
   return p;
 }
 
-// The same for the FP8-weight decode GEMM (csrc/kernels/gemm_w8.hip): w holds
+// The same for the FP8-weight decode GEMMs (csrc/kernels/gemm_w8.hip): w holds
 // E4M3 rows, wscale their fp32 scales [N]; p.W / p.ldw are a byte pointer and
-// a byte stride.  Kind 0 only: no other kernel reads FP8 weights.
+// a byte stride.  Kind 0 (split-K kernel) and kinds 2 / 3 (256-row-block
+// kernel): the tiled family (kind 1) has no kernel that reads FP8 weights.
 GemmParams w8_params(const torch::Tensor& a, const torch::Tensor& w, const torch::Tensor& wscale, int64_t tiled,
                      int epi, const char* what) {
-  TORCH_CHECK(tiled == 0, what, ": FP8 weights run on the split-K decode kernel (kind 0) only, got kind ", tiled);
+  TORCH_CHECK(tiled == 0 || tiled == 2 || tiled == 3, what, ": FP8 weights run on the split-K decode kernel "
+              "(kind 0) or the 256-row-block kernel (kind 2 / 3) only, got kind ", tiled);
   need(a, torch::kBFloat16, "a");
   need(w, torch::kFloat8_e4m3fn, "w");
   need_rows(a, "a");
@@ -222,7 +224,7 @@ GemmParams gemm_params(const torch::Tensor& a, const torch::Tensor& w, const c10
 // Launch with split-K bookkeeping: an in-kernel combine needs persistent
 // zeroed ticket counters (one per output tile) and an fp32 partial-tile
 // workspace, both sized from the plan that is then launched.
-// wscale: the FP8-weight kernel launches the (kind 0) plan.
+// wscale: an FP8-weight kernel launches the (kind 0 / 2 / 3) plan.
 void run_gemm(GemmParams& p, int epi, int64_t tiled, int64_t splits,
               const c10::optional<torch::Tensor>& counters, const torch::Tensor& like,
               const char* what, const c10::optional<torch::Tensor>& wscale = c10::nullopt) {
@@ -1054,7 +1056,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   lsd_register_exec(m);
   lsd_register_loopback(m);
   lsd_register_blaslt(m);
-  // wscale (all four): w is FP8 E4M3 rows with these fp32 row scales, run by gemm_w8.hip (kind 0)
+  // wscale (all four): w is FP8 E4M3 rows with these fp32 row scales, run by gemm_w8.hip (kind 0, 2 or 3)
   m.def("linear", &linear, py::arg("a"), py::arg("w"), py::arg("bias"), py::arg("act"), py::arg("tiled"),
         py::arg("splits"), py::arg("counters"), py::arg("wscale") = py::none());
   m.def("linear_f32", &linear_f32, py::arg("a"), py::arg("w"), py::arg("tiled"), py::arg("splits"),

@@ -39,7 +39,7 @@ int lsd_gemm_ring8_tiles(int M, int N, int K, int S);
 int lsd_gemm_sk_rblocks(int M, int N, int S);
 int lsd_gemm_sk_nw(int M, int epi);
 
-// gemm_w8.hip: a kind-0 plan on FP8 E4M3 weight rows (p->W bytes, p->ldw in bytes) with fp32 row scales
+// gemm_w8.hip: a kind-0 or kind-2 / 3 plan on FP8 E4M3 weight rows (p->W bytes, p->ldw in bytes) with fp32 row scales
 int lsd_gemm_w8_ok(int M, int N, int K, int epi);
 hipError_t lsd_gemm_w8(const lsd::GemmParams* p, const float* wscale, const lsd::GemmPlan* plan, int* cnt, float* ws,
                        hipStream_t st);

@@ -5,7 +5,9 @@
 // the bf16 MFMA loop: no bf16 copy of the weight is ever written.  Activations
 // stay bf16, the MFMA is v_mfma_f32_16x16x32_bf16, accumulation is fp32, and
 // the row scale is applied to the fp32 accumulator -- the arithmetic of
-// reference.linear over the dequantised weights.
+// reference.linear over the dequantised weights.  Two kernels: gemm_w8_kernel
+// (split-K, kind-0 plans; described here) and, further down, gemm_w8_d256_kernel
+// (one workgroup per 256-row block x column tile, kind-2 / 3 plans).
 //
 // Work split, staging and combine are gemm_sk_kernel's (gemm.hip): grid =
 // (column tiles of 64 NW, K splits, row blocks of 16 MT rows), 4 waves, wave w
@@ -329,6 +331,294 @@ void gemm_w8_kernel(GemmParams p, const float* __restrict__ wscale,
   }
 }
 
+// ---------------------------------------------------------------------------
+// FP8-weight all-rows decode GEMM, 129-1024 rows: one workgroup owns every row
+// of a 256-row block x BN columns
+// ---------------------------------------------------------------------------
+// The split-K kernel above reads A once per 128-row block and column tile and
+// is LDS-bound from MT = 2 on; the bf16 path covers this row range with
+// gemm_d256_kernel (gemm.hip).  This is that kernel's work split on E4M3
+// weight rows: plan_gemm(kind 2 / 3) sizes grid, counters and workspace for
+// both (512 threads, tile = remapped id / S, column-major over 256-row blocks,
+// k-step 64, S-way split K, lane-major partials of 256 x BN floats per tile).
+//
+// W through LDS as FP8, staged 128 k at a time.  An E4M3 row is 64 B per
+// k-step, half a cache line, so W is staged once per PAIR of k-steps: one
+// LDS-DMA wave-instruction (64 lanes x 16 B) reads 8 rows x 128 B, full lines.
+// The LDS holds two rings in ONE array: SLOTS A images of [256][64 k] bf16
+// (32 KiB, gemm_d256's) and NWS = SLOTS / 2 + 1 W images of [BN][128 k] bytes
+// (BN x 128 B = the bytes of ONE bf16 k-step image, for two steps).  With
+// D = SLOTS - 1 steps in flight, the pair issued with step 2P meets the pairs
+// of steps 2P - D .. 2P - 1 alive: ceil(D / 2) + 1 = NWS images.  LDS per
+// (BN, SLOTS): (64,2) 80, (64,3) 112, (64,4) 152, (128,2) 96 -> 132 (C tile),
+// (128,3) 128 -> 132 KiB.  A pair's second half past the end of K re-reads the
+// last block (never multiplied); a split's odd last step wastes 64 B per row.
+// Steps are counted from the split's first, so even steps issue 4 + BN / 64
+// DMAs per thread and odd steps 4: the counted vmcnt of step t allows the
+// loads of the `later` steps after it, by the parity of t.  One raw barrier
+// per step, as in gemm_d256_kernel (its comments say why).
+//
+// LDS images, both conflict-free.  Both are 128-byte rows of eight 16-byte
+// chunks with chunk c of row `row` at position c ^ ((row >> 1) & 7) (the DMA
+// swizzles the SOURCE address, the reads apply the same XOR: lds_frag's
+// image).  A ds_read_b128 serves 16 lanes at a time, lanes r = 0..15 of one
+// group g: rows 16 t + r at one logical chunk c.  16-byte bank group =
+// 8 (row & 1) + (c ^ (row >> 1) & 7); over r, (row >> 1) & 7 takes every value
+// once per parity of row, so the 16 lanes hit 16 distinct bank groups.
+//   * A, MFMA step s of the k-step: chunk 2 g + s (k = 16 g + 8 s .. + 7);
+//   * W: chunk 4 h + g of the pair's half h = 16 BYTES = k 16 g .. + 15 of the
+//     step: low 8 bytes are step 0's B fragment, high 8 step 1's -- the
+//     k-permutation of gemm_w8_kernel, A and B agree on it.
+//
+// Wave grid 4 (M) x 2 (N): wave w owns rows 64 (w >> 1) .. + 63 x columns
+// BN / 2 (w & 1) .. -- 4 x BN / 32 accumulator tiles, as many registers as the
+// bf16 kernel's 8 x 1 grid (2 x BN / 16), so the lane-major partial tile keeps
+// its size.  Per MFMA step a wave converts BN / 32 fragments (4 converts
+// each) for 4 x BN / 32 MFMAs: ONE v_cvt_scalef32_pk_bf16_fp8 PER MFMA (8 x 1
+// would convert the whole W tile in every wave: 2 per MFMA), and per k-step
+// 8 + BN / 32 ds_read_b128 (bf16 kernel: 4 + BN / 4).  A bf16 LDS image
+// converted once would cost an LDS write, a second barrier per step and the
+// bf16 kernel's LDS bytes again.  (64, 2), at 127 VGPRs and 80 KiB, happens to
+// let two workgroups share a CU; no default reaches it (d256_slots = 3) and
+// nothing here is tuned for that.  Step 1's fragments are converted ahead of
+// step 0's MFMAs, which cover them; step 0's own converts are covered by the
+// SIMD's other wave (a step's bytes only become visible at its barrier).
+//
+// Row scale: one register per column tile of the lane, applied at the three
+// sites of gemm_w8_kernel.  Combine: gemm_d256_kernel's (fixed split order,
+// counter re-armed by the last arriver).
+template <int BN, int SLOTS>
+constexpr int w8d_smem() {
+  constexpr int ring = SLOTS * 256 * 128 + (SLOTS / 2 + 1) * BN * 128;
+  return ring > 256 * (BN + 4) * 4 ? ring : 256 * (BN + 4) * 4;
+}
+
+template <int EPI, int BN, int SLOTS>
+__global__ LSD_NO_PK_F32 __launch_bounds__(512)
+void gemm_w8_d256_kernel(GemmParams p, const float* __restrict__ wscale, int* __restrict__ cnt,
+                         float* __restrict__ ws) {
+  constexpr int NJ = BN / 32;            // 16-column MFMA tiles per wave
+  constexpr int A_BYTES = 256 * 128;     // [256][64 k] bf16
+  constexpr int W_BYTES = BN * 128;      // [BN][128 k] E4M3
+  constexpr int NWS = SLOTS / 2 + 1;     // W images
+  constexpr int LA = 4, LW = BN / 64;    // DMAs per thread: an A image, a W image
+  constexpr int D = SLOTS - 1;           // k-steps in flight
+  constexpr int SMEM = w8d_smem<BN, SLOTS>();
+  static_assert(SLOTS >= 2 && SLOTS <= 4 && SLOTS * A_BYTES + NWS * W_BYTES <= 160 * 1024, "LDS rings");
+  static_assert(2 * LA + LW <= 63, "vmcnt range");
+  __shared__ __attribute__((aligned(16))) char smem[SMEM];
+  int* s_flag = reinterpret_cast<int*>(smem);  // the rings are dead by then
+  char* const wring = smem + SLOTS * A_BYTES;
+
+  const int S = p.splits;
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
+  const int tile = bid / S, split = bid % S;
+  const int RB = (p.M + 255) / 256;
+  const int rb = tile % RB, n0 = (tile / RB) * BN, m0 = rb * 256;
+  const int KT = p.K >> 6;
+  const int kb = (int)((long)KT * split / S), ke = (int)((long)KT * (split + 1) / S);
+  const int nst = ke - kb;
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int wr = w >> 1, wc = w & 1;
+
+  // a partial last tile re-reads row N - 1 and its scale; never stored
+  float sc[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) sc[j] = wscale[min(n0 + wc * (BN / 2) + j * 16 + r, p.N - 1)];
+
+  f32x4 acc[4][NJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // step t (from the split's first): A image into slot `slot`; even t: the W
+  // image of steps t, t + 1.  Wave-instruction = 1 KiB = 8 rows of 128 B.
+  const int srow = lane >> 3;
+  auto issue = [&](int t, int slot) LSD_INL {
+#pragma unroll
+    for (int q = 0; q < LA; ++q) {
+      const int inst = w * LA + q, row = inst * 8 + srow;
+      const int lch = (lane & 7) ^ ((row >> 1) & 7);
+      glds16(p.A + (long)min(m0 + row, p.M - 1) * p.lda + (kb + t) * 64 + lch * 8,
+             smem + slot * A_BYTES + inst * 1024);
+    }
+    if (t & 1) return;
+    char* wd = wring + ((t >> 1) % NWS) * W_BYTES;
+#pragma unroll
+    for (int q = 0; q < LW; ++q) {
+      const int inst = w * LW + q, row = inst * 8 + srow;
+      const int lch = (lane & 7) ^ ((row >> 1) & 7);
+      const int blk = min(kb + t + (lch >> 2), KT - 1);
+      glds16(reinterpret_cast<const unsigned char*>(p.W) + (long)min(n0 + row, p.N - 1) * p.ldw + blk * 64 +
+                 (lch & 3) * 16,
+             wd + inst * 1024);
+    }
+  };
+#pragma unroll
+  for (int d = 0; d < D; ++d)
+    if (d < nst) issue(d, d);
+  int slot = 0;
+  for (int t = 0; t < nst; ++t) {
+    // this thread's DMAs of step t landed; those of the later steps stay in flight
+    const int later = min(D - 1, nst - 1 - t);
+    if (D >= 3 && later >= 2) __builtin_amdgcn_s_waitcnt(vmcnt_imm(2 * LA + LW));
+    else if (later == 1 && (t & 1)) __builtin_amdgcn_s_waitcnt(vmcnt_imm(LA + LW));
+    else if (later == 1) __builtin_amdgcn_s_waitcnt(vmcnt_imm(LA));
+    else __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
+    // publishes every wave's DMA of step t AND proves every wave is done with
+    // step t - 1, whose A slot (and, t even, W image) is refilled right after
+    __builtin_amdgcn_s_barrier();
+    if (t + D < nst) issue(t + D, slot == 0 ? SLOTS - 1 : slot - 1);
+    const char* ta = smem + slot * A_BYTES;
+    const char* tw = wring + ((t >> 1) % NWS) * W_BYTES;
+    u32x4 wb[NJ];
+    bf16x8 a0[4], a1[4], b0[NJ], b1[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int row = wc * (BN / 2) + j * 16 + r;
+      wb[j] = *reinterpret_cast<const u32x4*>(tw + row * 128 + (((4 * (t & 1) + g) ^ ((row >> 1) & 7)) << 4));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = wr * 64 + i * 16 + r;
+      a0[i] = *reinterpret_cast<const bf16x8*>(ta + row * 128 + (((2 * g) ^ ((row >> 1) & 7)) << 4));
+      a1[i] = *reinterpret_cast<const bf16x8*>(ta + row * 128 + (((2 * g + 1) ^ ((row >> 1) & 7)) << 4));
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) b0[j] = w8_frag<0>(wb[j]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) b1[j] = w8_frag<1>(wb[j]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[i][j] = mfma16(a0[i], b0[j], acc[i][j]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[i][j] = mfma16(a1[i], b1[j], acc[i][j]);
+    slot = slot == SLOTS - 1 ? 0 : slot + 1;
+  }
+
+  if (S > 1 && EPI != EPI_SLAB) {
+    // publish this split's RAW partial tile, thread t's (i, j) accumulator at
+    // ((i * NJ + j) * 512 + t) * 16 B; the last arriver sums all S in split order
+    constexpr int PER_BLOCK = 4 * NJ * 512;  // f32x4 per split tile = 256 x BN floats
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        ws + (long)tile * S * PER_BLOCK * 4, (short)0, S * PER_BLOCK * 16, 0x00020000);
+    const int toff = threadIdx.x * 16;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rs,
+                                               split * PER_BLOCK * 16 + (i * NJ + j) * 8192 + toff, 0, 16);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    block_sync();
+    if (threadIdx.x == 0) {
+      const int t = __hip_atomic_fetch_add(cnt + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      *s_flag = (t == S - 1);
+      if (t == S - 1) __hip_atomic_store(cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    block_sync();
+    if (*s_flag == 0) return;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // every slab load of a group in flight before the adds; clamped index x
+    // 0/1 mask, no per-load branch; 32 f32x4 (128 VGPRs) of partials in flight
+    constexpr int RG = 8 / NJ;
+    for (int s0 = 0; s0 < S; s0 += RG) {
+      f32x4 v[RG][4][NJ];
+#pragma unroll
+      for (int u = 0; u < RG; ++u) {
+        const int s2 = min(s0 + u, S - 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+            v[u][i][j] = __builtin_bit_cast(
+                f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, s2 * PER_BLOCK * 16 + (i * NJ + j) * 8192 + toff,
+                                                             0, 16));
+      }
+#pragma unroll
+      for (int u = 0; u < RG; ++u) {
+        const float msk = (s0 + u < S) ? 1.f : 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) acc[i][j] += v[u][i][j] * msk;
+      }
+    }
+  }
+
+  // The row scale, once: the whole sum (S = 1, or the last arriver's), or this
+  // split's own partial on its way to a slab.
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] *= sc[j];
+
+  // Epilogue through the fp32 [256][BN + 4] C tile over the rings (every DMA
+  // waited for; the barrier keeps it off a slot another wave still reads).
+  constexpr int CLD = BN + 4;
+  constexpr int CPR = BN / 8;
+  block_sync();
+  float* ct = reinterpret_cast<float*>(smem);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        ct[(wr * 64 + i * 16 + 4 * g + q) * CLD + wc * (BN / 2) + j * 16 + r] = acc[i][j][q];
+  block_sync();
+  if constexpr (EPI != EPI_SILU_MUL) {
+    store_pass<EPI, (256 * CPR + 511) / 512, 512>(
+        p, 256 * CPR, split, [&](int c, int& m, int& n, const float*& src) LSD_INL {
+          const int row = c / CPR, ch = c % CPR;
+          m = m0 + row;
+          n = n0 + ch * 8;
+          src = ct + row * CLD + ch * 8;
+          return m < p.M && n < p.N;
+        });
+  } else {
+    // interleaved [gate16 | up16] 32-column blocks: a gate chunk pairs with
+    // the up chunk 16 columns right (same tile: BN % 32 == 0)
+    for (int c = threadIdx.x; c < 256 * CPR; c += 512) {
+      const int row = c / CPR, ch = c % CPR, m = m0 + row, n = n0 + ch * 8;
+      if (m >= p.M || n >= p.N || (ch & 3) >= 2) continue;
+      const float* src = ct + row * CLD + ch * 8;
+      bf16x8 o;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const f32x4 gt = *reinterpret_cast<const f32x4*>(src + 4 * h);
+        const f32x4 up = *reinterpret_cast<const f32x4*>(src + 16 + 4 * h);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[4 * h + e] = f2bf(silu(gt[e]) * up[e]);
+      }
+      st8(reinterpret_cast<bf16*>(p.out) + (long)m * p.ldo + (n >> 5) * 16 + (n & 15), o);
+    }
+  }
+}
+
+template <int EPI>
+static hipError_t launch_w8_d256(const GemmParams& p, const float* wscale, const GemmPlan& pl, int* cnt, float* ws,
+                                 hipStream_t st) {
+  const dim3 grid(pl.grid[0]), block(512);
+#define LSD_W8D(BN_, SLOTS_)                                                                            \
+  if (pl.tn == BN_ && pl.slots == SLOTS_) {                                                             \
+    lsd_gemm_note_launch("w8d256<" #BN_ "," #SLOTS_ ">");                                               \
+    hipLaunchKernelGGL((gemm_w8_d256_kernel<EPI, BN_, SLOTS_>), grid, block, 0, st, p, wscale, cnt, ws); \
+    return hipGetLastError();                                                                           \
+  }
+  LSD_W8D(64, 2) LSD_W8D(64, 3) LSD_W8D(64, 4) LSD_W8D(128, 2) LSD_W8D(128, 3)
+#undef LSD_W8D
+  return hipErrorInvalidValue;
+}
+
 template <int EPI, int NW>
 static hipError_t launch_w8(const GemmParams& p, const float* wscale, const GemmPlan& pl, int* cnt, float* ws,
                             hipStream_t st) {
@@ -368,16 +658,32 @@ extern "C" int lsd_gemm_w8_ok(int M, int N, int K, int epi) {
   return epi == EPI_SILU_MUL ? N % 128 == 0 : N % 8 == 0;
 }
 
-// Launches a kind-0 plan of plan_gemm() on the FP8-weight kernel.  p->W holds
+// Launches a plan of plan_gemm() on an FP8-weight kernel: kind 0 (GK_SK) on
+// gemm_w8_kernel, kind 2 / 3 (GK_D256) on gemm_w8_d256_kernel.  p->W holds
 // E4M3 bytes, p->ldw is the row stride in bytes.  No launch on a refusal.
 extern "C" hipError_t lsd_gemm_w8(const GemmParams* p, const float* wscale, const GemmPlan* plan, int* cnt, float* ws,
                                   hipStream_t st) {
   const GemmPlan& pl = *plan;
-  if (!pl.valid || pl.kernel != GK_SK || pl.block != 256) return hipErrorInvalidValue;
+  const bool rows = pl.kernel == GK_D256;
+  if (!pl.valid || (rows ? pl.block != 512 : pl.kernel != GK_SK || pl.block != 256))
+    return hipErrorInvalidValue;
   if (pl.M != p->M || pl.N != p->N || pl.K != p->K || pl.splits != p->splits) return hipErrorInvalidValue;
   if (!lsd_gemm_w8_ok(p->M, p->N, p->K, pl.epi) || p->splits > p->K / 64) return hipErrorInvalidValue;
   if (wscale == nullptr || p->ldw % 16 != 0 || p->ldw < p->K) return hipErrorInvalidValue;
   if (pl.combine_tiles > 0 && (cnt == nullptr || ws == nullptr)) return hipErrorInvalidValue;
+  if (rows) {
+    if (pl.combine_tiles > 0 && pl.tile_floats != 256L * pl.tn) return hipErrorInvalidValue;
+    switch (pl.epi) {
+      case EPI_BF16: return launch_w8_d256<EPI_BF16>(*p, wscale, pl, cnt, ws, st);
+      case EPI_GELU: return launch_w8_d256<EPI_GELU>(*p, wscale, pl, cnt, ws, st);
+      case EPI_SILU_MUL: return launch_w8_d256<EPI_SILU_MUL>(*p, wscale, pl, cnt, ws, st);
+      case EPI_F32: return launch_w8_d256<EPI_F32>(*p, wscale, pl, cnt, ws, st);
+      case EPI_RESID: return launch_w8_d256<EPI_RESID>(*p, wscale, pl, cnt, ws, st);
+      case EPI_QKV: return launch_w8_d256<EPI_QKV>(*p, wscale, pl, cnt, ws, st);
+      case EPI_SLAB: return launch_w8_d256<EPI_SLAB>(*p, wscale, pl, cnt, ws, st);
+      default: return hipErrorInvalidValue;
+    }
+  }
   switch (pl.epi) {
     case EPI_BF16: return launch_w8_epi<EPI_BF16>(*p, wscale, pl, cnt, ws, st);
     case EPI_GELU: return launch_w8_epi<EPI_GELU>(*p, wscale, pl, cnt, ws, st);

@@ -16,7 +16,8 @@ Device weight layout (set up once per stage by `prepare_stage`):
     with their rows) the blocks' four linear projections become E4M3 rows with
     one fp32 scale per row (csrc/kernels/wquant.hip), `w._lsd_scale`.  At
     M <= gemv_max_m rows the FP8 GEMV streams them as they are, and decode
-    GEMMs up to w8_max_m rows the FP8-weight MFMA kernel (gemm_w8.hip); every
+    GEMMs up to w8_max_m rows the FP8-weight MFMA kernels (gemm_w8.hip: split-K
+    up to w8_sk_max_m rows, one workgroup per 256-row block above); every
     other GEMM (prefill included) first dequantises the weight into a per-lane
     bf16 scratch and then runs exactly as it does on a bf16 weight.
 """
@@ -30,7 +31,7 @@ import torch
 
 from . import Backend, Residual, dequant_lanes
 from . import reference as ref
-from .routing import Routing
+from .routing import D256_MAX_M, Routing
 
 _C = None
 _ERR: Optional[BaseException] = None
@@ -290,9 +291,17 @@ class HipBackend(Backend):
         return {"wscale": w._lsd_scale} if w.dtype == FP8 else {}
 
     def _w8(self, M: int, w, epi: int) -> bool:
-        """This decode GEMM streams its FP8 weight in the FP8-weight kernel."""
-        return (w.dtype == FP8 and self._decode and self.R.gemv_max_m < M <= self.R.w8_max_m
+        """This decode GEMM streams its FP8 weight in an FP8-weight kernel."""
+        return (w.dtype == FP8 and self._decode and self.R.gemv_max_m < M <= min(self.R.w8_max_m, D256_MAX_M)
                 and self.C.gemm_w8_ok(M, w.shape[0], w.shape[1], epi))
+
+    def _w8_kw(self, M: int, N: int, K: int, nw: int = 1, resid: bool = False):
+        """(launch kind, K splits) on it: the split-K kernel up to w8_sk_max_m
+        rows, the all-rows kernel above."""
+        lanes = getattr(self, "concurrency", 1)
+        if M > self.R.w8_sk_max_m:
+            return self.R.w8_rows_kw(M, N, K, resid, lanes)
+        return 0, (self.R.w8_resid_splits(M, N, K, lanes) if resid else self.R.w8_splits(M, N, K, lanes, nw))
 
     def _dense(self, w):
         """The weight a GEMM other than the FP8 GEMV reads: an FP8 weight is
@@ -310,10 +319,10 @@ class HipBackend(Backend):
                                kv_size=mcfg.kv_size, hd=mcfg.head_dim, rope=self._rope, **self._ws(w))
         xn = self.materialize(xn)
         if self._w8(xn.shape[0], w, EPI_QKV):
-            splits = self.R.w8_splits(xn.shape[0], w.shape[0], w.shape[1], self.concurrency)
+            kind, splits = self._w8_kw(xn.shape[0], w.shape[0], w.shape[1])
             return self.C.linear_qkv(xn, w, b, cache_k, cache_v, meta.token_slots, meta.token_pos,
                                      mcfg.q_size, mcfg.kv_size, mcfg.head_dim, self._rope,
-                                     0, splits, self.counters, wscale=w._lsd_scale)
+                                     kind, splits, self.counters, wscale=w._lsd_scale)
         w = self._dense(w)
         if self.R.blaslt_qkv(xn.shape[0], w.shape[1], getattr(self, "decode", False)) and xn.is_contiguous():
             y = self.C.blaslt_f32(xn, w, self.lane)
@@ -346,8 +355,8 @@ class HipBackend(Backend):
             return self.C.gemv(x, w, b, code, nc, gw, gb, eps, **self._ws(w))
         a = self.materialize(a)
         if self._w8(a.shape[0], w, code):
-            splits = self.R.w8_splits(a.shape[0], w.shape[0], w.shape[1], self.concurrency, 2 if code == 2 else 1)
-            return self.C.linear(a, w, b, code, 0, splits, self.counters, wscale=w._lsd_scale)
+            kind, splits = self._w8_kw(a.shape[0], w.shape[0], w.shape[1], 2 if code == 2 else 1)
+            return self.C.linear(a, w, b, code, kind, splits, self.counters, wscale=w._lsd_scale)
         w = self._dense(w)
         dec = getattr(self, "decode", False)
         if code == 1 and self.R.blaslt_gelu(a.shape[0], dec) and a.is_contiguous():
@@ -368,9 +377,9 @@ class HipBackend(Backend):
             self.C.gemv(a, w, b, EPI_RESID, 0, None, None, 0.0, resid=r.x, **self._ws(w))
             return
         if self._w8(M, w, EPI_RESID):
-            splits = self.R.w8_resid_splits(M, N, K, getattr(self, "concurrency", 1))
+            kind, splits = self._w8_kw(M, N, K, resid=True)
             defer = bool(self.R.defer_resid) and splits > 1
-            slab = self.C.linear_residual(a, w, b, r.x, splits, 0, self.counters, defer, wscale=w._lsd_scale)
+            slab = self.C.linear_residual(a, w, b, r.x, splits, kind, self.counters, defer, wscale=w._lsd_scale)
             if slab is not None:
                 r.pending.append((slab, b))
             return

@@ -26,6 +26,9 @@ import os
 from dataclasses import dataclass
 
 
+D256_MAX_M = 1024  # rows plan_gemm() (csrc/kernels/gemm_plan.h) gives a kind 2 / 3 launch
+
+
 @dataclass(frozen=True)
 class Routing:
     # -- single stream / small batches ------------------------------------
@@ -74,14 +77,23 @@ class Routing:
     sk_rows: int = 64
     defer_resid: int = 1  # residual split-K partials as slabs folded by the next norm
     # FP8 weights (weight_dtype="fp8_e4m3"): decode GEMMs of gemv_max_m < rows <=
-    # w8_max_m stream the E4M3 rows in the FP8-weight kernel (gemm_w8.hip)
+    # w8_max_m stream the E4M3 rows in an FP8-weight kernel (gemm_w8.hip)
     # instead of dequantising into the bf16 scratch first (0: always dequantise).
-    # 128: the largest measured row count at which it beats the dequant route on
-    # all eight GPT-2 XL / Llama-3 8B projections by more than that route's own
-    # spread (1.51-2.24x at 128 rows; at 256 Llama-3 8B gate_up is inside it:
-    # "M": 256 ... "dequant_us": 126.56, "w8_us": 119.73, "dequant_spread_us": 7.84,
-    # "w8_wins": false; profiles/gemm_w8_ab.log)
+    # Rule: the largest measured row count at which that beats the dequant route
+    # on all eight GPT-2 XL / Llama-3 8B projections by more than that route's own
+    # spread.  The split-K kernel set 128 (profiles/gemm_w8_ab.log).  With the
+    # all-rows kernel above w8_sk_max_m, 256 rows qualify (1.16-1.79x, the closest
+    # being Llama-3 8B o_proj: "M": 256 ... "dequant_us": 29.66, "w8_us": 25.69,
+    # "dequant_spread_us": 0.25, "w8_wins": true) and 512 do not (that shape:
+    # "M": 512 ... "dequant_us": 34.39, "w8_us": 34.23, "dequant_spread_us": 0.31,
+    # "w8_wins": false; profiles/gemm_w8_rows_ab.log).  The default is still 128
+    # (README, "FP8 (E4M3) weights", says what holds it there);
+    # LSD_ROUTING=w8_max_m=256 takes the measured value.
     w8_max_m: int = 128
+    # ... of which rows up to w8_sk_max_m run the split-K gemm_w8_kernel and the
+    # rows above it the all-rows gemm_w8_d256_kernel (one workgroup per 256-row
+    # block x column tile; a kind 2 / 3 plan takes at most D256_MAX_M rows)
+    w8_sk_max_m: int = 128
     # LDS ring kernels: grids of <= tiled3_max 128x64 tiles (QKV at 256 rows
     # 25.8 -> 20.4 us; profiles/r1_ab_ring_n64.log), ring depth, tile columns
     # (0 = auto: 32-wide below ring_fill 64-wide workgroups; r2_ring_tn32.log)
@@ -168,14 +180,19 @@ class Routing:
         if 256 < M <= self.d256_rb_max_m:  # several 256-row blocks (auto only)
             if self.d256 != 1 or K < self.d256_min_k or N > self.d256_rb_max_n:
                 return 0
-            return 128 if N % 128 == 0 else 64
+            return self.d256_auto_bn(M, N)
         if not (128 < M <= 256):
             return 0
         if self.d256 == 1:  # auto: long-K GEMMs; 128-wide tiles when they alone fill the chip
             if K < self.d256_min_k:
                 return 0
-            return 128 if N % 128 == 0 and N // 128 >= 128 else 64
+            return self.d256_auto_bn(M, N)
         return 128 if self.d256 == 128 and N % 128 == 0 else 64
+
+    @staticmethod
+    def d256_auto_bn(M: int, N: int) -> int:
+        """128-column tiles when several 256-row blocks share them or when they alone fill the chip."""
+        return 128 if N % 128 == 0 and (M > 256 or N // 128 >= 128) else 64
 
     @staticmethod
     def d256_kind(bn: int) -> int:  # lsd_gemm launch kind of gemm_d256
@@ -196,6 +213,17 @@ class Routing:
         """K splits of a non-residual GEMM on the FP8-weight kernel: sk_splits,
         with at least two of that kernel's 64-k blocks per split."""
         return max(1, min(self.sk_splits(M, N, K, lanes, nw), K // 64 // 2 or 1))
+
+    def w8_rows_kw(self, M: int, N: int, K: int, resid: bool = False, lanes: int = 1):
+        """(launch kind, K splits) of a decode GEMM of w8_sk_max_m < M <= w8_max_m
+        rows on the FP8-weight all-rows kernel (gemm_w8_d256_kernel): gemm_d256's
+        tile and split policy without d256_min_k / d256_rb_max_n (those weigh
+        the bf16 kernel against the ring kernels; here the alternative is a
+        dequant pass); residual projections keep the deferred-slab rule."""
+        bn = self.d256_auto_bn(M, N)
+        if resid:
+            return self.d256_kind(bn), self.w8_resid_splits(M, N, K, lanes)
+        return self.d256_kind(bn), self.d256_splits(N, K, bn, self.d256_target, M)
 
     def w8_resid_splits(self, M: int, N: int, K: int, lanes: int = 1) -> int:
         """... and of a residual projection: the split-K kernel's own rule

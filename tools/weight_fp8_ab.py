@@ -17,7 +17,9 @@ The decode GEMMs of the same shapes at M = 16 .. 512 rows through the backend
 (ops/hip.py), three routes alternating within each of 5 rounds: (a) the bf16
 weight on the kernel ops/routing.py picks for it, (b) the FP8 weight on the
 dequant route (dequant_rows_fp8 into the scratch + that kernel; w8_max_m = 0),
-(c) the FP8 weight on the FP8-weight kernel (csrc/kernels/gemm_w8.hip).  One
+(c) the FP8 weight on the FP8-weight kernels (csrc/kernels/gemm_w8.hip: split-K
+up to Routing.w8_sk_max_m rows, the all-rows kernel above; "w8_kernel" names
+the instance that ran).  --rows M,M,... picks the row counts.  One
 JSON line per case: medians in us, (b)'s spread (max - min of its rounds), the
 weight TB/s of (a) and (c), and whether (c) beats (b) by more than that spread
 -- what sets Routing.w8_max_m."""
@@ -68,7 +70,7 @@ def gemm_rows(a):
         for be in bes.values():
             be._wscratch = torch.empty(1, N * K, dtype=torch.bfloat16, device=dev)
         bias = None if epi == 2 else torch.zeros(N, dtype=torch.bfloat16, device=dev)
-        for M in (16, 32, 64, 128, 256, 512):
+        for M in a.rows:
             x = torch.randn(M, K, device=dev, generator=g).bfloat16()
             r = Residual(torch.zeros(M, N, device=dev))
             turn = [0]
@@ -88,10 +90,12 @@ def gemm_rows(a):
                 for k, (be, ws) in routes.items():
                     t[k].append(timeit(lambda: run(be, ws), iters=max(copies, 32)))
             med = {k: statistics.median(v) for k, v in t.items()}
+            run(*routes["w8"])
+            tag = C.gemm_last_launch()
             spread = max(t["dequant"]) - min(t["dequant"])
             print(json.dumps({"label": a.label, "model": model, "proj": name, "N": N, "K": K, "M": M,
                               "bf16_us": round(med["bf16"], 2), "dequant_us": round(med["dequant"], 2),
-                              "w8_us": round(med["w8"], 2), "dequant_spread_us": round(spread, 2),
+                              "w8_us": round(med["w8"], 2), "w8_kernel": tag, "dequant_spread_us": round(spread, 2),
                               "bf16_TBps": round(2 * N * K / med["bf16"] / 1e6, 3),
                               "w8_TBps": round(N * K / med["w8"] / 1e6, 3),
                               "w8_vs_dequant": round(med["dequant"] / med["w8"], 3),
@@ -106,6 +110,7 @@ def main():
     ap.add_argument("--label", default="this")
     ap.add_argument("--hot", action="store_true")
     ap.add_argument("--gemm", action="store_true")
+    ap.add_argument("--rows", type=lambda v: [int(m) for m in v.split(",")], default=[16, 32, 64, 128, 192, 256, 384, 512])
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     if a.gemm:
