@@ -29,7 +29,8 @@
 #include "gemm_params.h"
 #include "gemm_plan.h"  // Epi, tile constants, GemmTuning / GemmPlan / plan_gemm()
 #include "api.h"
-#include "gemm_epilogue.h"  // hd_split .. store_pass, glds16
+#include "gemm_epilogue.h"  // hd_split .. store_pass, ct_store, glds16
+#include "gemm_combine.h"   // splitk_combine
 
 namespace lsd {
 
@@ -47,10 +48,8 @@ namespace lsd {
 //   * every W fragment of the round is issued straight to VGPRs (W is read
 //     once: no LDS round trip), so a block costs ONE memory round trip;
 //   * one barrier, then MFMAs out of LDS (A) and registers (W).
-// S > 1: each split stores its fp32 partial tile, the last arriver (agent-scope
-// release/acquire ticket, guide §5 "In-launch split-K reduction") sums the S
-// partials and runs the fused epilogue -- so any epilogue (QKV scatter + RoPE,
-// GELU, residual add) works with any split and no extra launch is needed.
+// S > 1: the in-launch combine of gemm_combine.h; the last arriver runs the
+// fused epilogue (QKV scatter + RoPE, GELU, residual add) on the S-way sum.
 // 32-k MFMA steps per round: 16 (512 k) up to M = 64; 8 (256 k) for M <= 128
 // so the A image stays at 64 KiB (2 blocks / CU) while the rows double.
 // Rounds are double-buffered (2 LDS images): 4 steps (128 k) above 64 rows,
@@ -224,66 +223,13 @@ __global__ __launch_bounds__(256) void gemm_sk_kernel(GemmParams p, int* __restr
   // slab[split] and the consumer (the next norm kernel, which reads the rows
   // anyway) sums the S slabs -- no publish, ticket or reducer tail here.
   if (S > 1 && EPI != EPI_SLAB) {
-    // ---- publish this split's partial tile; the last arriver combines.
-    // Slab layout is lane-major ([wave][mt][ns][lane] x f32x4) so every lane
-    // moves 16 contiguous bytes; stores are write-through (sc1) and every
-    // reducer load is sc1, so no agent release/acquire fence is needed (guide
-    // §5 "In-launch split-K reduction", sc1 form; a buffer_wbl2 release per
-    // block cost ~5 us here).
-    constexpr int PER_BLOCK = 4 * MT * NW * 64;  // f32x4 per split tile
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        ws + (long)tile_id * S * PER_BLOCK * 4, (short)0, S * PER_BLOCK * 16, 0x00020000);
-    const int lane_off = ((w * MT * NW) * 64 + lane) * 16;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int ns = 0; ns < NW; ++ns)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[mt][ns]), rs,
-                                               split * PER_BLOCK * 16 + lane_off + (mt * NW + ns) * 1024,
-                                               0, 16);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int t = __hip_atomic_fetch_add(cnt + tile_id, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *s_flag = (t == S - 1);
-      if (t == S - 1) __hip_atomic_store(cnt + tile_id, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    LSD_STAMP(3)
-    if (*s_flag == 0) return;
-    // Sum ALL S partials (own included, from the slab) in fixed split order:
-    // the result must not depend on which split arrived last.
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int ns = 0; ns < NW; ++ns) acc[mt][ns] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // Issue every slab load of a group before summing (no per-load branch:
-    // clamped index x 0/1 mask), so the reduce is one round trip per group
-    // instead of one per split.
+    // base: wave w's block of MT * NW accumulators, 64 lanes each (1024 B apart)
     // group size: <= 128 VGPRs of in-flight partials (the W registers are dead here)
     constexpr int RG = (32 / (MT * NW)) < 4 ? 4 : ((32 / (MT * NW)) > 16 ? 16 : 32 / (MT * NW));
-    for (int s0 = 0; s0 < S; s0 += RG) {
-      f32x4 v[RG][MT][NW];
-#pragma unroll
-      for (int u = 0; u < RG; ++u) {
-        const int s2 = min(s0 + u, S - 1);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int ns = 0; ns < NW; ++ns)
-            v[u][mt][ns] = __builtin_bit_cast(
-                f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                           rs, s2 * PER_BLOCK * 16 + lane_off + (mt * NW + ns) * 1024, 0, 16));
-      }
-#pragma unroll
-      for (int u = 0; u < RG; ++u) {
-        const float msk = (s0 + u < S) ? 1.f : 0.f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int ns = 0; ns < NW; ++ns) acc[mt][ns] += v[u][mt][ns] * msk;
-      }
-    }
+    const bool last = splitk_combine<256, 1024, RG>(acc, ws, cnt, tile_id, split, S,
+                                                    ((w * MT * NW) * 64 + lane) * 16, s_flag);
+    LSD_STAMP(3)
+    if (!last) return;
   }
   LSD_STAMP(4)
 
@@ -295,24 +241,7 @@ __global__ __launch_bounds__(256) void gemm_sk_kernel(GemmParams p, int* __restr
   constexpr int CLD = BNB + 4;  // row stride: 4 rows x 16 columns hit 64 distinct banks
   constexpr bool LDS_EPI = EPI != EPI_SILU_MUL && ROWS * CLD * 4 <= 2 * NCHUNK * CHUNK_BYTES;
   if constexpr (LDS_EPI) {
-    float* ct = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int ns = 0; ns < NW; ++ns)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          ct[(mt * 16 + 4 * g + q) * CLD + w * 16 * NW + ns * 16 + r] = acc[mt][ns][q];
-    __syncthreads();
-    const int n0 = tile * BNB;
-    store_pass<EPI, (ROWS * (BNB / 8) + 255) / 256, 256>(
-        p, ROWS * (BNB / 8), split, [&](int c, int& m, int& n, const float*& src) {
-          const int row = c / (BNB / 8), ch = c % (BNB / 8);
-          m = rb0 + row;
-          n = n0 + ch * 8;
-          src = ct + row * CLD + ch * 8;
-          return m < p.M && n < p.N;
-        });
+    sk_tile_store<EPI, ROWS, BNB, 256>(p, acc, smem, rb0, tile * BNB, split);
   } else {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
@@ -388,47 +317,6 @@ __device__ __forceinline__ void stage_tile(char* lds_tile, const bf16* src, long
 __device__ __forceinline__ bf16x8 lds_frag(const char* tile, int row, int chunk) {
   const int pch = chunk ^ ((row >> 1) & 7);
   return *reinterpret_cast<const bf16x8*>(tile + row * 128 + pch * 16);
-}
-
-// Store loop of an fp32 [TM][TN + 4] C tile in LDS: NT threads, one 8-column
-// row chunk each per pass, 16-byte global stores (epilogue8).
-template <int EPI, int TN, int TM, int NT>
-__device__ __forceinline__ void ct_store(const GemmParams& p, const float* ct, int m0, int n0, int split) {
-  constexpr int CLD = TN + 4;
-  constexpr int CPR = TN / 8;  // 8-column chunks per row
-  if constexpr (EPI != EPI_SILU_MUL) {
-    store_pass<EPI, (TM * CPR + NT - 1) / NT, NT>(p, TM * CPR, split, [&](int c, int& m, int& n, const float*& src) {
-      const int row = c / CPR;
-      m = m0 + row;
-      n = n0 + (c % CPR) * 8;
-      src = ct + row * CLD + (c % CPR) * 8;
-      return m < p.M && n < p.N;
-    });
-    return;
-  }
-  for (int c = threadIdx.x; c < TM * CPR; c += NT) {
-    const int row = c / CPR, n = n0 + (c % CPR) * 8, m = m0 + row;
-    if (m >= p.M || n >= p.N) continue;
-    const float* src = ct + row * CLD + (c % CPR) * 8;
-    const f32x4 lo = *reinterpret_cast<const f32x4*>(src);
-    const f32x4 hi = *reinterpret_cast<const f32x4*>(src + 4);
-    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    if constexpr (EPI == EPI_SILU_MUL) {
-      // interleaved [gate16 | up16] 32-column blocks: gate chunks pair with
-      // the up chunk 16 columns right, in the same tile
-      if ((c & 3) >= 2) continue;
-      const float* up = src + 16;
-      const f32x4 ulo = *reinterpret_cast<const f32x4*>(up);
-      const f32x4 uhi = *reinterpret_cast<const f32x4*>(up + 4);
-      const float u[8] = {ulo[0], ulo[1], ulo[2], ulo[3], uhi[0], uhi[1], uhi[2], uhi[3]};
-      bf16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = f2bf(silu(v[e]) * u[e]);
-      st8(reinterpret_cast<bf16*>(p.out) + (long)m * p.ldo + (n >> 5) * 16 + (n & 15), o);
-    } else {
-      epilogue8<EPI>(p, m, n, v, split);
-    }
-  }
 }
 
 // Epilogue through LDS (free after the main loop's last barrier): the MFMA C
@@ -675,13 +563,8 @@ __device__ __forceinline__ void stage_rows_packed(char* lds_tile, const bf16* sr
 //
 // K splits (p.splits > 1): EPI_SLAB writes its partial slab (residual
 // projections; the next norm folds the slabs).  Any other epilogue (QKV /
-// MLP-up at 129-256 rows, VAR 2 only): every split publishes its fp32
-// partial tile write-through (sc1 stores) in a lane-major layout (each
-// thread's 16-byte accumulators contiguous across the workgroup: whole-line
-// stores and loads), takes an agent-scope ticket, and the last-arriving split
-// reloads the other partials (sc1 loads) and sums all S in split order
-// (deterministic) before the fused epilogue (guide §5 "In-launch split-K
-// reduction", sc1 form: no release / acquire fences).
+// MLP-up at 129-256 rows, VAR 2 only) goes through the in-launch combine of
+// gemm_combine.h: the last-arriving split sums all S partials in split order.
 // Measured and removed (round 5): a W-line L2 prefetch, one extra 4-byte-per-lane
 // LDS-DMA touch per k-step of the rows 2-6 k-steps ahead -- 7-16 % slower on every
 // GPT-2 XL shape, bench 50.1-50.5k -> 46.5-47.3k (profiles/r5_rejected_ring8_prefetch.log).
@@ -772,61 +655,11 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmParams p, int tiles
   if constexpr (VAR == 2 && EPI != EPI_SLAB) {
     const int S = p.splits;
     if (S > 1) {
-      constexpr int PER = MI * JT * 512;  // f32x4 per split tile
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-          ws + (long)t * S * PER * 4, (short)0, S * PER * 16, 0x00020000);
-      const int toff = threadIdx.x * 16;
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < JT; ++j)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rs,
-                                                 split * PER * 16 + (i * JT + j) * 8192 + toff, 0, 16);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      int* s_flag = reinterpret_cast<int*>(smem);
-      if (threadIdx.x == 0) {
-        const int tk = __hip_atomic_fetch_add(cnt + t, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *s_flag = (tk == S - 1);
-        if (tk == S - 1) __hip_atomic_store(cnt + t, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      __syncthreads();
-      if (*s_flag == 0) return;
+      // base: thread-major, 512 threads x 16 B (8192 B) per accumulator; the
+      // flag word lies under the C tile
+      if (!splitk_combine<512, 8192, 4>(acc, ws, cnt, t, split, S, threadIdx.x * 16, reinterpret_cast<int*>(smem)))
+        return;
       __syncthreads();  // every wave has read the flag before the C tile overwrites it
-      // every partial of a group in flight before the adds (its own one too:
-      // no per-load register-or-load select); clamped split index x 0/1 mask,
-      // no per-load branch (guide §5 trap (c))
-      constexpr int RG = 4;
-      f32x4 sum[MI][JT];
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < JT; ++j) sum[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int s0 = 0; s0 < S; s0 += RG) {
-        f32x4 v[RG][MI][JT];
-#pragma unroll
-        for (int u = 0; u < RG; ++u) {
-          const int s2 = min(s0 + u, S - 1);
-#pragma unroll
-          for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < JT; ++j)
-              v[u][i][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                  rs, s2 * PER * 16 + (i * JT + j) * 8192 + toff, 0, 16));
-        }
-#pragma unroll
-        for (int u = 0; u < RG; ++u) {
-          const float msk = (s0 + u < S) ? 1.f : 0.f;
-#pragma unroll
-          for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < JT; ++j) sum[i][j] += v[u][i][j] * msk;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < JT; ++j) acc[i][j] = sum[i][j];
     }
   }
   float* ct = reinterpret_cast<float*>(smem);
@@ -1373,11 +1206,9 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(GemmParams p, int tiles_m,
 //     ring, counted vmcnt + one raw s_barrier per step (as gemm_ring_kernel);
 //   * S > 1 K splits: EPI_SLAB writes its partial slab (the residual
 //     projections: the next norm folds the S slabs, bindings linear_residual);
-//     every other epilogue publishes its fp32 partial tile write-through (sc1
-//     stores, sc1 loads: guide §5 "In-launch split-K reduction", sc1 form) and
-//     the last-arriving split sums the S partials in split order
-//     (deterministic) and runs the fused epilogue.  A tile's splits have
-//     consecutive remapped ids, so they share an XCD (speed only).
+//     every other epilogue goes through the in-launch combine (gemm_combine.h)
+//     and the last-arriving split runs it.  A tile's splits have consecutive
+//     remapped ids, so they share an XCD (speed only).
 template <int ROWS, bool BL = kStageBL>
 __device__ __forceinline__ void stage8(char* lds_tile, const bf16* src, long ld, int row0, int row_max,
                                        int k0) {
@@ -1466,65 +1297,16 @@ __global__ __launch_bounds__(512) void gemm_d256_kernel(GemmParams p, int* __res
   LSD_STAMP(1)
 
   if (S > 1 && EPI != EPI_SLAB) {
-    // ---- publish this split's partial tile (write-through), last arriver
-    // sums all S.  Lane-major slab: thread t's (i, j) accumulator at
-    // ((i * NJ + j) * 512 + t) * 16 B, so every access is 16 contiguous bytes.
-    constexpr int PER_BLOCK = 2 * NJ * 512;  // f32x4 per split tile
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        ws + (long)tile * S * PER_BLOCK * 4, (short)0, S * PER_BLOCK * 16, 0x00020000);
-    const int toff = threadIdx.x * 16;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rs,
-                                               split * PER_BLOCK * 16 + (i * NJ + j) * 8192 + toff, 0, 16);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int t = __hip_atomic_fetch_add(cnt + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *s_flag = (t == S - 1);
-      if (t == S - 1) __hip_atomic_store(cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (*s_flag == 0) return;
+    // base: thread-major, 512 threads x 16 B (8192 B) per accumulator;
+    // splits per group: 32 f32x4 (128 VGPRs) in flight
+    if (!splitk_combine<512, 8192, 16 / NJ>(acc, ws, cnt, tile, split, S, threadIdx.x * 16, s_flag)) return;
     LSD_STAMP(2)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // every slab load of a group in flight before the adds (one round trip per
-    // group); clamped index x 0/1 mask, no per-load branch (guide §5 trap (c))
-    constexpr int RG = 16 / NJ;  // splits per group: 32 f32x4 (128 VGPRs) in flight
-    for (int s0 = 0; s0 < S; s0 += RG) {
-      f32x4 v[RG][2][NJ];
-#pragma unroll
-      for (int u = 0; u < RG; ++u) {
-        const int s2 = min(s0 + u, S - 1);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            v[u][i][j] = __builtin_bit_cast(
-                f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, s2 * PER_BLOCK * 16 + (i * NJ + j) * 8192 + toff,
-                                                             0, 16));
-      }
-#pragma unroll
-      for (int u = 0; u < RG; ++u) {
-        const float msk = (s0 + u < S) ? 1.f : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) acc[i][j] += v[u][i][j] * msk;
-      }
-    }
   }
 
   // ---- epilogue through LDS: fp32 [256][BN + 4] C tile, then 16-byte
   // row-contiguous stores (epilogue8); the ring is idle (every glds waited,
   // every wave past the last barrier below)
   constexpr int CLD = BN + 4;
-  constexpr int CPR = BN / 8;
   __syncthreads();
   float* ct = reinterpret_cast<float*>(smem);
 #pragma unroll
@@ -1534,40 +1316,7 @@ __global__ __launch_bounds__(512) void gemm_d256_kernel(GemmParams p, int* __res
 #pragma unroll
       for (int q = 0; q < 4; ++q) ct[(w * 32 + i * 16 + 4 * g + q) * CLD + j * 16 + r] = acc[i][j][q];
   __syncthreads();
-  if constexpr (EPI != EPI_SILU_MUL) {
-    store_pass<EPI, (256 * CPR + 511) / 512, 512>(p, 256 * CPR, split, [&](int c, int& m, int& n, const float*& src) {
-      const int row = c / CPR, ch = c % CPR;
-      m = m0 + row;
-      n = n0 + ch * 8;
-      src = ct + row * CLD + ch * 8;
-      return m < p.M && n < p.N;
-    });
-    LSD_STAMP(3)
-    return;
-  }
-  for (int c = threadIdx.x; c < 256 * CPR; c += 512) {
-    const int row = c / CPR, ch = c % CPR, m = m0 + row, n = n0 + ch * 8;
-    if (m >= p.M || n >= p.N) continue;
-    const float* src = ct + row * CLD + ch * 8;
-    const f32x4 lo = *reinterpret_cast<const f32x4*>(src);
-    const f32x4 hi = *reinterpret_cast<const f32x4*>(src + 4);
-    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    if constexpr (EPI == EPI_SILU_MUL) {
-      // interleaved [gate16 | up16] 32-column blocks: a gate chunk pairs with
-      // the up chunk 16 columns right (same tile: BN % 32 == 0)
-      if ((ch & 3) >= 2) continue;
-      const float* up = src + 16;
-      const f32x4 ulo = *reinterpret_cast<const f32x4*>(up);
-      const f32x4 uhi = *reinterpret_cast<const f32x4*>(up + 4);
-      const float u[8] = {ulo[0], ulo[1], ulo[2], ulo[3], uhi[0], uhi[1], uhi[2], uhi[3]};
-      bf16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = f2bf(silu(v[e]) * u[e]);
-      st8(reinterpret_cast<bf16*>(p.out) + (long)m * p.ldo + (n >> 5) * 16 + (n & 15), o);
-    } else {
-      epilogue8<EPI>(p, m, n, v, split);
-    }
-  }
+  ct_store<EPI, BN, 256, 512>(p, ct, m0, n0, split);
   LSD_STAMP(3)
 }
 
@@ -1714,15 +1463,6 @@ extern "C" hipError_t lsd_gemm(const GemmParams* p, const GemmPlan* plan, int* c
   const GemmPlan& pl = *plan;
   if (!pl.valid || pl.M != p->M || pl.N != p->N || pl.K != p->K || pl.splits != p->splits) return hipErrorInvalidValue;
   if (pl.combine_tiles > 0 && (cnt == nullptr || ws == nullptr)) return hipErrorInvalidValue;
-  switch (pl.epi) {
-    case EPI_BF16: return launch_plan<EPI_BF16>(*p, pl, cnt, ws, st);
-    case EPI_GELU: return launch_plan<EPI_GELU>(*p, pl, cnt, ws, st);
-    case EPI_SILU_MUL: return launch_plan<EPI_SILU_MUL>(*p, pl, cnt, ws, st);
-    case EPI_F32: return launch_plan<EPI_F32>(*p, pl, cnt, ws, st);
-    case EPI_RESID: return launch_plan<EPI_RESID>(*p, pl, cnt, ws, st);
-    case EPI_QKV: return launch_plan<EPI_QKV>(*p, pl, cnt, ws, st);
-    case EPI_SLAB: return launch_plan<EPI_SLAB>(*p, pl, cnt, ws, st);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_epi(pl.epi, [&](auto e) { return launch_plan<decltype(e)::value>(*p, pl, cnt, ws, st); });
 }
 

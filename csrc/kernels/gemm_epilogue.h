@@ -298,6 +298,68 @@ __device__ __forceinline__ void store_pass(const GemmParams& p, int nchunks, int
   }
 }
 
+// lambdas that must inline into a kernel built with LSD_NO_PK_F32 (common.h)
+#define LSD_INL __attribute__((always_inline))
+
+// Store loop of an fp32 [TM][TN + 4] C tile in LDS: NT threads, one 8-column
+// row chunk each per pass, 16-byte global stores (epilogue8).  SiLU*up:
+// interleaved [gate16 | up16] 32-column blocks, a gate chunk pairs with the up
+// chunk 16 columns right (same tile: TN % 32 == 0).
+template <int EPI, int TN, int TM, int NT>
+__device__ __forceinline__ void ct_store(const GemmParams& p, const float* ct, int m0, int n0, int split) {
+  constexpr int CLD = TN + 4;
+  constexpr int CPR = TN / 8;  // 8-column chunks per row
+  if constexpr (EPI != EPI_SILU_MUL) {
+    store_pass<EPI, (TM * CPR + NT - 1) / NT, NT>(
+        p, TM * CPR, split, [&](int c, int& m, int& n, const float*& src) LSD_INL {
+          const int row = c / CPR, ch = c % CPR;
+          m = m0 + row;
+          n = n0 + ch * 8;
+          src = ct + row * CLD + ch * 8;
+          return m < p.M && n < p.N;
+        });
+  } else {
+    for (int c = threadIdx.x; c < TM * CPR; c += NT) {
+      const int row = c / CPR, n = n0 + (c % CPR) * 8, m = m0 + row;
+      if (m >= p.M || n >= p.N) continue;
+      const float* src = ct + row * CLD + (c % CPR) * 8;
+      const f32x4 lo = *reinterpret_cast<const f32x4*>(src);
+      const f32x4 hi = *reinterpret_cast<const f32x4*>(src + 4);
+      float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      if ((c & 3) >= 2) continue;  // up chunks are read by their gate chunk (CPR % 4 == 0)
+      const float* up = src + 16;
+      const f32x4 ulo = *reinterpret_cast<const f32x4*>(up);
+      const f32x4 uhi = *reinterpret_cast<const f32x4*>(up + 4);
+      const float u[8] = {ulo[0], ulo[1], ulo[2], ulo[3], uhi[0], uhi[1], uhi[2], uhi[3]};
+      bf16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = f2bf(silu(v[e]) * u[e]);
+      st8(reinterpret_cast<bf16*>(p.out) + (long)m * p.ldo + (n >> 5) * 16 + (n & 15), o);
+    }
+  }
+}
+
+// C tile of the split-K pair (gemm_sk_kernel, gemm_w8_kernel): NT / 64 waves
+// side by side, wave w owns columns [w, w + 1) * BNB / (NT / 64) of every row.
+// The MFMA layout gives a lane 4 rows x 1 column; transposed through the fp32
+// [ROWS][BNB + 4] tile (4 rows x 16 columns hit 64 distinct banks), every
+// global store is a row-contiguous 16-byte vector.  The caller's LDS is idle.
+template <int EPI, int ROWS, int BNB, int NT>
+__device__ __forceinline__ void sk_tile_store(const GemmParams& p, const f32x4 (&acc)[ROWS / 16][BNB / (NT / 4)],
+                                              char* smem, int m0, int n0, int split) {
+  constexpr int CLD = BNB + 4, MT = ROWS / 16, NW = BNB / (NT / 4);
+  const int lane = lane_id(), w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+  float* ct = reinterpret_cast<float*>(smem);
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int ns = 0; ns < NW; ++ns)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ct[(mt * 16 + 4 * g + q) * CLD + w * 16 * NW + ns * 16 + r] = acc[mt][ns][q];
+  block_sync();
+  ct_store<EPI, BNB, ROWS, NT>(p, ct, m0, n0, split);
+}
+
 // s_waitcnt simm16 (gfx9 layout) for lgkmcnt(0) alone
 constexpr int LGKM0_SK = 0xC07F;
 

@@ -9,6 +9,7 @@
 //
 // Plain C++17, no HIP header: tests/test_gemm_plan.py compiles it alone.
 #pragma once
+#include <type_traits>
 
 namespace lsd {
 
@@ -21,6 +22,20 @@ enum Epi : int {
   EPI_SLAB = 5,      // slab[split][M][N] = acc
   EPI_QKV = 6,       // q -> out bf16, k/v -> KV cache (+ RoPE)
 };
+
+#ifdef __HIPCC__  // the launchers' side; the plan itself needs no HIP header
+// f(std::integral_constant<int, epi>{}): the runtime epilogue as a template argument
+template <class F>
+hipError_t dispatch_epi(int epi, F f) {
+  switch (epi) {
+#define LSD_EPI_CASE(E) case E: return f(std::integral_constant<int, E>{});
+    LSD_EPI_CASE(EPI_BF16) LSD_EPI_CASE(EPI_GELU) LSD_EPI_CASE(EPI_SILU_MUL) LSD_EPI_CASE(EPI_F32)
+    LSD_EPI_CASE(EPI_RESID) LSD_EPI_CASE(EPI_QKV) LSD_EPI_CASE(EPI_SLAB)
+#undef LSD_EPI_CASE
+  }
+  return hipErrorInvalidValue;
+}
+#endif
 
 // Block tiles of the 128x128 (tiled / ring) and the 256x256 (big / p8) kernels.
 constexpr int TBM = 128, TBN = 128;

@@ -66,6 +66,7 @@
 #include "gemm_plan.h"
 #include "api.h"
 #include "gemm_epilogue.h"
+#include "gemm_combine.h"
 
 namespace lsd {
 
@@ -88,8 +89,6 @@ __device__ __forceinline__ bf16x8 w8_frag(u32x4 w) {
   const bf16x4 hi = __builtin_shufflevector(p2, p3, 0, 1, 2, 3);
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
-
-#define LSD_INL __attribute__((always_inline))
 
 // 64-column tiles hold 2 workgroups per CU (2 waves per SIMD: at most 256 registers)
 template <int MT, int NW, int EPI>
@@ -238,57 +237,11 @@ void gemm_w8_kernel(GemmParams p, const float* __restrict__ wscale,
   }
 
   if (S > 1 && EPI != EPI_SLAB) {
-    // publish this split's RAW partial tile, lane-major; the last arriver sums
-    // all S of them in fixed split order (gemm_sk_kernel's combine: sc1 stores
-    // and loads, agent-scope ticket)
-    constexpr int PER_BLOCK = 4 * MT * NW * 64;  // f32x4 per split tile
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        ws + (long)tile_id * S * PER_BLOCK * 4, (short)0, S * PER_BLOCK * 16, 0x00020000);
-    const int lane_off = ((w * MT * NW) * 64 + lane) * 16;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int ns = 0; ns < NW; ++ns)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[mt][ns]), rs,
-                                               split * PER_BLOCK * 16 + lane_off + (mt * NW + ns) * 1024, 0, 16);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    block_sync();
-    if (threadIdx.x == 0) {
-      const int t = __hip_atomic_fetch_add(cnt + tile_id, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *s_flag = (t == S - 1);
-      if (t == S - 1) __hip_atomic_store(cnt + tile_id, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    block_sync();
-    if (*s_flag == 0) return;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int ns = 0; ns < NW; ++ns) acc[mt][ns] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // every slab load of a group is issued before the sums (clamped index x
-    // 0/1 mask, no per-load branch); <= 128 VGPRs of partials in flight
+    // RAW partials are combined (gemm_combine.h); base: wave w's block of
+    // MT * NW accumulators, 64 lanes each (1024 B apart); <= 128 VGPRs in flight
     constexpr int RG = (32 / (MT * NW)) < 4 ? 4 : ((32 / (MT * NW)) > 16 ? 16 : 32 / (MT * NW));
-    for (int s0 = 0; s0 < S; s0 += RG) {
-      f32x4 v[RG][MT][NW];
-#pragma unroll
-      for (int u = 0; u < RG; ++u) {
-        const int s2 = min(s0 + u, S - 1);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int ns = 0; ns < NW; ++ns)
-            v[u][mt][ns] = __builtin_bit_cast(
-                f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                           rs, s2 * PER_BLOCK * 16 + lane_off + (mt * NW + ns) * 1024, 0, 16));
-      }
-#pragma unroll
-      for (int u = 0; u < RG; ++u) {
-        const float msk = (s0 + u < S) ? 1.f : 0.f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int ns = 0; ns < NW; ++ns) acc[mt][ns] += v[u][mt][ns] * msk;
-      }
-    }
+    if (!splitk_combine<256, 1024, RG>(acc, ws, cnt, tile_id, split, S, ((w * MT * NW) * 64 + lane) * 16, s_flag))
+      return;
   }
 
   // The row scale, once: the whole sum (S = 1, or the last arriver's), or this
@@ -305,23 +258,7 @@ void gemm_w8_kernel(GemmParams p, const float* __restrict__ wscale,
   if constexpr (EPI != EPI_SILU_MUL) {
     // always: epilogue4's 16-column sub-tiles would overrun a last tile of 8 live columns
     static_assert(ROWS * CLD * 4 <= 2 * BUF_BYTES, "C tile fits the A buffers");
-    float* ct = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int ns = 0; ns < NW; ++ns)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ct[(mt * 16 + 4 * g + q) * CLD + w * 16 * NW + ns * 16 + r] = acc[mt][ns][q];
-    block_sync();
-    const int n0 = tile * BNB;
-    store_pass<EPI, (ROWS * (BNB / 8) + 255) / 256, 256>(
-        p, ROWS * (BNB / 8), split, [&](int c, int& m, int& n, const float*& src) LSD_INL {
-          const int row = c / (BNB / 8), ch = c % (BNB / 8);
-          m = rb0 + row;
-          n = n0 + ch * 8;
-          src = ct + row * CLD + ch * 8;
-          return m < p.M && n < p.N;
-        });
+    sk_tile_store<EPI, ROWS, BNB, 256>(p, acc, smem, rb0, tile * BNB, split);
   } else {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -502,56 +439,9 @@ void gemm_w8_d256_kernel(GemmParams p, const float* __restrict__ wscale, int* __
   }
 
   if (S > 1 && EPI != EPI_SLAB) {
-    // publish this split's RAW partial tile, thread t's (i, j) accumulator at
-    // ((i * NJ + j) * 512 + t) * 16 B; the last arriver sums all S in split order
-    constexpr int PER_BLOCK = 4 * NJ * 512;  // f32x4 per split tile = 256 x BN floats
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        ws + (long)tile * S * PER_BLOCK * 4, (short)0, S * PER_BLOCK * 16, 0x00020000);
-    const int toff = threadIdx.x * 16;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rs,
-                                               split * PER_BLOCK * 16 + (i * NJ + j) * 8192 + toff, 0, 16);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    block_sync();
-    if (threadIdx.x == 0) {
-      const int t = __hip_atomic_fetch_add(cnt + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *s_flag = (t == S - 1);
-      if (t == S - 1) __hip_atomic_store(cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    block_sync();
-    if (*s_flag == 0) return;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // every slab load of a group in flight before the adds; clamped index x
-    // 0/1 mask, no per-load branch; 32 f32x4 (128 VGPRs) of partials in flight
-    constexpr int RG = 8 / NJ;
-    for (int s0 = 0; s0 < S; s0 += RG) {
-      f32x4 v[RG][4][NJ];
-#pragma unroll
-      for (int u = 0; u < RG; ++u) {
-        const int s2 = min(s0 + u, S - 1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            v[u][i][j] = __builtin_bit_cast(
-                f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, s2 * PER_BLOCK * 16 + (i * NJ + j) * 8192 + toff,
-                                                             0, 16));
-      }
-#pragma unroll
-      for (int u = 0; u < RG; ++u) {
-        const float msk = (s0 + u < S) ? 1.f : 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) acc[i][j] += v[u][i][j] * msk;
-      }
-    }
+    // RAW partials are combined (gemm_combine.h); base: thread-major, 512
+    // threads x 16 B (8192 B) per accumulator; 32 f32x4 (128 VGPRs) in flight
+    if (!splitk_combine<512, 8192, 8 / NJ>(acc, ws, cnt, tile, split, S, threadIdx.x * 16, s_flag)) return;
   }
 
   // The row scale, once: the whole sum (S = 1, or the last arriver's), or this
@@ -564,7 +454,6 @@ void gemm_w8_d256_kernel(GemmParams p, const float* __restrict__ wscale, int* __
   // Epilogue through the fp32 [256][BN + 4] C tile over the rings (every DMA
   // waited for; the barrier keeps it off a slot another wave still reads).
   constexpr int CLD = BN + 4;
-  constexpr int CPR = BN / 8;
   block_sync();
   float* ct = reinterpret_cast<float*>(smem);
 #pragma unroll
@@ -575,33 +464,7 @@ void gemm_w8_d256_kernel(GemmParams p, const float* __restrict__ wscale, int* __
       for (int q = 0; q < 4; ++q)
         ct[(wr * 64 + i * 16 + 4 * g + q) * CLD + wc * (BN / 2) + j * 16 + r] = acc[i][j][q];
   block_sync();
-  if constexpr (EPI != EPI_SILU_MUL) {
-    store_pass<EPI, (256 * CPR + 511) / 512, 512>(
-        p, 256 * CPR, split, [&](int c, int& m, int& n, const float*& src) LSD_INL {
-          const int row = c / CPR, ch = c % CPR;
-          m = m0 + row;
-          n = n0 + ch * 8;
-          src = ct + row * CLD + ch * 8;
-          return m < p.M && n < p.N;
-        });
-  } else {
-    // interleaved [gate16 | up16] 32-column blocks: a gate chunk pairs with
-    // the up chunk 16 columns right (same tile: BN % 32 == 0)
-    for (int c = threadIdx.x; c < 256 * CPR; c += 512) {
-      const int row = c / CPR, ch = c % CPR, m = m0 + row, n = n0 + ch * 8;
-      if (m >= p.M || n >= p.N || (ch & 3) >= 2) continue;
-      const float* src = ct + row * CLD + ch * 8;
-      bf16x8 o;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const f32x4 gt = *reinterpret_cast<const f32x4*>(src + 4 * h);
-        const f32x4 up = *reinterpret_cast<const f32x4*>(src + 16 + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[4 * h + e] = f2bf(silu(gt[e]) * up[e]);
-      }
-      st8(reinterpret_cast<bf16*>(p.out) + (long)m * p.ldo + (n >> 5) * 16 + (n & 15), o);
-    }
-  }
+  ct_store<EPI, BN, 256, 512>(p, ct, m0, n0, split);
 }
 
 template <int EPI>
@@ -671,27 +534,9 @@ extern "C" hipError_t lsd_gemm_w8(const GemmParams* p, const float* wscale, cons
   if (!lsd_gemm_w8_ok(p->M, p->N, p->K, pl.epi) || p->splits > p->K / 64) return hipErrorInvalidValue;
   if (wscale == nullptr || p->ldw % 16 != 0 || p->ldw < p->K) return hipErrorInvalidValue;
   if (pl.combine_tiles > 0 && (cnt == nullptr || ws == nullptr)) return hipErrorInvalidValue;
-  if (rows) {
-    if (pl.combine_tiles > 0 && pl.tile_floats != 256L * pl.tn) return hipErrorInvalidValue;
-    switch (pl.epi) {
-      case EPI_BF16: return launch_w8_d256<EPI_BF16>(*p, wscale, pl, cnt, ws, st);
-      case EPI_GELU: return launch_w8_d256<EPI_GELU>(*p, wscale, pl, cnt, ws, st);
-      case EPI_SILU_MUL: return launch_w8_d256<EPI_SILU_MUL>(*p, wscale, pl, cnt, ws, st);
-      case EPI_F32: return launch_w8_d256<EPI_F32>(*p, wscale, pl, cnt, ws, st);
-      case EPI_RESID: return launch_w8_d256<EPI_RESID>(*p, wscale, pl, cnt, ws, st);
-      case EPI_QKV: return launch_w8_d256<EPI_QKV>(*p, wscale, pl, cnt, ws, st);
-      case EPI_SLAB: return launch_w8_d256<EPI_SLAB>(*p, wscale, pl, cnt, ws, st);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  switch (pl.epi) {
-    case EPI_BF16: return launch_w8_epi<EPI_BF16>(*p, wscale, pl, cnt, ws, st);
-    case EPI_GELU: return launch_w8_epi<EPI_GELU>(*p, wscale, pl, cnt, ws, st);
-    case EPI_SILU_MUL: return launch_w8_epi<EPI_SILU_MUL>(*p, wscale, pl, cnt, ws, st);
-    case EPI_F32: return launch_w8_epi<EPI_F32>(*p, wscale, pl, cnt, ws, st);
-    case EPI_RESID: return launch_w8_epi<EPI_RESID>(*p, wscale, pl, cnt, ws, st);
-    case EPI_QKV: return launch_w8_epi<EPI_QKV>(*p, wscale, pl, cnt, ws, st);
-    case EPI_SLAB: return launch_w8_epi<EPI_SLAB>(*p, wscale, pl, cnt, ws, st);
-    default: return hipErrorInvalidValue;
-  }
+  if (rows && pl.combine_tiles > 0 && pl.tile_floats != 256L * pl.tn) return hipErrorInvalidValue;
+  return dispatch_epi(pl.epi, [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    return rows ? launch_w8_d256<EPI>(*p, wscale, pl, cnt, ws, st) : launch_w8_epi<EPI>(*p, wscale, pl, cnt, ws, st);
+  });
 }

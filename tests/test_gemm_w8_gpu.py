@@ -55,6 +55,46 @@ def test_gemm_w8_exact(C, CNT, M, K):
     assert int(CNT.abs().sum()) == 0  # every ticket counter re-armed
 
 
+def exact_case(C, M, N, K, seed, e_lo, e_hi):
+    """test_gemm_w8_exact's operands with row scales 2^e, e in [e_lo, e_hi]: (a, q, scale, bias, float64 a @ w^T,
+    float64 bias).  The quantised bytes are the integers 64 wi, so every raw partial sum is an integer below
+    3 * 448 * K (< 2^24 up to K = 3900) and the row scale 2^e / 64 multiplies it without error."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    wi = torch.randint(-7, 8, (N, K), device=DEV, generator=g).double()
+    wi[:, K - 1] = 7
+    w = wi * (2.0 ** torch.randint(e_lo, e_hi + 1, (N, 1), device=DEV, generator=g).double())
+    a = torch.randint(-3, 4, (M, K), device=DEV, generator=g).double()
+    bias = torch.randint(-9, 10, (N,), device=DEV, generator=g).double()
+    q, s = C.quantize_rows_fp8(w.bfloat16())
+    assert torch.equal(q.float().double() * s.double()[:, None], w)
+    return a.bfloat16(), q, s, bias.bfloat16(), a @ w.T, bias
+
+
+def stale_workspace_rounds(C, CNT, kind, big, small):
+    """test_split_k_ignores_stale_workspace (test_gemm_exact_gpu.py) on the FP8-weight kernels: a larger problem of
+    larger values first, then a smaller shape of smaller values on the same ticket counters.  The workspace comes
+    from torch.empty (the allocator hands the freed block back), so a partial that is read before it is written, or
+    a ticket left over, changes the second, exact result."""
+    (M1, N1, K1, S1), (M2, N2, K2, S2) = big, small
+    a1, q1, s1, _, y1, _ = exact_case(C, M1, N1, K1, 1, 2, 4)
+    a2, q2, s2, b2, y2, bias2 = exact_case(C, M2, N2, K2, 2, -2, 2)
+    for _ in range(2):
+        out = C.linear_f32(a1, q1, kind, S1, CNT, wscale=s1)
+        assert torch.equal(out.double(), y1)
+        del out
+        out = C.linear(a2, q2, b2, 0, kind, S2, CNT, wscale=s2)
+        assert torch.equal(out, (y2 + bias2).float().bfloat16())
+        out = C.linear_f32(a2, q2, kind, S2, CNT, wscale=s2)
+        assert torch.equal(out.double(), y2)
+        del out
+    assert int(CNT.abs().sum()) == 0
+
+
+def test_gemm_w8_split_k_ignores_stale_workspace(C, CNT):
+    stale_workspace_rounds(C, CNT, 0, (64, 256, 1600, 7), (33, 192, 576, 3))
+    assert C.gemm_last_launch().startswith("w8<")
+
+
 @pytest.mark.parametrize("splits", [1, 2])
 @pytest.mark.parametrize("K", [768, 1600])
 @pytest.mark.parametrize("M", [16, 80])

@@ -9,7 +9,7 @@ from llm_sharding_demo_amd.ops.routing import Routing
 from llm_sharding_demo_amd.runtime.engine import Engine
 from llm_sharding_demo_amd.utils.golden import compare_with_golden
 
-from .test_gemm_w8_gpu import _backend, _qkv_case
+from .test_gemm_w8_gpu import _backend, _qkv_case, stale_workspace_rounds
 from .test_kernels_gpu import C, CNT, DEV, _fp32_slabs, bf, close  # noqa: F401  (fixtures)
 from .test_numerics_gpu import BOUNDS, _prompts
 from .test_weight_fp8_gpu import FP8, quant
@@ -59,6 +59,13 @@ def test_gemm_w8_rows_exact(C, CNT, M, K, slots):
                 assert torch.equal(x.double(), want)
     C.gemm_set_d256_slots(3)
     assert int(CNT.abs().sum()) == 0  # every ticket counter re-armed
+
+
+@pytest.mark.parametrize("kind", [2, 3])
+def test_gemm_w8_rows_split_k_ignores_stale_workspace(C, CNT, kind):
+    """Kind 3: 128-column tiles at N = 384, then 64-column tiles (N = 352 is no multiple of 128) on their counters."""
+    stale_workspace_rounds(C, CNT, kind, (513, 384, 1600, 5), (255, 352, 320, 3))
+    assert C.gemm_last_launch() == "w8d256<64,3>"
 
 
 @pytest.mark.parametrize("kind,splits", [(2, 1), (2, 2), (3, 1), (3, 2)])

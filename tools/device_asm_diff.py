@@ -10,6 +10,12 @@ at every object and at every kernel entry of the `amdgpu_metadata` note.  Emissi
 labels lose their function number before chunks are compared by symbol.  The
 exit status is 0 when the two symbol sets and every chunk are equal; differing
 symbols are listed with a unified diff of their first differing chunk.
+
+    python tools/device_asm_diff.py --resources csrc/kernels/gemm.hip HEAD WORKTREE
+
+lists, for every kernel whose code or metadata differs, both revisions' VGPR,
+AGPR and SGPR counts, LDS and scratch bytes, spill counts (all from the kernel's
+metadata entry) and instruction count, instead of the diff.
 """
 from __future__ import annotations
 
@@ -79,7 +85,30 @@ def chunks(asm: str) -> dict:
     return out
 
 
+FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size",
+          "vgpr_spill_count", "sgpr_spill_count")
+FIELD = re.compile(r"^\s*(?:- )?\.(\w+):\s+(\d+)\s*$")
+INSTRUCTION = re.compile(r"^\s+[a-z]\w*(\s|$)")  # not a directive, a label or a comment
+
+
+def resources(ch: dict, kernel: str) -> list:
+    """[vgpr, agpr, sgpr, lds, scratch, vgpr spills, sgpr spills, instructions] of one kernel."""
+    meta = dict(m.groups() for m in map(FIELD.match, ch["meta:" + kernel]) if m)
+    return [int(meta[f]) for f in FIELDS] + [sum(1 for l in ch[kernel] if INSTRUCTION.match(l))]
+
+
+def report_resources(a: dict, b: dict, kernels: list) -> None:
+    print("vgpr agpr sgpr lds scratch vspill sspill insts: before -> after")
+    for k in kernels:
+        ra, rb = resources(a, k), resources(b, k)
+        print(subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip() or k)
+        print("    " + " ".join(str(x) if x == y else f"{x}->{y}" for x, y in zip(ra, rb)))
+
+
 def main(argv) -> int:
+    res = argv[1:2] == ["--resources"]
+    if res:
+        del argv[1]
     if len(argv) != 4:
         print(__doc__)
         return 2
@@ -95,7 +124,10 @@ def main(argv) -> int:
     differ = [s for s in a if s in b and a[s] != b[s]]
     for s in differ:
         print(f"differs: {s}")
-    if differ:
+    if res:
+        report_resources(a, b, [k[5:] for k in kernels if k[5:] in b and "meta:" + k[5:] in b and
+                                (k in differ or k[5:] in differ)])
+    elif differ:
         s = differ[0]
         print("\n".join(list(difflib.unified_diff(a[s], b[s], rev_a, rev_b, lineterm=""))[:80]))
     same = not (only_a or only_b or differ)
