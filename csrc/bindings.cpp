@@ -166,6 +166,24 @@ bool slab_bf16_enabled() {
   return g_slab_bf16 != 0;
 }
 
+constexpr auto kFP4 = c10::ScalarType::Float4_e2m1fn_x2;
+constexpr auto kE8M0 = c10::ScalarType::Float8_e8m0fnu;
+
+// An MXFP4 weight (csrc/kernels/wquant.hip): q packed E2M1 pairs [N, K / 2] and
+// e E8M0 scale bytes [N, K / 32], both contiguous GPU tensors, q's rows whole
+// 16-byte blocks (K % 32 == 0) at a 16-byte aligned base.  Returns K.
+int64_t need_mx4(const torch::Tensor& q, const torch::Tensor& e, const char* what) {
+  need(q, kFP4, "w");
+  need(e, kE8M0, "wscale");
+  TORCH_CHECK(q.dim() == 2 && q.is_contiguous() && q.size(0) >= 1 && q.size(1) >= 16 && q.size(1) % 16 == 0, what,
+              ": MXFP4 w must be contiguous [N, K / 2] with K % 32 == 0, got ", q.sizes());
+  TORCH_CHECK(aligned16(q), what, ": MXFP4 w must be 16-byte aligned");
+  TORCH_CHECK(e.dim() == 2 && e.is_contiguous() && e.size(0) == q.size(0) && e.size(1) * 16 == q.size(1), what,
+              ": MXFP4 wscale must be contiguous [N, K / 32] beside w [N, K / 2], got ", e.sizes(), " beside ",
+              q.sizes());
+  return q.size(1) * 2;
+}
+
 GemmParams base_params(const torch::Tensor& a, const torch::Tensor& w, int64_t tiled) {
   need(a, torch::kBFloat16, "a");
   need(w, torch::kBFloat16, "w");
@@ -218,6 +236,8 @@ GemmParams w8_params(const torch::Tensor& a, const torch::Tensor& w, const torch
 
 GemmParams gemm_params(const torch::Tensor& a, const torch::Tensor& w, const c10::optional<torch::Tensor>& wscale,
                        int64_t tiled, int epi, const char* what) {
+  TORCH_CHECK(w.scalar_type() != kFP4, what, ": the GEMMs read no MXFP4 weights; dequantise with dequant_rows_mxfp4 "
+              "into a bf16 scratch first (ops/hip.py _dense), or run the GEMV (at most 8 rows)");
   return wscale.has_value() ? w8_params(a, w, *wscale, tiled, epi, what) : base_params(a, w, tiled);
 }
 
@@ -357,7 +377,9 @@ torch::Tensor linear_qkv(torch::Tensor a, torch::Tensor w, c10::optional<torch::
 //   epi: 0 bf16, 1 gelu, 2 silu(gate)*up, 3 f32, 4 residual add into `resid`,
 //   6 QKV (q returned, k/v appended to the caches, optional RoPE).
 //   wscale: w holds FP8 E4M3 rows (csrc/kernels/wquant.hip) and wscale their
-//   fp32 scales [N]; the outputs are what the bf16 weight's would be.
+//   fp32 scales [N]; the outputs are what the bf16 weight's would be.  w of
+//   dtype float4_e2m1fn_x2 [N, K / 2] beside wscale of dtype float8_e8m0fnu
+//   [N, K / 32]: an MXFP4 weight, run by gemv_mxfp4_kernel.
 c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias,
                                   int64_t epi, int64_t norm, c10::optional<torch::Tensor> gamma,
                                   c10::optional<torch::Tensor> beta, double eps,
@@ -368,9 +390,16 @@ c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optiona
                                   c10::optional<torch::Tensor> rope,
                                   c10::optional<torch::Tensor> segmax = c10::nullopt,
                                   c10::optional<torch::Tensor> wscale = c10::nullopt) {
-  const bool w8 = wscale.has_value();
-  need(w, w8 ? torch::kFloat8_e4m3fn : torch::kBFloat16, "w");
-  need_rows(w, "w");
+  // an MXFP4 weight is named by either of its two dtypes, so a mismatched pair is refused by need_mx4
+  const bool w4 = wscale.has_value() && (w.scalar_type() == kFP4 || wscale->scalar_type() == kE8M0);
+  const bool w8 = wscale.has_value() && !w4;
+  TORCH_CHECK(wscale.has_value() || w.scalar_type() != kFP4, "gemv: an MXFP4 w needs its E8M0 wscale [N, K / 32]");
+  if (w4) {
+    need_mx4(w, *wscale, "gemv");
+  } else {
+    need(w, w8 ? torch::kFloat8_e4m3fn : torch::kBFloat16, "w");
+    need_rows(w, "w");
+  }
   if (w8) {
     need(*wscale, torch::kFloat32, "wscale");
     TORCH_CHECK(w.stride(0) % 16 == 0, "FP8 w rows must be 16-byte aligned");
@@ -380,9 +409,9 @@ c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optiona
   TORCH_CHECK(aligned16(x), "x must be 16-byte aligned");
   GemvParams p{};
   p.M = x.size(0); p.K = x.size(1); p.N = w.size(0);
-  TORCH_CHECK(w.size(1) == p.K, "K mismatch: x ", x.sizes(), " w ", w.sizes());
-  TORCH_CHECK(lsd_gemv_ok_w(p.M, p.K, (int)epi, (int)norm, w8), "gemv: shape M=", p.M, " K=", p.K,
-              " epi=", epi, " norm=", norm, w8 ? " (FP8 weights)" : "", " not supported");
+  TORCH_CHECK(w.size(1) * (w4 ? 2 : 1) == p.K, "K mismatch: x ", x.sizes(), " w ", w.sizes());
+  TORCH_CHECK(lsd_gemv_ok_w(p.M, p.K, (int)epi, (int)norm, w4 ? 2 : w8), "gemv: shape M=", p.M, " K=", p.K,
+              " epi=", epi, " norm=", norm, w4 ? " (MXFP4 weights)" : w8 ? " (FP8 weights)" : "", " not supported");
   p.W = bptr(w); p.ldw = w.stride(0);
   if (norm == 0) {
     need(x, torch::kBFloat16, "x");
@@ -440,7 +469,8 @@ c10::optional<torch::Tensor> gemv(torch::Tensor x, torch::Tensor w, c10::optiona
     TORCH_CHECK(false, "gemv: unknown epilogue ", epi);
   }
   TORCH_CHECK(!segmax.has_value() || epi == EPI_F32, "segmax needs the fp32 logits epilogue");
-  if (w8) check_hip(lsd_gemv_fp8(&p, wscale->data_ptr<float>(), (int)epi, (int)norm, cur_stream()), "gemv(fp8)");
+  if (w4) check_hip(lsd_gemv_mxfp4(&p, wscale->data_ptr(), (int)epi, (int)norm, cur_stream()), "gemv(mxfp4)");
+  else if (w8) check_hip(lsd_gemv_fp8(&p, wscale->data_ptr<float>(), (int)epi, (int)norm, cur_stream()), "gemv(fp8)");
   else check_hip(lsd_gemv(&p, (int)epi, (int)norm, cur_stream()), "gemv");
   return ret;
 }
@@ -472,6 +502,31 @@ torch::Tensor dequant_rows_fp8(torch::Tensor q, torch::Tensor scale, torch::Tens
   TORCH_CHECK(aligned16(q) && aligned16(out), "q and out must be 16-byte aligned");
   check_hip(lsd_dequant_rows_fp8(q.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), (int)N, (int)K, cur_stream()),
             "dequant_rows_fp8");
+  return out.flatten().narrow(0, 0, N * K).view({N, K});
+}
+
+// Weight-only MXFP4 (csrc/kernels/wquant.hip): w bf16 [N, K], K % 32 == 0 ->
+// (q float4_e2m1fn_x2 [N, K / 2], e float8_e8m0fnu [N, K / 32])
+std::tuple<torch::Tensor, torch::Tensor> quantize_rows_mxfp4(torch::Tensor w) {
+  need(w, torch::kBFloat16, "w");
+  need_rows(w, "w");
+  TORCH_CHECK(w.size(0) >= 1 && w.size(1) >= 32 && w.size(1) % 32 == 0,
+              "quantize_rows_mxfp4: K must be a multiple of 32, got ", w.sizes());
+  auto q = torch::empty({w.size(0), w.size(1) / 2}, w.options().dtype(kFP4));
+  auto e = torch::empty({w.size(0), w.size(1) / 32}, w.options().dtype(kE8M0));
+  check_hip(lsd_quantize_rows_mxfp4(w.data_ptr(), w.stride(0), q.data_ptr(), e.data_ptr(), (int)w.size(0),
+                                    (int)w.size(1), cur_stream()), "quantize_rows_mxfp4");
+  return {q, e};
+}
+
+// q, e -> bf16 [N, K] = e2m1(q) 2^X (exact) into the first N * K elements of `out`
+torch::Tensor dequant_rows_mxfp4(torch::Tensor q, torch::Tensor e, torch::Tensor out) {
+  const int64_t K = need_mx4(q, e, "dequant_rows_mxfp4"), N = q.size(0);
+  need(out, torch::kBFloat16, "out");
+  TORCH_CHECK(out.is_contiguous() && out.numel() >= N * K, "out must be contiguous with room for N * K elements");
+  TORCH_CHECK(aligned16(out), "out must be 16-byte aligned");
+  check_hip(lsd_dequant_rows_mxfp4(q.data_ptr(), e.data_ptr(), out.data_ptr(), (int)N, (int)K, cur_stream()),
+            "dequant_rows_mxfp4");
   return out.flatten().narrow(0, 0, N * K).view({N, K});
 }
 
@@ -1103,6 +1158,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // weight-only FP8 (wquant.hip)
   m.def("quantize_rows_fp8", &quantize_rows_fp8);
   m.def("dequant_rows_fp8", &dequant_rows_fp8);
+  // weight-only MXFP4 (wquant.hip)
+  m.def("quantize_rows_mxfp4", &quantize_rows_mxfp4);
+  m.def("dequant_rows_mxfp4", &dequant_rows_mxfp4);
   m.def("silu_mul", &silu_mul);
   m.def("apply_rows", &apply_rows, py::arg("args"), py::arg("b"));
   m.def("penalize", &penalize, py::arg("logits"), py::arg("V"), py::arg("hist"), py::arg("slots"),
@@ -1134,9 +1192,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("qkv_post", &qkv_post);
   // GEMV weight stream with non-temporal loads (A/B knob, LSD_GEMV_NT)
   m.def("gemv_set_nt", [](int64_t v) { lsd_gemv_set_nt((int)v); });
-  m.def("gemv_ok", [](int64_t M, int64_t K, int64_t epi, int64_t norm, bool w_fp8) {
-    return lsd_gemv_ok_w((int)M, (int)K, (int)epi, (int)norm, w_fp8 ? 1 : 0) != 0; },
-    py::arg("M"), py::arg("K"), py::arg("epi"), py::arg("norm"), py::arg("w_fp8") = false);
+  // w_fp8: the weight kind, 0 / False bf16, 1 / True FP8 E4M3, 2 MXFP4
+  m.def("gemv_ok", [](int64_t M, int64_t K, int64_t epi, int64_t norm, int64_t w_fp8) {
+    return lsd_gemv_ok_w((int)M, (int)K, (int)epi, (int)norm, (int)w_fp8) != 0; },
+    py::arg("M"), py::arg("K"), py::arg("epi"), py::arg("norm"), py::arg("w_fp8") = 0);
+  // MXFP4 GEMV: 1 its own rows per wave (default), 0 the bf16 kernel's (A/B knob)
+  m.def("gemv_set_mx4_wide", [](int64_t v) { lsd_gemv_set_mx4_wide((int)v); });
   m.def("set_stamps", &set_stamps);
   m.def("gemm_last_launch", [] { return std::string(lsd_gemm_last_launch()); });
   m.def("norm_last_launch", [] { return std::string(lsd_norm_last_launch()); });

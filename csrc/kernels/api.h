@@ -45,14 +45,19 @@ hipError_t lsd_gemm_w8(const lsd::GemmParams* p, const float* wscale, const lsd:
                        hipStream_t st);
 
 // gemv.hip
-int lsd_gemv_ok_w(int M, int K, int epi, int norm, int w_fp8);
+int lsd_gemv_ok_w(int M, int K, int epi, int norm, int wkind);  // 0 bf16, 1 FP8 E4M3, 2 MXFP4
 void lsd_gemv_set_nt(int v);
 hipError_t lsd_gemv(const lsd::GemvParams* p, int epi, int norm, hipStream_t st);
 hipError_t lsd_gemv_fp8(const lsd::GemvParams* p, const float* wscale, int epi, int norm, hipStream_t st);
+// MXFP4 rows (p->W nibble bytes, p->ldw in bytes) with E8M0 scale bytes wexp [N][K / 32]
+hipError_t lsd_gemv_mxfp4(const lsd::GemvParams* p, const void* wexp, int epi, int norm, hipStream_t st);
+void lsd_gemv_set_mx4_wide(int v);
 
 // wquant.hip
 hipError_t lsd_quantize_rows_fp8(const void* W, long ldw, void* q, float* scale, int N, int K, hipStream_t st);
 hipError_t lsd_dequant_rows_fp8(const void* q, const float* scale, void* out, int N, int K, hipStream_t st);
+hipError_t lsd_quantize_rows_mxfp4(const void* W, long ldw, void* q, void* e, int N, int K, hipStream_t st);
+hipError_t lsd_dequant_rows_mxfp4(const void* q, const void* e, void* out, int N, int K, hipStream_t st);
 
 // norm.hip
 hipError_t lsd_embed(const int* ids, const int* pos, const lsd_bf16_t* wte, const lsd_bf16_t* wpe, float* out, int T,

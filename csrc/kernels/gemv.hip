@@ -42,7 +42,50 @@
 //     row bring their own scales; segmax repeats the same fma.
 // The bf16 instantiations are the code they were (W8 = false folds every
 // branch below away).
+//
+// MXFP4 weights (WK = 2, gemv_mxfp4_kernel): the same kernel over W stored as
+// OCP Microscaling FP4 (wquant.hip, mx4.h) -- 17/64 of the bf16 bytes.
+//   * a lane's 16-byte load is one MX block: 32 E2M1 weights under one E8M0
+//     scale byte.  SLOTS = NB chunks per lane per row over the same K buckets
+//     and the same KS = 2048 NB element LDS image.  The scale byte of chunk c
+//     of a row is e[row][c]: the wave reads 64 consecutive bytes, requested in
+//     the same loop as the chunk itself (step 2), never after it.
+//   * v_cvt_scalef32_pk_bf16_fp4 takes the scale (the byte moved into an fp32
+//     exponent field) as its scale operand: the 16 converts of a chunk yield
+//     the exact dequantised bf16x2 pairs, shared by all MR activation rows.
+//     Nothing of the scale reaches the epilogue: y = acc + bias as on bf16; the
+//     FP8 kernel's e_sc / e_scp operands and its segmax fma have no counterpart.
+//   * LDS image.  A lane reads the 64 contiguous bytes of block c = lane + 64 i
+//     as four ds_read_b128 (16-byte chunks u = 4 c + d, d = 0..3), so in a
+//     linear image consecutive lanes are 64 bytes apart.  LDS serves a
+//     ds_read_b128 in groups of 16 lanes over 64 banks of 4 bytes, i.e. 16
+//     bank groups of 16 bytes, bank group = chunk address % 16; linear, the 16
+//     lanes of a group at one d hit chunks 4 c + d: only 4 distinct bank groups,
+//     a 4-way conflict.  The image is therefore stored swizzled (this kernel
+//     writes it itself in step 3): chunk u lives at
+//         (u & ~3) | ((u ^ (u >> 4)) & 3)    =  4 c + (d ^ ((c >> 2) & 3)).
+//     Bank check: a group is c = 16 g + t, t = 0..15; its bank group is
+//     4 (t & 3) + (d ^ (t >> 2)).  (t & 3, t >> 2) runs over all 16 pairs and
+//     XOR with the fixed d permutes the second member, so the 16 lanes hit 16
+//     distinct bank groups: every ds_read_b128 is conflict-free.  An
+//     activation row is 4096 NB bytes, a multiple of the 256-byte bank row, so
+//     the row m does not enter.  The step-3 stores write 16 consecutive chunks
+//     per 16 lanes; the swizzle permutes them inside one 256-byte bank row, so
+//     the stores stay conflict-free too (the norm prologue's 8-byte stores
+//     likewise move only inside their 64-byte block).
+//   * rows per wave.  At the bf16 kernel's CPW a lane has a quarter of its
+//     weight bytes outstanding and every workgroup still pays the whole
+//     activation prologue, so the MXFP4 kernel may own more rows per wave where
+//     V = CPW MR <= 16.  Measured (profiles/weight_mxfp4_ab.log, README "MXFP4
+//     weights"): the residual epilogue at CPW = 2 is faster than, or within 2 % of,
+//     the bf16 kernel's 1 on all four residual shapes (0.98-1.33x), SiLU at 4
+//     rows is faster at CPW = 4 (1.08x); the bf16 / GELU epilogues at CPW = 4
+//     lost to CPW = 2 (0.88-0.98x) and keep 2, as do QKV (same stream) and the
+//     fp32 logits (a workgroup stays one 8-column sampler segment).  mx4_cpw
+//     below is that rule; lsd_gemv_set_mx4_wide(0) launches the bf16 kernel's
+//     CPW instead (A/B).
 #include "common.h"
+#include "mx4.h"
 #include "gemm_params.h"
 #include "api.h"
 
@@ -158,8 +201,9 @@ constexpr bool gv_ok() {
 
 template <int MR, int CPW, int EPI, int NORM, int NB>
 __global__ __launch_bounds__(256) void gemv_kernel(GemvParams p) {
-  constexpr bool W8 = false;
+  constexpr int WK = 0;
   constexpr const float* wscale = nullptr;
+  constexpr const unsigned char* wexp = nullptr;
 #define LSD_GV_SYNC() __syncthreads()
 #define LSD_GV_BLOCK_SUMS block_sums
 #include "gemv_body.h"
@@ -171,12 +215,59 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvParams p) {
 // VALU forms (common.h LSD_NO_PK_F32), where HIP's __syncthreads() stays a call.
 template <int MR, int CPW, int EPI, int NORM, int NB>
 __global__ LSD_NO_PK_F32 __launch_bounds__(256) void gemv_fp8_kernel(GemvParams p, const float* wscale) {
-  constexpr bool W8 = true;
+  constexpr int WK = 1;
+  constexpr const unsigned char* wexp = nullptr;
 #define LSD_GV_SYNC() block_sync()
 #define LSD_GV_BLOCK_SUMS block_sums_nopk
 #include "gemv_body.h"
 #undef LSD_GV_SYNC
 #undef LSD_GV_BLOCK_SUMS
+}
+
+// MXFP4 blocks with E8M0 scale bytes wexp [N][K / 32]; compiled like the FP8 kernel.
+template <int MR, int CPW, int EPI, int NORM, int NB>
+__global__ LSD_NO_PK_F32 __launch_bounds__(256) void gemv_mxfp4_kernel(GemvParams p, const unsigned char* wexp) {
+  constexpr int WK = 2;
+  constexpr const float* wscale = nullptr;
+#define LSD_GV_SYNC() block_sync()
+#define LSD_GV_BLOCK_SUMS block_sums_nopk
+#include "gemv_body.h"
+#undef LSD_GV_SYNC
+#undef LSD_GV_BLOCK_SUMS
+}
+
+// W rows per wave of the MXFP4 kernel (header comment, "rows per wave")
+template <int EPI, int MR, int NB>
+constexpr int mx4_cpw() {
+  return EPI == gv::SILU && MR == 4 && NB == 2 ? 4 : 2;
+}
+
+template <int MR, int CPW, int EPI, int NORM, int NB>
+hipError_t gemv_mxfp4_go(const GemvParams& p, const unsigned char* wexp, hipStream_t st) {
+  hipLaunchKernelGGL((gemv_mxfp4_kernel<MR, CPW, EPI, NORM, NB>), dim3((p.N + 4 * CPW - 1) / (4 * CPW)), dim3(256),
+                     0, st, p, wexp);
+  return hipGetLastError();
+}
+
+template <int EPI, int NORM>
+hipError_t gemv_mxfp4_launch(const GemvParams& p, const unsigned char* wexp, int mr, int nb, bool wide,
+                             hipStream_t st) {
+#define LSD_GV(MR_, NB_)                                                                          \
+  if (mr == MR_ && nb == NB_) {                                                                   \
+    if constexpr (!gv_ok<MR_, NB_, NORM>()) {                                                     \
+      return hipErrorInvalidValue;                                                                \
+    } else {                                                                                      \
+      constexpr int NARROW = EPI == gv::RESID ? 1 : 2, WIDE = mx4_cpw<EPI, MR_, NB_>();           \
+      if (wide && WIDE != NARROW) return gemv_mxfp4_go<MR_, WIDE, EPI, NORM, NB_>(p, wexp, st);   \
+      return gemv_mxfp4_go<MR_, NARROW, EPI, NORM, NB_>(p, wexp, st);                             \
+    }                                                                                             \
+  }
+  LSD_GV(1, 1) LSD_GV(1, 2) LSD_GV(1, 4) LSD_GV(1, 7)
+  LSD_GV(2, 1) LSD_GV(2, 2) LSD_GV(2, 4) LSD_GV(2, 7)
+  LSD_GV(4, 1) LSD_GV(4, 2) LSD_GV(4, 4)
+  LSD_GV(8, 1) LSD_GV(8, 2)
+#undef LSD_GV
+  return hipErrorInvalidValue;
 }
 
 template <int EPI, int NORM, bool W8>
@@ -232,17 +323,21 @@ static int lsd_gemv_ok(int M, int K, int epi, int norm) {  // host code asks lsd
   }
 }
 
-// The same question for a weight type: 0 bf16, 1 FP8 E4M3 rows with per-row
-// scales.  The FP8 variant keeps the K buckets and the LDS image of the bf16
-// one (a 16-byte chunk is 16 weights, so a row takes half the chunks), so it
-// accepts what the bf16 kernel accepts wherever a row is whole chunks.
-extern "C" int lsd_gemv_ok_w(int M, int K, int epi, int norm, int w_fp8) {
-  if (w_fp8 && K % 16 != 0) return 0;
+// The same question for a weight kind: 0 bf16, 1 FP8 E4M3 rows with per-row
+// scales, 2 MXFP4 blocks.  Both variants keep the K buckets and the LDS image
+// of the bf16 one (a 16-byte chunk is 16 / 32 weights, so a row takes half / a
+// quarter of the chunks), so they accept what the bf16 kernel accepts wherever
+// a row is whole chunks.
+extern "C" int lsd_gemv_ok_w(int M, int K, int epi, int norm, int wkind) {
+  if (wkind < 0 || wkind > 2) return 0;
+  if (wkind && K % (16 * wkind) != 0) return 0;
   return lsd_gemv_ok(M, K, epi, norm);
 }
 
 static int g_gemv_nt = 0;
 extern "C" void lsd_gemv_set_nt(int v) { g_gemv_nt = v; }
+static int g_mx4_wide = 1;
+extern "C" void lsd_gemv_set_mx4_wide(int v) { g_mx4_wide = v; }
 
 // wscale != null: W holds E4M3 bytes (p.ldw in bytes) with those row scales
 template <bool W8>
@@ -277,4 +372,28 @@ extern "C" hipError_t lsd_gemv_fp8(const GemvParams* pin, const float* wscale, i
   GemvParams q = *pin;
   q.nt = g_gemv_nt;
   return gemv_dispatch<true>(q, wscale, epi, norm, st);
+}
+
+extern "C" hipError_t lsd_gemv_mxfp4(const GemvParams* pin, const void* wexp, int epi, int norm, hipStream_t st) {
+  if (!lsd_gemv_ok_w(pin->M, pin->K, epi, norm, 2) || wexp == nullptr) return hipErrorInvalidValue;
+  GemvParams p = *pin;
+  p.nt = g_gemv_nt;
+  const unsigned char* e = static_cast<const unsigned char*>(wexp);
+  const int mr = gv_mr(p.M), nb = gv_nb(p.K);
+  const bool wide = g_mx4_wide != 0;
+  switch (epi * 4 + norm) {
+    case gv::BF16 * 4 + gv::NONE: return gemv_mxfp4_launch<gv::BF16, gv::NONE>(p, e, mr, nb, wide, st);
+    case gv::GELU * 4 + gv::NONE: return gemv_mxfp4_launch<gv::GELU, gv::NONE>(p, e, mr, nb, wide, st);
+    case gv::GELU * 4 + gv::LN: return gemv_mxfp4_launch<gv::GELU, gv::LN>(p, e, mr, nb, wide, st);
+    case gv::SILU * 4 + gv::NONE: return gemv_mxfp4_launch<gv::SILU, gv::NONE>(p, e, mr, nb, wide, st);
+    case gv::SILU * 4 + gv::RMS: return gemv_mxfp4_launch<gv::SILU, gv::RMS>(p, e, mr, nb, wide, st);
+    case gv::F32 * 4 + gv::NONE: return gemv_mxfp4_launch<gv::F32, gv::NONE>(p, e, mr, nb, wide, st);
+    case gv::F32 * 4 + gv::LN: return gemv_mxfp4_launch<gv::F32, gv::LN>(p, e, mr, nb, wide, st);
+    case gv::F32 * 4 + gv::RMS: return gemv_mxfp4_launch<gv::F32, gv::RMS>(p, e, mr, nb, wide, st);
+    case gv::RESID * 4 + gv::NONE: return gemv_mxfp4_launch<gv::RESID, gv::NONE>(p, e, mr, nb, wide, st);
+    case gv::QKV * 4 + gv::NONE: return gemv_mxfp4_launch<gv::QKV, gv::NONE>(p, e, mr, nb, wide, st);
+    case gv::QKV * 4 + gv::LN: return gemv_mxfp4_launch<gv::QKV, gv::LN>(p, e, mr, nb, wide, st);
+    case gv::QKV * 4 + gv::RMS: return gemv_mxfp4_launch<gv::QKV, gv::RMS>(p, e, mr, nb, wide, st);
+    default: return hipErrorInvalidValue;
+  }
 }

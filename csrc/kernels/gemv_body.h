@@ -1,16 +1,20 @@
 // The body of the small-M GEMV kernels (gemv.hip), included once per weight
 // type so that each kernel is compiled from the text itself: the bf16 kernel
 // stays the code it was, the FP8-weight kernel carries its own target
-// attribute.  The including kernel provides
-//   W8                  constexpr bool: W holds E4M3 bytes (p.W a byte pointer,
-//                       p.ldw in bytes) and `wscale` the rows' fp32 scales
+// attribute, and so does the MXFP4-weight kernel.  The including kernel provides
+//   WK                  constexpr int, the weight kind: 0 bf16; 1 W holds E4M3
+//                       bytes (p.W a byte pointer, p.ldw in bytes) and `wscale`
+//                       the rows' fp32 scales; 2 W holds MXFP4 blocks (16 bytes
+//                       = 32 weights, p.W / p.ldw in bytes again) and `wexp`
+//                       their E8M0 scale bytes [N][K / 32]
 //   LSD_GV_SYNC()       the workgroup barrier
 //   LSD_GV_BLOCK_SUMS   block_sums over that barrier
 // and the template parameters MR, CPW, EPI, NORM, NB and `GemvParams p`.
   if constexpr (!gv_ok<MR, NB, NORM>()) {
     return;
   } else {
-    constexpr int SLOTS = W8 ? 2 * NB : 4 * NB;  // 16-byte chunks per lane per W row
+    constexpr bool W8 = WK == 1, W4 = WK == 2;
+    constexpr int SLOTS = W4 ? NB : W8 ? 2 * NB : 4 * NB;  // 16-byte chunks per lane per W row
     constexpr int KS = NB * 2048;                // LDS image row length (elements), zero past K
     constexpr int XCH = KS / 8;                  // 8-element chunks of an LDS image row
     constexpr int V = CPW * MR;      // partial sums per lane
@@ -20,7 +24,7 @@
     const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
     const int gw = blockIdx.x * 4 + w;
     const int KC = p.K >> 3;  // valid 16-byte chunks per row
-    const int KW = W8 ? p.K >> 4 : KC;  // ... per W row
+    const int KW = W4 ? p.K >> 5 : W8 ? p.K >> 4 : KC;  // ... per W row
     const int M = p.M;
 
     // ---- 0. the epilogue's own operands, fetched NOW (they do not depend on
@@ -86,9 +90,27 @@
 
     // ---- 2. the weight stream: every chunk of this wave's rows, issued now
     bf16x8 wv[W8 ? 1 : CPW][W8 ? 1 : SLOTS];
-    u32x4 wq[W8 ? CPW : 1][W8 ? SLOTS : 1];  // W8: 16 weights per chunk
+    u32x4 wq[W8 || W4 ? CPW : 1][W8 || W4 ? SLOTS : 1];  // W8: 16 weights per chunk, W4: 32
+    unsigned char we[W4 ? CPW : 1][W4 ? SLOTS : 1];      // W4: the chunks' scale bytes
     // waves past N re-read row N-1 (never stored)
-    if constexpr (W8) {
+    if constexpr (W4) {
+      // chunk c of a row and its scale byte e[row][c] are requested together: a
+      // wave's 64 lanes read 1 KiB of nibbles and 64 consecutive scale bytes
+      const unsigned char* wb = reinterpret_cast<const unsigned char*>(p.W);
+#pragma unroll
+      for (int j = 0; j < CPW; ++j) {
+        const long row = min(gv_row<EPI, CPW>(gw, j), p.N - 1);
+        const unsigned char* wr = wb + row * p.ldw;
+        const unsigned char* er = wexp + row * KW;
+#pragma unroll
+        for (int i = 0; i < SLOTS; ++i) {
+          const int c = min(lane + 64 * i, KW - 1);
+          if (p.nt) wq[j][i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wr + c * 16));
+          else wq[j][i] = *reinterpret_cast<const u32x4*>(wr + c * 16);
+          we[j][i] = er[c];
+        }
+      }
+    } else if constexpr (W8) {
       const unsigned char* wb = reinterpret_cast<const unsigned char*>(p.W);
       if (p.nt) {
 #pragma unroll
@@ -167,7 +189,8 @@
             if constexpr (NORM == gv::LN) z += bf2f(btv[i][e]);
             r[e] = f2bf((c < p.K && m < M) ? z : 0.f);
           }
-          st4(xs + m * KS + c, r);
+          if constexpr (W4) st4(xs + m * KS + mx4_swz(c >> 3) * 8 + (c & 7), r);
+          else st4(xs + m * KS + c, r);
         }
     } else {
       const bf16x8 zero = {};
@@ -175,7 +198,8 @@
       for (int i = 0; i < NA; ++i) {
         const int q = tid + 256 * i;
         const int m = q / XCH, c = q % XCH;
-        st8(xs + m * KS + c * 8, (m < M && c < KC) ? av[i] : zero);
+        if constexpr (W4) st8(xs + m * KS + mx4_swz(c) * 8, (m < M && c < KC) ? av[i] : zero);
+        else st8(xs + m * KS + c * 8, (m < M && c < KC) ? av[i] : zero);
       }
     }
     LSD_GV_SYNC();
@@ -196,7 +220,33 @@
     float acc[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) acc[v] = 0.f;
-    if constexpr (W8) {
+    if constexpr (W4) {
+#pragma unroll
+      for (int i = 0; i < SLOTS; ++i) {
+        const int c = lane + 64 * i;  // one MX block against LDS elements [32 c, 32 c + 32), swizzled
+        mx4_pair wb2[CPW][16];        // the exact dequantised pairs, shared by the MR rows
+#pragma unroll
+        for (int j = 0; j < CPW; ++j) mx4_cvt32(wq[j][i], mx4_scale(we[j][i]), wb2[j]);
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+          bf16x8 x[4];
+#pragma unroll
+          for (int d = 0; d < 4; ++d)
+            x[d] = *reinterpret_cast<const bf16x8*>(xs + m * KS + mx4_swz(4 * c + d) * 8);
+#pragma unroll
+          for (int j = 0; j < CPW; ++j)
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+              float a = acc[j * MR + m];
+              a = __builtin_amdgcn_fdot2_f32_bf16(wb2[j][4 * d + 0], LSD_PAIR(x[d], 0), a, false);
+              a = __builtin_amdgcn_fdot2_f32_bf16(wb2[j][4 * d + 1], LSD_PAIR(x[d], 1), a, false);
+              a = __builtin_amdgcn_fdot2_f32_bf16(wb2[j][4 * d + 2], LSD_PAIR(x[d], 2), a, false);
+              a = __builtin_amdgcn_fdot2_f32_bf16(wb2[j][4 * d + 3], LSD_PAIR(x[d], 3), a, false);
+              acc[j * MR + m] = a;
+            }
+        }
+      }
+    } else if constexpr (W8) {
 #pragma unroll
       for (int i = 0; i < SLOTS; ++i) {
         const int c = lane + 64 * i;  // 16 weights against LDS elements [16 c, 16 c + 16)

@@ -17,7 +17,23 @@
 //   * dequant_rows_fp8: the route of GEMMs the FP8 GEMV does not take
 //     (ops/hip.py): q, scale -> bf16 [N, K] in a caller's scratch, 16 bytes in
 //     and 2 x 16 bytes out per lane, one rounding (bf16(float(q) * scale)).
+//
+// Weight-only MXFP4 (mx4.h): W[N, K] bf16, K % 32 == 0 -> q[N, K/2] E2M1
+// nibbles + e[N, K/32] E8M0 bytes, one per 32 consecutive k of a row:
+//   amax = f 2^p, f in [1, 2)     (read off the fp32 bits of the block's max |w|)
+//   X    = p - 2 + (f > 1.5)      (smallest power of two with amax <= 6 2^X;
+//                                  clamped to [-126, 127]; 0 for a block of zeros)
+//   e    = X + 127,  q = e2m1_rne(w 2^-X) with w's sign bit,  W' = e2m1(q) 2^X
+// ops/reference.py quantize_mx4 is the same integer and exact-fp32 steps.
+//   * quantize_rows_mxfp4: a lane owns a whole block: 4 x 16 bytes in, 16
+//     bytes and one scale byte out, no cross-lane step.  Blocks are numbered
+//     row-major, so a wave covers 64 consecutive blocks (4 KiB of a row in, 1
+//     KiB + 64 scale bytes out, each contiguous).
+//   * dequant_rows_mxfp4: the route of every GEMM the MXFP4 GEMV does not
+//     take: 16 bytes + 1 in, 4 x 16 bytes out per lane through the convert the
+//     GEMV uses (v_cvt_scalef32_pk_bf16_fp4); exact, nothing is rounded.
 #include "common.h"
+#include "mx4.h"
 #include "api.h"
 
 namespace lsd {
@@ -89,6 +105,61 @@ __global__ LSD_NO_PK_F32 __launch_bounds__(256) void dequant_rows_fp8_kernel(
   st8(out + c * 16 + 8, o[1]);
 }
 
+// |w| 2^-X -> E2M1 code 0..7 of {0, .5, 1, 1.5, 2, 3, 4, 6}, ties to the even mantissa bit
+__device__ __forceinline__ unsigned int e2m1_code(float v) {
+  return (v > 0.25f) + (v >= 0.75f) + (v > 1.25f) + (v >= 1.75f) + (v > 2.5f) + (v >= 3.5f) + (v > 5.f);
+}
+
+__global__ LSD_NO_PK_F32 __launch_bounds__(256) void quantize_rows_mxfp4_kernel(
+    const bf16* __restrict__ W, long ldw, u32x4* __restrict__ q, unsigned char* __restrict__ e, int KB,
+    long blocks) {
+  const long b = (long)blockIdx.x * 256 + threadIdx.x;  // MX block of the [N, K / 32] grid
+  if (b >= blocks) return;
+  const bf16* src = W + (b / KB) * ldw + (b % KB) * 32;
+  bf16x8 v[4];
+#pragma unroll
+  for (int d = 0; d < 4; ++d) v[d] = ld8(src + 8 * d);
+  float m = 0.f;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) m = amax8(v[d], m);
+  const int bits = __builtin_bit_cast(int, m);
+  int X = (bits >> 23) - 129 + ((bits & 0x7FFFFF) > 0x400000 ? 1 : 0);
+  X = bits == 0 ? 0 : min(max(X, -126), 127);
+  const float inv = __builtin_bit_cast(float, (127 - X) << 23);  // 2^-X: the product below is exact
+  u32x4 o;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    unsigned int word = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float f = bf2f(v[d][i]);  // the sign is read off the fp32 (-0 keeps its bit)
+      word |= (e2m1_code(fabsf(f) * inv) | (__builtin_bit_cast(unsigned int, f) >> 31 << 3)) << (4 * i);
+    }
+    o[d] = word;
+  }
+  q[b] = o;
+  e[b] = (unsigned char)(X + 127);
+}
+
+__global__ LSD_NO_PK_F32 __launch_bounds__(256) void dequant_rows_mxfp4_kernel(
+    const u32x4* __restrict__ q, const unsigned char* __restrict__ e, bf16* __restrict__ out, long blocks) {
+  const long b = (long)blockIdx.x * 256 + threadIdx.x;
+  if (b >= blocks) return;
+  const float s = mx4_scale(e[b]);
+  mx4_pair pr[16];
+  mx4_cvt32(__builtin_nontemporal_load(q + b), s, pr);
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    bf16x8 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      o[2 * i] = pr[4 * d + i][0];
+      o[2 * i + 1] = pr[4 * d + i][1];
+    }
+    st8(out + b * 32 + 8 * d, o);
+  }
+}
+
 }  // namespace lsd
 
 using namespace lsd;
@@ -109,5 +180,27 @@ extern "C" hipError_t lsd_dequant_rows_fp8(const void* q, const float* scale, vo
   const long chunks = (long)N * (K >> 4);
   hipLaunchKernelGGL(dequant_rows_fp8_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st,
                      static_cast<const unsigned char*>(q), scale, static_cast<bf16*>(out), K >> 4, chunks);
+  return hipGetLastError();
+}
+
+// W bf16 [N][K] (row stride ldw elements, rows 16-byte aligned), K % 32 == 0;
+// q [N][K / 2] bytes and e [N][K / 32] bytes, both contiguous, q 16-byte aligned
+extern "C" hipError_t lsd_quantize_rows_mxfp4(const void* W, long ldw, void* q, void* e, int N, int K,
+                                              hipStream_t st) {
+  if (N < 1 || K < 32 || K % 32 != 0 || ldw % 8 != 0) return hipErrorInvalidValue;
+  const long blocks = (long)N * (K >> 5);
+  hipLaunchKernelGGL(quantize_rows_mxfp4_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st,
+                     static_cast<const bf16*>(W), ldw, static_cast<u32x4*>(q), static_cast<unsigned char*>(e),
+                     K >> 5, blocks);
+  return hipGetLastError();
+}
+
+// q, e as above and out bf16 [N][K] contiguous, 16-byte aligned
+extern "C" hipError_t lsd_dequant_rows_mxfp4(const void* q, const void* e, void* out, int N, int K, hipStream_t st) {
+  if (N < 1 || K < 32 || K % 32 != 0) return hipErrorInvalidValue;
+  const long blocks = (long)N * (K >> 5);
+  hipLaunchKernelGGL(dequant_rows_mxfp4_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st,
+                     static_cast<const u32x4*>(q), static_cast<const unsigned char*>(e), static_cast<bf16*>(out),
+                     blocks);
   return hipGetLastError();
 }

@@ -51,8 +51,9 @@ def main(argv=None) -> int:
     sub.choices["serve"].add_argument("--role")
     sub.choices["serve"].add_argument("--kv-dtype", dest="kv_dtype", choices=("bf16", "fp8_e4m3"),
                                       help="KV cache element type (fp8_e4m3: half the bytes, twice the slots)")
-    sub.choices["serve"].add_argument("--weight-dtype", dest="weight_dtype", choices=("bf16", "fp8_e4m3"),
-                                      help="block linear weights (fp8_e4m3: half the bytes streamed at small batch)")
+    sub.choices["serve"].add_argument("--weight-dtype", dest="weight_dtype", choices=("bf16", "fp8_e4m3", "mxfp4"),
+                                      help="block linear weights (fp8_e4m3: half, mxfp4: about a quarter of the "
+                                           "bytes streamed at small batch)")
     sub.choices["serve"].add_argument("--host", default="0.0.0.0")
     sub.choices["serve"].add_argument("--port", type=int,
                                       default=int(os.environ.get("PORT", os.environ.get("SHARD_PORT", "5000"))))

@@ -737,11 +737,12 @@ class EngineConfig:
     # element, values saturated to +-448, no scale factors): half the bytes the
     # decode attention streams and twice the slots in the same kv_fraction.
     kv_dtype: str = "bf16"
-    # Weights of the blocks' four linear projections: "bf16", or "fp8_e4m3"
+    # Weights of the blocks' four linear projections: "bf16", "fp8_e4m3"
     # (OCP E4M3 rows with one fp32 scale per output row, quantised when a stage
     # is prepared): half the bytes a small-batch decode step streams, and the
-    # freed memory goes to the KV cache.  Embeddings, lm_head, norms and biases
-    # stay bf16.
+    # freed memory goes to the KV cache; or "mxfp4" (OCP Microscaling FP4: E2M1
+    # nibbles with one E8M0 scale byte per 32 consecutive k of a row): 17/64 of
+    # the bf16 bytes.  Embeddings, lm_head, norms and biases stay bf16.
     weight_dtype: str = "bf16"
     # Serving: record per-stage busy / bubble timing on one pipeline session
     # in this many (0 = never) -- it costs a control-plane gather per session.
@@ -792,8 +793,8 @@ class EngineConfig:
     def __post_init__(self):
         if self.kv_dtype not in ("bf16", "fp8_e4m3"):
             raise ValueError(f"kv_dtype must be 'bf16' or 'fp8_e4m3', got {self.kv_dtype!r}")
-        if self.weight_dtype not in ("bf16", "fp8_e4m3"):
-            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8_e4m3', got {self.weight_dtype!r}")
+        if self.weight_dtype not in ("bf16", "fp8_e4m3", "mxfp4"):
+            raise ValueError(f"weight_dtype must be 'bf16', 'fp8_e4m3' or 'mxfp4', got {self.weight_dtype!r}")
         if not (0 <= self.prefix_cache <= self.max_batch):
             raise ValueError("prefix_cache must be in [0, max_batch]: an entry is one of the replica's KV slots")
         if self.prefix_cache_min_tokens < 1:

@@ -54,8 +54,11 @@ class ReferenceBackend(Backend):
     name = "reference"
 
     def prepare_stage(self, stage) -> None:
-        if getattr(stage, "weight_dtype", "bf16") == "fp8_e4m3":
+        wd = getattr(stage, "weight_dtype", "bf16")
+        if wd == "fp8_e4m3":
             ref.quantize_stage(stage)
+        elif wd == "mxfp4":  # a row that is not whole blocks of 32 (tiny-gpt2) stays as it is
+            ref.quantize_stage(stage, ref.quantize_mx4, keep=lambda t: t.shape[1] % 32 != 0)
 
     def embed(self, ids, pos, wte, wpe):
         return ref.embed(ids, pos, wte, wpe)

@@ -20,6 +20,17 @@ Device weight layout (set up once per stage by `prepare_stage`):
     up to w8_sk_max_m rows, one workgroup per 256-row block above); every
     other GEMM (prefill included) first dequantises the weight into a per-lane
     bf16 scratch and then runs exactly as it does on a bf16 weight.
+  * `weight_dtype="mxfp4"`: at the same point the same four projections become
+    OCP MXFP4 (csrc/kernels/wquant.hip, mx4.h): `float4_e2m1fn_x2` [N, K / 2]
+    with `w._lsd_scale` of dtype `float8_e8m0fnu` [N, K / 32], one scale byte
+    per 32 consecutive k of a row; a weight whose K is no multiple of 32
+    (tiny-gpt2) stays bf16.  The packed tensor's shape[1] is K / 2, so every
+    read of a weight's K below goes through `_wk` (the logical K).  At
+    M <= gemv_max_m rows the MXFP4 GEMV (gemv.hip) streams the blocks and
+    dequantises in its convert; every other GEMM (more rows, prefill, a shape
+    the GEMV refuses) dequantises into the same per-lane bf16 scratch first --
+    exactly, nothing is rounded -- and runs as on a bf16 weight.  No MFMA
+    kernel reads MXFP4 (`_w8` is false for it).
 """
 from __future__ import annotations
 
@@ -112,6 +123,8 @@ class LazyNorm:
 _EPI = {"none": 0, "gelu": 1, "silu_mul": 2}
 EPI_F32, EPI_RESID, EPI_QKV = 3, 4, 6
 FP8 = torch.float8_e4m3fn
+FP4 = torch.float4_e2m1fn_x2
+_WKIND = {FP8: 1, FP4: 2}  # gemv_ok's weight kind; 0: bf16
 # longest row the sampler loads once into registers (sample.hip: CH x NT x 4)
 SAMPLER_ONE_LOAD = 13 * 1024 * 4
 
@@ -142,6 +155,7 @@ class HipBackend(Backend):
         self.C.norm_set_wave_narrow_min(R.norm_wave_narrow_min)
         self.C.attn_set_max_wg(R.attn_max_wg)
         self.C.gemv_set_nt(R.gemv_nt)
+        self.C.gemv_set_mx4_wide(R.gemv_mx4_wide)
         self.C.attn_set_small_waves(R.attn_small_waves)
         self.C.attn_set_small_waves128(R.attn_small_waves128)
         self.C.attn_set_large_waves(64, R.attn_large_waves)
@@ -192,14 +206,17 @@ class HipBackend(Backend):
             # layer by layer, each bf16 tensor freed as it is replaced; a row that
             # is not whole 16-byte chunks of bytes (tiny-gpt2) stays bf16
             ref.quantize_stage(stage, self.C.quantize_rows_fp8, keep=lambda t: t.shape[1] % 16 != 0)
-            big = max((t.numel() for t in w.values() if t.dtype == FP8), default=0)
-            if big:
-                # bf16 scratch of the dequant route, one per microbatch lane (indexed
-                # by self.lane like the counters above).  A lane is one stream: the dequant kernel,
-                # the GEMM that reads the scratch and the next layer's dequant
-                # run in that order, so one buffer serves every layer -- in a
-                # captured graph too, whose nodes keep the stream's order.
-                self._wscratch = torch.empty(dequant_lanes(), big, dtype=torch.bfloat16, device=dev)
+        elif getattr(stage, "weight_dtype", "bf16") == "mxfp4":
+            # the same, in blocks of 32: a row that is not whole blocks (tiny-gpt2) stays bf16
+            ref.quantize_stage(stage, self.C.quantize_rows_mxfp4, keep=lambda t: t.shape[1] % 32 != 0)
+        big = max((t.shape[0] * self._wk(t) for t in w.values() if t.dtype in _WKIND), default=0)
+        if big:
+            # bf16 scratch of the dequant route, one per microbatch lane (indexed
+            # by self.lane like the counters above).  A lane is one stream: the dequant kernel,
+            # the GEMM that reads the scratch and the next layer's dequant
+            # run in that order, so one buffer serves every layer -- in a
+            # captured graph too, whose nodes keep the stream's order.
+            self._wscratch = torch.empty(dequant_lanes(), big, dtype=torch.bfloat16, device=dev)
         stage._hip_prepared = True
 
     @property
@@ -270,10 +287,15 @@ class HipBackend(Backend):
             return self.C.norm(xn.x, None, None, xn.w, xn.b, xn.eps, xn.rms, None, True)
         return xn
 
-    def _gemv_in(self, xn, K: int, epi: int, w8: bool = False):
+    @staticmethod
+    def _wk(w) -> int:
+        """A weight's logical K: an MXFP4 tensor packs two elements per byte."""
+        return w.shape[1] * 2 if w.dtype == FP4 else w.shape[1]
+
+    def _gemv_in(self, xn, K: int, epi: int, w8: int = 0):
         """(x, norm code, gamma, beta, eps) for a GEMV launch, or None when this
         GEMM does not run on the GEMV (the caller takes the MFMA path).  `w8`:
-        the weight is FP8 rows (the GEMV's FP8 variant answers)."""
+        the weight kind, 1 FP8 rows, 2 MXFP4 blocks (that GEMV variant answers)."""
         M = xn.shape[0]
         if M > self.R.gemv_max_m:
             return None
@@ -287,8 +309,8 @@ class HipBackend(Backend):
 
     @staticmethod
     def _ws(w) -> dict:
-        """The GEMV's extra argument for an FP8 weight: its row scales."""
-        return {"wscale": w._lsd_scale} if w.dtype == FP8 else {}
+        """The GEMV's extra argument for an FP8 or MXFP4 weight: its scales."""
+        return {"wscale": w._lsd_scale} if w.dtype in _WKIND else {}
 
     def _w8(self, M: int, w, epi: int) -> bool:
         """This decode GEMM streams its FP8 weight in an FP8-weight kernel."""
@@ -304,14 +326,15 @@ class HipBackend(Backend):
         return 0, (self.R.w8_resid_splits(M, N, K, lanes) if resid else self.R.w8_splits(M, N, K, lanes, nw))
 
     def _dense(self, w):
-        """The weight a GEMM other than the FP8 GEMV reads: an FP8 weight is
-        dequantised into this lane's scratch (wquant.hip), a bf16 one is itself."""
-        if w.dtype != FP8:
+        """The weight a GEMM other than the FP8 / MXFP4 GEMV reads: a quantised
+        weight is dequantised into this lane's scratch (wquant.hip), a bf16 one is itself."""
+        if w.dtype not in _WKIND:
             return w
-        return self.C.dequant_rows_fp8(w, w._lsd_scale, self._wscratch[self.lane % self._wscratch.shape[0]])
+        dq = self.C.dequant_rows_mxfp4 if w.dtype == FP4 else self.C.dequant_rows_fp8
+        return dq(w, w._lsd_scale, self._wscratch[self.lane % self._wscratch.shape[0]])
 
     def qkv_kv_append(self, xn, w, b, cache_k, cache_v, meta, mcfg):
-        g = self._gemv_in(xn, w.shape[1], EPI_QKV, w.dtype == FP8)
+        g = self._gemv_in(xn, self._wk(w), EPI_QKV, _WKIND.get(w.dtype, 0))
         if g is not None:
             x, nc, gw, gb, eps = g
             return self.C.gemv(x, w, b, EPI_QKV, nc, gw, gb, eps, kc=cache_k, vc=cache_v,
@@ -349,7 +372,7 @@ class HipBackend(Backend):
 
     def linear(self, a, w, b=None, act: str = "none"):
         code = _EPI[act]
-        g = self._gemv_in(a, w.shape[1], code, w.dtype == FP8)
+        g = self._gemv_in(a, self._wk(w), code, _WKIND.get(w.dtype, 0))
         if g is not None:
             x, nc, gw, gb, eps = g
             return self.C.gemv(x, w, b, code, nc, gw, gb, eps, **self._ws(w))
@@ -373,7 +396,7 @@ class HipBackend(Backend):
     def linear_residual(self, a, w, b, r: Residual) -> None:
         M, K = a.shape
         N = w.shape[0]
-        if self._gemv_in(a, K, EPI_RESID, w.dtype == FP8) is not None:  # adds straight into r.x
+        if self._gemv_in(a, K, EPI_RESID, _WKIND.get(w.dtype, 0)) is not None:  # adds straight into r.x
             self.C.gemv(a, w, b, EPI_RESID, 0, None, None, 0.0, resid=r.x, **self._ws(w))
             return
         if self._w8(M, w, EPI_RESID):

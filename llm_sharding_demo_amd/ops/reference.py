@@ -64,11 +64,51 @@ def dequantize_rows(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return q.float() * scale[:, None]
 
 
+FP4 = torch.float4_e2m1fn_x2
+E8M0 = torch.float8_e8m0fnu
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_mx4(w: torch.Tensor):
+    """Weight-only OCP MXFP4: w [N, K], K % 32 == 0 -> (q float4_e2m1fn_x2
+    [N, K/2], e float8_e8m0fnu [N, K/32]).  Element 2i sits in bits 3:0 of byte
+    i, element 2i+1 in bits 7:4; one biased exponent byte per 32 consecutive k.
+    Per block: amax = f 2^p, f in [1, 2), read off the fp32 bits; X = p - 2 +
+    (f > 1.5), the smallest power of two with amax <= 6 2^X (nothing
+    saturates), clamped to [-126, 127], 0 for a block of zeros; the byte is
+    X + 127.  q = e2m1_rne(w / 2^X) (the division is an exact multiply by
+    2^-X), ties to the even mantissa bit, the sign bit is w's.  All integer and
+    exact fp32 steps, so csrc/kernels/wquant.hip reproduces it bit for bit."""
+    N, K = w.shape
+    assert K % 32 == 0, "MXFP4 rows are whole blocks of 32"
+    wf = w.float().reshape(N, K // 32, 32)
+    bits = wf.abs().amax(dim=2).view(torch.int32)
+    X = (bits >> 23) - 129 + ((bits & 0x7FFFFF) > 0x400000).int()
+    X = torch.where(bits == 0, torch.zeros_like(X), X.clamp(-126, 127))
+    v = wf.abs() * ((127 - X) << 23).view(torch.float32)[:, :, None]
+    code = ((v > 0.25).int() + (v >= 0.75).int() + (v > 1.25).int() + (v >= 1.75).int()
+            + (v > 2.5).int() + (v >= 3.5).int() + (v > 5.0).int())
+    nib = (code | (torch.signbit(wf).int() << 3)).reshape(N, K // 2, 2)
+    q = (nib[:, :, 0] | (nib[:, :, 1] << 4)).to(torch.uint8)
+    return q.view(FP4), (X + 127).to(torch.uint8).view(E8M0)
+
+
+def dequantize_mx4(q: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """fp32 [N, K] = e2m1(q) 2^X: exact, and exact in bf16 wherever the product
+    is in bf16's normal range."""
+    b = q.view(torch.uint8).int()
+    nib = torch.stack([b & 15, b >> 4], dim=2).reshape(b.shape[0], -1)
+    val = torch.tensor(_E2M1, device=q.device)[(nib & 7).long()] * (1.0 - 2.0 * (nib >> 3).float())
+    scale = (e.view(torch.uint8).int() << 23).view(torch.float32)
+    return val * scale.repeat_interleave(32, dim=1)
+
+
 def quantize_stage(stage, quantize=quantize_rows, keep=lambda w: False) -> None:
     """Replace the four linear projections of every block a stage owns by
-    their FP8 rows, one tensor at a time (each original is dropped as it is
+    their quantised rows (FP8 by default; quantize_mx4 for MXFP4), one tensor
+    at a time (each original is dropped as it is
     replaced); the scales ride on the tensor as `_lsd_scale`.  `keep(w)`: a
-    weight the backend cannot take in FP8 stays as it is."""
+    weight the backend cannot take quantised stays as it is."""
     p = "h." if stage.cfg.arch == "gpt2" else "layers."
     for i in stage.layers:
         for name in stage.cfg.block_linears():
@@ -81,10 +121,12 @@ def quantize_stage(stage, quantize=quantize_rows, keep=lambda w: False) -> None:
 
 
 def linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """a [T, K] @ w[N, K]^T (+ bias) in fp32; an FP8 weight (quantize_rows) is
-    dequantised first."""
+    """a [T, K] @ w[N, K]^T (+ bias) in fp32; an FP8 weight (quantize_rows)
+    or an MXFP4 one (quantize_mx4) is dequantised first."""
     if w.dtype == torch.float8_e4m3fn:
         out = a.float() @ dequantize_rows(w, w._lsd_scale).t()
+    elif w.dtype == FP4:
+        out = a.float() @ dequantize_mx4(w, w._lsd_scale).t()
     else:
         out = a.float() @ w.float().t()
     if bias is not None:

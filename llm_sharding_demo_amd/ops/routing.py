@@ -38,6 +38,7 @@ class Routing:
     gemv_max_m: int = 8
     gemv_norm_max_m: int = 2
     gemv_nt: int = 0  # non-temporal weight loads in the GEMV (A/B)
+    gemv_mx4_wide: int = 1  # MXFP4 GEMV: its own rows per wave (gemv.hip mx4_cpw); 0: the bf16 kernel's (A/B)
     # -- decode attention --------------------------------------------------
     target_blocks: int = 512  # >> 256 CUs: VALU decode attention splits the context up to this
     split_keys: int = 256      # ... with at least this many keys per split (64 / 128 lose at 1-16

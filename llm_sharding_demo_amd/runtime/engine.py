@@ -347,6 +347,12 @@ class Engine(racecheck.Shared):
             lin = mc.block_linears().values()
             per_layer += sum(4 * n_ - n_ * k_ for n_, k_ in lin)
             scratch = dequant_lanes() * 2 * max(n_ * k_ for n_, k_ in lin) if b > a else 0
+        elif self.cfg.weight_dtype == "mxfp4":
+            # half a byte per quantised element and a scale byte per 32 of them
+            # (a row that is not whole blocks stays bf16), plus the same scratch
+            lin = [(n_, k_) for n_, k_ in mc.block_linears().values() if k_ % 32 == 0]
+            per_layer += sum(n_ * k_ // 2 + n_ * k_ // 32 - 2 * n_ * k_ for n_, k_ in lin)
+            scratch = dequant_lanes() * 2 * max(n_ * k_ for n_, k_ in lin) if b > a and lin else 0
         n = per_layer * (b - a) // 2 + scratch
         if i == 0:
             n += mc.embed_params() * 2

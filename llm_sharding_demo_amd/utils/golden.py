@@ -42,8 +42,8 @@ def compare_with_golden(model_id, prompts: List[List[int]], steps: int = 8,
     is {"golden_kv": metrics of golden/kv_dtype vs golden/fp32,
         "hip_kv":    metrics of HIP/kv_dtype vs golden/fp32}.
 
-    `weight_dtype="fp8_e4m3"` gives the HIP model FP8 weights (EngineConfig's
-    field).  Its reference is then the fp32 golden over the *dequantised*
+    `weight_dtype="fp8_e4m3"` (or `"mxfp4"`) gives the HIP model FP8 (MXFP4)
+    weights (EngineConfig's field).  Its reference is then the fp32 golden over the *dequantised*
     weights -- the same numbers the kernels multiply by -- and the result is
     {"hip_w":    metrics of HIP/FP8 weights vs golden over dequantised weights,
      "golden_w": metrics of that golden vs the golden over the bf16 weights:
